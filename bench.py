@@ -37,6 +37,14 @@ bytes; the walk is bound by the latency of several hundred dependent passes, not
 in this run) is the ceiling the design can be held to, `frac_of_latency_ceiling` how close it is.
 `cpu_baseline` = the oracle (oracle/mode_r.c, a C port of the reference's sequential search,
 in-memory — an upper bound on what the BEAM service could do) timed on this box's host cores.
+
+A plain run (`--gpus N --steps K --warmup W`) does what the headline needs and nothing more: it sets up, warms up, times
+the K steps and prints the line (value, ms_per_step, exactness, path, and the roofline arithmetic of the timed steps
+without the two figures that take runs of their own, boundary_us and predicate_tests_physical).  `--full` adds every
+other leg and measurement: cpu_baseline, cfg3, pcie_inclusive, shared_pool_n1 with its sharding_prediction,
+concurrent_pools (weak_scaling and the one-GPU speed-up at N > 1), the stream legs, the kernel-boundary measurement and
+the predicate-test probe; the --no-* options switch single legs of a --full run off.  `--dump-outputs DIR` writes the
+match list of the last timed step (dump_outputs) after the clock has stopped.
 """
 import argparse
 import hashlib
@@ -322,7 +330,49 @@ def parse():
                          "gathers, the one JSON line; the line says same_device and its value is NOT a scaling number")
     ap.add_argument("--traffic-json", default=None,
                     help="optional PMC summary written by tools/make_traffic.py (default: profiles/traffic_latest*.json)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: cpu_baseline, the secondary legs (cfg3, pcie_inclusive, "
+                         "shared_pool_n1 + sharding_prediction, concurrent_pools; weak_scaling and the one-GPU speed-up at N>1), "
+                         "the stream legs, the kernel-boundary measurement and the predicate-test probe; the --no-* options "
+                         "switch single legs off again.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the match list of the last timed step as DIR/<name>.npy (float32 / "
+                         "float64; at N>1 one set per rank, DIR/<name>_rank<r>.npy), at most 64 MB in all")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline only: every leg and extra measurement beside it is --full's
+        args.no_cpu_baseline = args.no_secondary = args.no_stream = args.no_boundary = args.no_probe = True
+    return args
+
+
+DUMP_BYTES_MAX = 64_000_000
+
+
+def dump_outputs(out_dir, m, ids, rank=0, world=1, budget=DUMP_BYTES_MAX):
+    """--dump-outputs: the match list a caller of the timed step receives (mm_matches: slot handles, score, rating group and
+    pass of every lobby, in emission order) and the players' global arrival indices behind the handles, as .npy files.
+    Integer arrays go out as float64 (exact for every uint32).  A list larger than this rank's share of `budget` is cut to
+    a fixed, seeded sample of lobbies, the same rows in every array; `rows` holds their indices in the list.
+    m None: a rank that holds no players (its arrays are empty).  Returns {name: path}."""
+    os.makedirs(out_dir, exist_ok=True)
+    if m is None:
+        from microservice_matchmaking_amd._abi import Matches
+        m, ids = Matches(np.zeros((0, 1), np.uint32), np.zeros(0, np.float32), np.zeros(0, np.uint32),
+                         np.zeros(0, np.uint32), {}), np.zeros((0, 1), np.int64)
+    n, L = m.slots.shape
+    per_lobby = 2 * 8 * L + 4 + 3 * 8               # slots and players, score, group, pass, rows
+    keep = max(1, budget // max(world, 1) // per_lobby)
+    rows = np.arange(n, dtype=np.int64)
+    if n > keep:
+        rows = np.sort(np.random.default_rng(12345).choice(n, size=keep, replace=False))
+    arrays = {"slots": m.slots[rows].astype(np.float64), "players": np.asarray(ids)[rows].astype(np.float64),
+              "score": m.score[rows].astype(np.float32), "group": m.group[rows].astype(np.float64),
+              "pass": m.pass_[rows].astype(np.float64), "rows": rows.astype(np.float64)}
+    out = {}
+    for name, a in arrays.items():
+        out[name] = os.path.join(out_dir, "%s%s.npy" % (name, "_rank%d" % rank if world > 1 else ""))
+        np.save(out[name], a)
+    return out
 
 
 def cpu_baseline(cfg, rating, cons, mode_name, budget_s=20.0):
@@ -755,10 +805,11 @@ def main():
             pools[key] = make_pool(n, seed=1, dist=args.dist, **w["pool_kw"])
         return pools[key]
 
-    def shared_pool_run(w, n, nranks, r, steps, warmup, timing=True, collective=True):
+    def shared_pool_run(w, n, nranks, r, steps, warmup, timing=True, collective=True, dump_dir=None):
         """One pool of n players, sharded over nranks by chain; this process plays rank r of them.
         Returns (elapsed of the timed steps, last tick, per-step timers, my digests, the sharding, players
-        held, the pool).  collective=False: a single-process run (no barrier with the other ranks)."""
+        held, the pool).  collective=False: a single-process run (no barrier with the other ranks).
+        dump_dir: the last timed tick's match list goes there (dump_outputs), after the clock has stopped."""
         rating, cons = pool_of(w, n)
         modes = w["modes"]
         cfg1 = make_config(modes, capacity=16, device=local_rank, timing=False)
@@ -805,6 +856,10 @@ def main():
                        if sh.chain_owner[c] == r}
             timers["path"] = eng.path_stats()        # mm_path_stats_get: the launch shapes and fall-backs of the last timed tick
             eng.close()
+            if dump_dir:
+                dump_outputs(dump_dir, last, ids, r, nranks)
+        elif dump_dir:
+            dump_outputs(dump_dir, None, None, r, nranks)          # a rank without chains: its (empty) list all the same
         return elapsed, last, timers, digests, sh, int(idx.size), (rating, cons)
 
     def secondary_pool_leg(w, n, steps, traffic_path=None):
@@ -838,7 +893,8 @@ def main():
 
     # ------------------------------------------------------------------ the main leg
     n = args.players if args.players else (1_000_000 if world == 1 else 10_000_000)
-    elapsed, last, timers, digests, sh, n_mine, (rating, cons) = shared_pool_run(wl, n, world, rank, args.steps, args.warmup)
+    elapsed, last, timers, digests, sh, n_mine, (rating, cons) = shared_pool_run(wl, n, world, rank, args.steps, args.warmup,
+                                                                                 dump_dir=args.dump_outputs)
     st = last.stats if last is not None else {"players_matched": 0, "pairs": 0, "passes_max": 0}
     part = {"rank": rank, "elapsed": elapsed, "players": n_mine, "matched_per_step": int(st["players_matched"]),
             "pairs": int(st["pairs"]), "passes_max": int(st["passes_max"]),
@@ -884,6 +940,7 @@ def main():
                            ("torch.distributed.run / env" if world > 1 else "single process"),
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),                 # False: the headline alone (the legs beside it are --full's)
             "ms_per_step": step_ms,
             # the K timed steps one by one (host clock; the slowest rank's): what the mean above hides — runs of this line on
             # one box have differed by 8 %, so a reader can tell a regression from the box

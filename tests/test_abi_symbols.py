@@ -48,21 +48,21 @@ def test_oracle_exports_the_mirrored_abi(oracle_cls):
         assert hasattr(olib, "mo_" + n[3:]), n
 
 
-def test_struct_layouts_match_the_header(lib):
+def test_struct_layouts_match_the_header(lib, tmp_path):
     # sizes the C compiler gives the header's structs, via a tiny probe program
     probe = r'''
 #include <stdio.h>
 #include "mm_engine.h"
 int main(void){printf("%zu %zu %zu %zu %zu\n", sizeof(mm_config), sizeof(mm_mode_config), sizeof(mm_stats), sizeof(mm_enqueue_stats), sizeof(mm_path_stats));return 0;}
 '''
-    exe = "/tmp/mm_abi_probe"
+    exe = str(tmp_path / "mm_abi_probe")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe],
                    input=probe.encode(), check=True)
     sizes = [int(x) for x in subprocess.check_output([exe]).split()]
     assert sizes == [C.sizeof(MMConfig), C.sizeof(MMModeConfig), C.sizeof(MMStats), C.sizeof(MMEnqueueStats), C.sizeof(MMPathStats)]
 
 
-def test_tuning_record_by_name_and_by_layout(lib, monkeypatch):
+def test_tuning_record_by_name_and_by_layout(lib, monkeypatch, tmp_path):
     """mm_tuning (include/mm_engine.h): every uint32_t field of the header's struct has its name in mm_tuning_name, in the
     struct's order; mm_tuning_default fills as many bytes as the caller has room for; mm_tuning_set checks names and
     ranges; the MM_* environment supplies defaults only, and a value that is not one is reported and ignored (ADVICE r05:
@@ -75,7 +75,7 @@ def test_tuning_record_by_name_and_by_layout(lib, monkeypatch):
     fields = re.findall(r"^\s*uint32_t\s+(\w+);", body, re.M)
     assert fields[0] == "size" and fields[1:] == Engine.tuning_names() and len(fields) >= 30
     probe = '#include <stdio.h>\n#include "mm_engine.h"\nint main(void){printf("%zu\\n", sizeof(mm_tuning));return 0;}\n'
-    exe = "/tmp/mm_tuning_probe"
+    exe = str(tmp_path / "mm_tuning_probe")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=probe.encode(), check=True)
     assert int(subprocess.check_output([exe])) == 4 * len(fields)
     for k in list(os.environ):

@@ -161,7 +161,7 @@ def test_bench_main_dry_run_prints_one_contract_line(monkeypatch, mode):
     monkeypatch.setattr(pkg, "Engine", DryEngine)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--players", "12000", "--steps", "2", "--warmup", "1", "--mode", mode,
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--players", "12000", "--steps", "2", "--warmup", "1", "--mode", mode,
                                       "--stream-seconds", "0.1", "--stream-qps", "20000", "--cpu-baseline-seconds", "0.5",
                                       "--concurrent-pools", "2", "--shared-players", "20000",
                                       "--saturation-qps", "20000", "--saturation-seconds", "0.1"])
@@ -175,7 +175,7 @@ def test_bench_main_dry_run_prints_one_contract_line(monkeypatch, mode):
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
     assert d["metric"].startswith("matched players/sec") and d["unit"] == "matched players/s"
-    assert (d["n_gpus"], d["steps"], d["warmup"]) == (1, 2, 1)
+    assert (d["n_gpus"], d["steps"], d["warmup"]) == (1, 2, 1) and d["full"] is True
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None
     assert d["data"] == "synthetic" and "workload" in d["config"] and "model" not in d["config"]
     assert d["value"] == pytest.approx(d["matched_fraction"] * 12000 / (d["ms_per_step"] * 1e-3), rel=1e-6)
@@ -236,6 +236,92 @@ def test_bench_main_dry_run_prints_one_contract_line(monkeypatch, mode):
         assert set(np.asarray([len(d["latency_mixed"]["per_mode"])])) == {2}
 
 
+class CountingDryEngine(DryEngine):
+    ticks = 0
+
+    def tick(self, mode=0, reuse=False):
+        CountingDryEngine.ticks += 1
+        return super().tick(mode, reuse=reuse)
+
+
+@pytest.mark.parametrize("mode", ["1v1", "5v5"])
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(monkeypatch, tmp_path, mode):
+    """A plain run (no --full): warm-up + --steps ticks and nothing else, the contract fields, no leg beside the headline;
+    --dump-outputs writes the last timed step's match list, and a second run with the same pool writes the same arrays."""
+    import torch
+    import microservice_matchmaking_amd as pkg
+    from microservice_matchmaking_amd.sharding import tick_digests, union_digest
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: self)
+    monkeypatch.setattr(pkg, "Engine", CountingDryEngine)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+
+    def run(steps, warmup, out_dir):
+        CountingDryEngine.ticks = 0
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--players", "12000", "--steps", str(steps), "--warmup",
+                                          str(warmup), "--mode", mode, "--dump-outputs", str(out_dir)])
+        out = io.StringIO()
+        with redirect_stdout(out):
+            bench.main()
+        lines = [ln for ln in out.getvalue().splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        assert CountingDryEngine.ticks == steps + warmup
+        return json.loads(lines[0])
+
+    d = run(3, 2, tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "exactness", "roofline"):
+        assert k in d, k
+    assert (d["steps"], d["warmup"], d["full"]) == (3, 2, False) and d["ms_per_step"] > 0
+    assert d["metric"].startswith("matched players/sec") and d["higher_is_better"] is True and d["dtype"] == "int32"
+    assert d["value"] == pytest.approx(d["matched_fraction"] * 12000 / (d["ms_per_step"] * 1e-3), rel=1e-6)
+    for leg in ("cpu_baseline", "cfg3", "pcie_inclusive", "shared_pool_n1", "concurrent_pools", "latency",
+                "latency_saturation", "latency_mixed", "weak_scaling"):
+        assert leg not in d, leg
+    assert d["roofline"]["boundary_us"] is None and d["roofline"]["predicate_tests_physical"] is None
+    assert d["exactness"]["ok"] is True
+    names = ("slots", "players", "score", "group", "pass", "rows")
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in names)
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_BYTES_MAX
+    lobbies, L = a["slots"].shape
+    assert L == (2 if mode == "1v1" else 10) and a["players"].shape == (lobbies, L)
+    assert len(a["score"]) == len(a["group"]) == len(a["pass"]) == len(a["rows"]) == lobbies
+    assert np.array_equal(a["rows"], np.arange(lobbies)) and a["players"].size == round(d["matched_fraction"] * 12000)
+    # the arrays are the list the line's emission digest was taken over
+    assert union_digest(tick_digests(0, 7, a["players"].astype(np.int64), a["group"].astype(np.uint32))) == \
+        d["exactness"]["emission_digest"]
+    run(2, 1, tmp_path / "b")
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "b" / (n + ".npy")), a[n]), n
+
+
+def test_bench_dump_outputs_samples_a_large_list_within_its_budget(tmp_path):
+    """A match list larger than the budget: a fixed, seeded sample of lobbies, the same rows in every array; per rank at N > 1."""
+    from microservice_matchmaking_amd._abi import Matches
+    n, L = 50_000, 2
+    rng = np.random.default_rng(3)
+    m = Matches(rng.integers(0, 1 << 20, (n, L)).astype(np.uint32), rng.random(n).astype(np.float32),
+                rng.integers(0, 7, n).astype(np.uint32), rng.integers(0, 500, n).astype(np.uint32), {})
+    ids = m.slots.astype(np.int64) + 7
+    budget = 200_000
+    p1 = bench.dump_outputs(str(tmp_path / "a"), m, ids, budget=budget)
+    p2 = bench.dump_outputs(str(tmp_path / "b"), m, ids, budget=budget)
+    a = {k: np.load(v) for k, v in p1.items()}
+    assert sum(x.nbytes for x in a.values()) <= budget and 0 < len(a["rows"]) < n
+    rows = a["rows"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["slots"], m.slots[rows]) and np.array_equal(a["players"], ids[rows].astype(np.float64))
+    assert np.array_equal(a["score"], m.score[rows]) and np.array_equal(a["pass"], m.pass_[rows])
+    for k, v in p2.items():
+        assert np.array_equal(np.load(v), a[k]), k
+    p3 = bench.dump_outputs(str(tmp_path / "c"), None, None, rank=7, world=8, budget=budget)
+    assert os.path.basename(p3["slots"]) == "slots_rank7.npy" and np.load(p3["players"]).size == 0
+
+
 @pytest.mark.parametrize("world", [2, 8])
 def test_bench_ranks_dry_run_shards_one_pool(world, oracle_cls):
     """`bench.py --gpus N` as the driver launches it (one process per rank, env rendezvous on
@@ -253,7 +339,7 @@ def test_bench_ranks_dry_run_shards_one_pool(world, oracle_cls):
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0",   # the shim has one device
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, worker, "--gpus", str(world), "--players", "12000", "--steps", "2",
+        procs.append(subprocess.Popen([sys.executable, worker, "--full", "--gpus", str(world), "--players", "12000", "--steps", "2",
                                        "--warmup", "1", "--weak-players", "6000", "--stream-seconds", "0.1",
                                        "--stream-qps", "20000"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
     outs = [p.communicate(timeout=900) for p in procs]

@@ -29,6 +29,6 @@ for MODE in 1v1 5v5; do
   # 4 timed + 1 warm-up tick were profiled
   python "$R/tools/make_traffic.py" "$OUT/${TAG}_pmc_fetch_size_1m_$MODE.csv" "$OUT/${TAG}_pmc_write_size_1m_$MODE.csv" $MODE 1000000 5 "$PFX" "$OUT/${TAG}_kernel_stats_1m_$MODE.csv" > "$OUT/$TJ"
   cp "$OUT/$TJ" "$R/profiles/$TJ"
-  python "$R/bench.py" --mode $MODE --steps 20 --warmup 5 > "$OUT/${TAG}_bench_1m_$MODE.json" 2> "$OUT/bench_$MODE.err"
+  python "$R/bench.py" --full --mode $MODE --steps 20 --warmup 5 > "$OUT/${TAG}_bench_1m_$MODE.json" 2> "$OUT/bench_$MODE.err"
   tail -c 600 "$OUT/${TAG}_kernel_passes_1m_$MODE.txt"; head -6 "$OUT/${TAG}_kernel_stats_1m_$MODE.csv"
 done
