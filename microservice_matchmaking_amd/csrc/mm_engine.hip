@@ -747,8 +747,9 @@ __global__ __launch_bounds__(WK_THREADS) void k_walk(WalkParams P)
                                 if (t == 0 || sm < smin) smin = sm;
                                 if (t == 0 || sm > smax) smax = sm;
                             }
+                            // |team sums| differ by up to 2^35: divide in double (exact numerator), round to f32 once
                             P.out_score[(size_t)g * P.out_rec_stride + n_out] =
-                                (float)(int32_t)(smax - smin) / (float)(int32_t)M.team_size;
+                                (float)((double)(smax - smin) / (double)M.team_size);
                             P.out_pass[(size_t)g * P.out_rec_stride + n_out] = passes;
                         }
                         lb.n = 0;

@@ -198,7 +198,7 @@ struct PairParams {
     uint32_t* tilectl;                  // [TC_N][group][max_tiles]
     uint32_t max_tiles;
     uint32_t* out_slots;
-    float* out_score;
+    float* out_score;                   // |ra - rb| / 1: within the window (<= 2^30 - 1), so (float)(int32_t) never wraps
     uint32_t* out_pass;
     // What the host saw when it last looked at the chains — constant for the whole batch of kp_round launches
     // (a chain's length and buffer only change in the compaction between batches): kernel arguments, so that a

@@ -1199,7 +1199,9 @@ static __device__ __forceinline__ void tl_write_lobby(const TeamParams& P, uint3
         if (t == 0 || sm < smin) smin = sm;
         if (t == 0 || sm > smax) smax = sm;
     }
-    P.out_score[(size_t)g * P.out_rec_stride + idx] = (float)(int32_t)(smax - smin) / (float)(int32_t)M.team_size;
+    // |team sums| differ by up to 2^35 (a window of 2^30 - 1 around the anchor, 8 a team): the difference is exact in
+    // double, the quotient is rounded to f32 once (see k_walk's emission)
+    P.out_score[(size_t)g * P.out_rec_stride + idx] = (float)((double)(smax - smin) / (double)M.team_size);
     P.out_pass[(size_t)g * P.out_rec_stride + idx] = pass;
 }
 

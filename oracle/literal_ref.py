@@ -39,17 +39,19 @@ def default_rating_group(groups):
     return groups[len(groups) // 2 + 1]
 
 
-def find_rating_group_by_rating(rating, groups=RATING_GROUPS):
+def find_rating_group_by_rating(rating, groups=RATING_GROUPS, default=None):
     """generic/worker.ex:46-53.  A non-number rating compares greater than every number
-    under Erlang term order, so it falls through to the default group."""
+    under Erlang term order, so it falls through to the default group.  `default`: a group
+    of `groups` that replaces :27's rule (a configuration that names its own default)."""
+    dflt = default if default is not None else default_rating_group(groups)
     if isinstance(rating, bool) or not isinstance(rating, (int, float)) or (
         isinstance(rating, float) and math.isnan(rating)
     ):
-        return default_rating_group(groups)
+        return dflt
     for g in groups:
         if rating >= g[0] and rating <= g[1]:
             return g
-    return default_rating_group(groups)
+    return dflt
 
 
 def team_name(t):
@@ -139,8 +141,9 @@ def get_players_count(teams):
 class SearchStage:
     """The generic hop + one Search.Worker per rating group, driven synchronously."""
 
-    def __init__(self, mode_cfgs, groups=RATING_GROUPS):
+    def __init__(self, mode_cfgs, groups=RATING_GROUPS, default=None):
         self.groups = groups
+        self.default = default                # None: generic/worker.ex:27
         self.mode_cfgs = mode_cfgs            # game-mode name -> dict
         self.queues = {g[2]: deque() for g in groups}
         self.lobbies = LobbyState(groups)
@@ -151,7 +154,7 @@ class SearchStage:
     # middleware + generic hop --------------------------------------------------------
     def deliver(self, player):
         self.active.add_user(player["id"])    # middleware/worker.ex:65-70
-        g = find_rating_group_by_rating(player.get("rating"), self.groups)
+        g = find_rating_group_by_rating(player.get("rating"), self.groups, self.default)
         self.queues[g[2]].append(player)      # generic/worker.ex:55-66
 
     def cancel(self, player_id):

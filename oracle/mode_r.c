@@ -318,7 +318,9 @@ static int chain_emit(chain* c, const mm_mode_config* mc, uint32_t group, uint32
         if (t == 0 || s < smin) smin = s;
         if (t == 0 || s > smax) smax = s;
     }
-    m->score = (float)(int32_t)(smax - smin) / (float)(int32_t)mc->team_size;
+    /* |smax - smin| < 2^36 is exact in double; one rounding to f32 (a quotient is either exact in double or not a dyadic
+       rational, so the double never lands on an f32 tie: the two roundings give the nearest f32) */
+    m->score = (float)((double)(smax - smin) / (double)mc->team_size);
     m->group = group;
     m->pass = pass;
     return MM_OK;

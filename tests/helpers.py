@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import json
 import os
+from fractions import Fraction
 
 import numpy as np
 
@@ -71,6 +72,37 @@ def assert_same_tick(a, b, tag="", score_tol=1e-6):
         assert a.stats[k] == b.stats[k], (tag, k, a.stats[k], b.stats[k])
 
 
+def f32_nearest(q: Fraction) -> np.float32:
+    """The f32 nearest to the exact rational q, ties to even: a candidate and its two neighbours, judged exactly."""
+    c = np.float32(float(q))
+    best = None
+    for x in (np.nextafter(c, np.float32(-np.inf)), c, np.nextafter(c, np.float32(np.inf))):
+        d = abs(Fraction(float(x)) - q)
+        if best is None or d < best[0] or (d == best[0] and int(np.float32(x).view(np.uint32)) & 1 == 0):
+            best = (d, np.float32(x))
+    return best[1]
+
+
+def exact_scores(slots, mode, rating_of):
+    """The score every emitted lobby must carry (include/mm_engine.h: |sum of team max - sum of team min| / team_size):
+    team sums in emission (team) order from the enqueued ratings as Python ints, the difference exact, the quotient
+    rounded once to the nearest f32.  slots: (n, teams * team_size); mode: dict or mm_mode_config; rating_of: slot -> int."""
+    ts = int(mode["team_size"] if isinstance(mode, dict) else mode.team_size)
+    out = np.empty(len(slots), np.float32)
+    for i, row in enumerate(slots):
+        sums = [sum(int(rating_of[int(s)]) for s in row[t:t + ts]) for t in range(0, len(row), ts)]
+        out[i] = f32_nearest(Fraction(max(sums) - min(sums), ts))
+    return out
+
+
+def assert_exact_scores(m, mode, rating_of, tag=""):
+    """Bit-exact scores of one tick's Matches against exact_scores (no tolerance)."""
+    want = exact_scores(m.slots, mode, rating_of)
+    got = np.asarray(m.score, np.float32)
+    bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
+    assert bad.size == 0, (tag, "score", int(bad[0]), float(got[bad[0]]), float(want[bad[0]]), m.slots[bad[0]].tolist())
+
+
 def assert_same_state(ea, eb, cfg, tag=""):
     """Queue depth, queue ORDER (requeue ordering, worker.ex:239-248 -> requeue/worker.ex:51-54: the
     survivors of a tick in the order the broker would deliver them next) and the stored lobby."""
@@ -89,6 +121,7 @@ def random_scenario(rng, cfg, ea, eb, n_rounds=4, batch=200, cancel_frac=0.05, n
                     rating_lo=0, rating_hi=5000, n_parties=2):
     """Drive two engines with the same random enqueue/cancel/tick script and compare."""
     live = []
+    rating_of = {}                    # slot -> the rating it was enqueued with (slots are reused: the latest wins)
     for rnd in range(n_rounds):
         n = int(rng.integers(0, batch + 1))
         rating = rng.integers(rating_lo, rating_hi + 1, size=n).astype(np.int32)
@@ -101,6 +134,7 @@ def random_scenario(rng, cfg, ea, eb, n_rounds=4, batch=200, cancel_frac=0.05, n
         sb = eb.enqueue(rating, cons)
         assert np.array_equal(sa, sb), "slots"
         live.extend(int(s) for s in sa if s != NO_SLOT)
+        rating_of.update((int(s), int(r)) for s, r in zip(sa, rating) if s != NO_SLOT)
         if live and cancel_frac > 0:
             k = int(len(live) * cancel_frac)
             if k:
@@ -114,6 +148,8 @@ def random_scenario(rng, cfg, ea, eb, n_rounds=4, batch=200, cancel_frac=0.05, n
             ma = ea.tick(mode_i)
             mb = eb.tick(mode_i)
             assert_same_tick(ma, mb, tag="round %d mode %d" % (rnd, mode_i))
+            assert_exact_scores(ma, cfg.modes[mode_i], rating_of, "round %d mode %d" % (rnd, mode_i))
+            assert_exact_scores(mb, cfg.modes[mode_i], rating_of, "round %d mode %d" % (rnd, mode_i))
             gone = set(ma.slots.ravel().tolist())
             live = [s for s in live if s not in gone]
         assert_same_state(ea, eb, cfg, tag="round %d" % rnd)

@@ -2,7 +2,7 @@
 """Test infrastructure (it drives the oracle, so it lives under tests/).  Randomised differential stress on a real GPU: HIP engine vs oracle over many seeded
 scenarios (pool sizes that hit the LDS-resident walk, the tiled rounds and the hand-over
 between them; windows from 0 to wider than the rating span; 1..64 regions; multi-tick with
-arrivals and cancels).  Usage: python tests/stress.py [seconds] [seed] [team] [--fuzz-knobs]
+arrivals and cancels).  Usage: python tests/stress.py [seconds] [seed] [team] [--fuzz-knobs] [--wide]
 
 --fuzz-knobs (round 6): every scenario's engine is created with a random COMBINATION of the engine's tuning fields
 (include/mm_engine.h mm_tuning, passed per engine through mm_engine_create_ex) off their defaults — batch sizes, the
@@ -10,6 +10,11 @@ persistent launch shapes on / off / cut short, bounded waits of zero, the test h
 random iteration and a kt_fc chunk flag never come.  Round 5's tile-length bug needed a stop of kp_rounds to show and no
 default-configuration test could see it; one knob at a time found it, combinations are what this draws.  The draw is a
 function of the scenario's seed alone (MM_STRESS_ONLY=<seed> replays scenario AND knobs); a failure prints both.
+
+--wide: configurations past the reference's shape instead — 1-16 rating groups from random tables (contiguous,
+overlapping, gapped; default group anywhere), 1-16 modes (1v1 and team modes, up to 256 chains), ratings spanning the
+whole table and beyond it; scores checked exactly (helpers.exact_scores).  Its draws come from a stream of their own:
+without the flag every seed gives the scenario it always gave.
 
 MM_STRESS_ENGINE=emu_small runs the same scenarios without a GPU on the fiber-shim build of the
 kernel source with the tiny tile geometry (tests/emu/), pool sizes divided by 16 so that they
@@ -25,8 +30,9 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 
-from helpers import assert_same_state, assert_same_tick  # noqa: E402
+from helpers import assert_exact_scores, assert_same_state, assert_same_tick  # noqa: E402
 from microservice_matchmaking_amd import Engine, cons_make, make_config, mode_1v1, mode_team  # noqa: E402
+from microservice_matchmaking_amd._abi import NO_SLOT  # noqa: E402
 from oracle.oracle import OracleEngine  # noqa: E402
 
 SCALE = 1
@@ -86,6 +92,90 @@ def random_team_mode(rng):
     window = int(rng.choice([5, 25, 50, 150, 600, 10 ** 6]))
     return mode_team(team_size, teams, window, tuple(int(q) for q in quota),
                      region_filter=bool(rng.integers(0, 3) == 0), party_filter=bool(rng.integers(0, 5) == 0))
+
+
+def random_group_table(rng):
+    """1-16 groups: contiguous, overlapping (the lowest index wins) or with gaps (the default group takes them)."""
+    n = int(rng.integers(1, 17))
+    kind = int(rng.integers(0, 3))
+    width = int(rng.choice([1, 50, 300, 1000, 5000]))
+    lo = int(rng.choice([0, 0, -3000, 1500]))
+    rows = []
+    for i in range(n):
+        a = lo + i * width
+        if kind == 1:                                           # overlapping: each reaches into the next ones
+            a -= int(rng.integers(0, width + 1))
+            b = a + width + int(rng.integers(0, 2 * width + 1))
+        elif kind == 2:                                         # gaps: a share of each step is nobody's
+            b = a + max(0, width - 1 - int(rng.integers(0, width // 2 + 1)))
+        else:
+            b = a + width - 1
+        rows.append((a, b, "g%d" % i))
+    return rows, int(rng.integers(0, n))
+
+
+def wide_main(budget, seed0):
+    """--wide: group tables, mode counts and rating ranges past the reference's seven groups and four modes."""
+    t_end = time.time() + budget
+    n_done = 0
+    k = 0
+    only = os.environ.get("MM_STRESS_ONLY")
+    while time.time() < t_end:
+        seed = seed0 * 100003 + k
+        k += 1
+        if only:
+            if k > 1:
+                break
+            seed = int(only)
+        rng = np.random.default_rng([seed, 0x77696465])
+        groups, dflt = random_group_table(rng)
+        n_modes = int(rng.choice([1, 2, 4, 16]))
+        modes = []
+        for _ in range(n_modes):
+            if rng.integers(0, 2):
+                window = int(rng.choice([0, 3, 25, 200, 10 ** 6, 0x3FFFFFFF]))
+                modes.append(mode_1v1(window=window, region_filter=bool(rng.integers(0, 2)),
+                                      party_filter=bool(rng.integers(0, 4) == 0)))
+            else:
+                modes.append(random_team_mode(rng))
+        chains = n_modes * len(groups)
+        capacity = 1 << (18 if chains <= 16 else 16)
+        cfg = make_config(modes, capacity=capacity, groups=groups, default_group=dflt, timing=False)
+        lo = min(g[0] for g in groups) - 100
+        hi = max(g[1] for g in groups) + 100
+        regions = int(rng.choice([1, 2, 8]))
+        top = 40000 if chains <= 16 else 12000
+        sizes = [scaled(rng.choice([50, 3000, 20000, top]))] + \
+                [scaled(rng.choice([0, 100, 3000])) for _ in range(int(rng.integers(0, 3)))]
+        tag = "wide seed %d groups=%s default=%d modes=%s sizes=%s" % (seed, groups, dflt, modes, sizes)
+        if os.environ.get("MM_STRESS_VERBOSE"):
+            print(tag, flush=True)
+        rating_of = {}
+        with Engine(cfg) as a, OracleEngine(cfg) as b:
+            live = np.zeros(0, np.uint32)
+            for j, n in enumerate(sizes):
+                rating = rng.integers(lo, hi + 1, size=n).astype(np.int32)
+                mode = rng.integers(0, n_modes, size=n)
+                role = np.array([rng.integers(0, modes[int(m)]["n_roles"]) for m in mode], dtype=np.int64)
+                cons = cons_make(mode, rng.integers(0, regions, size=n), rng.integers(0, 3, size=n), role)
+                sa, sb = a.enqueue(rating, cons), b.enqueue(rating, cons)
+                assert np.array_equal(sa, sb), tag
+                ok = sa != NO_SLOT
+                rating_of.update(zip(sa[ok].tolist(), rating[ok].tolist()))
+                live = np.concatenate([live, sa[ok]])
+                if live.size > 10 and rng.integers(0, 3) == 0:
+                    cs = rng.choice(live, size=max(1, live.size // 50), replace=False)
+                    a.cancel(cs)
+                    b.cancel(cs)
+                    live = np.setdiff1d(live, cs)
+                for md in range(n_modes):
+                    ma, mb = a.tick(md), b.tick(md)
+                    assert_same_tick(ma, mb, tag + " tick %d mode %d" % (j, md))
+                    assert_exact_scores(ma, cfg.modes[md], rating_of, tag + " tick %d mode %d" % (j, md))
+                    live = np.setdiff1d(live, ma.slots.ravel())
+                assert_same_state(a, b, cfg, tag)
+        n_done += 1
+    print("gpu_stress --wide: %d scenarios ok (seeds %d..%d)" % (n_done, seed0 * 100003, seed0 * 100003 + k - 1))
 
 
 def team_main(budget, seed0):
@@ -148,6 +238,8 @@ def main(argv=None):
     ARGV = [a for a in argv if not a.startswith("--")]
     budget = float(ARGV[0]) if len(ARGV) > 0 else 30.0
     seed0 = int(ARGV[1]) if len(ARGV) > 1 else 1
+    if "--wide" in argv:
+        return wide_main(budget, seed0)
     if len(ARGV) > 2 and ARGV[2] == "team":
         return team_main(budget, seed0)
     t_end = time.time() + budget

@@ -19,9 +19,12 @@ MODE_SETS = {
 }
 
 
-def literal_stage(cfg):
+def literal_stage(cfg, groups=REFERENCE_RATING_GROUPS):
+    """groups: (from, to, name) rows as make_config got them; a cfg.default_group other than
+    generic/worker.ex:27's div(n, 2) + 1 is handed to the literal stage explicitly."""
     md = mode_dicts(cfg)
-    return SearchStage({"mode%d" % i: m for i, m in enumerate(md)}, REFERENCE_RATING_GROUPS)
+    dflt = None if cfg.default_group == len(groups) // 2 + 1 else groups[cfg.default_group]
+    return SearchStage({"mode%d" % i: m for i, m in enumerate(md)}, groups, dflt)
 
 
 def to_payload(slot, rating, cons):
@@ -30,11 +33,11 @@ def to_payload(slot, rating, cons):
             "region": (c >> 4) & 0xFF, "party": (c >> 12) & 0xF, "role": (c >> 16) & 0xF}
 
 
-def literal_tick(stage, cfg):
+def literal_tick(stage, cfg, groups=REFERENCE_RATING_GROUPS):
     """All groups, all modes in one mixed run; returns per-mode emission lists
     [(group_index, pass, [slots in team order])]."""
     per_mode = {m: [] for m in range(cfg.n_modes)}
-    for gi, g in enumerate(REFERENCE_RATING_GROUPS):
+    for gi, g in enumerate(groups):
         n0 = len(stage.emitted)
         plog = []
         stage.run_group_to_quiescence(g[2], pass_log=plog)
