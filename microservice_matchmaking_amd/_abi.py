@@ -236,6 +236,14 @@ class EngineBase:
 
     _lib = None
     _prefix = "mm_"
+    _load = None                              # subclasses: staticmethod that loads and binds the library
+
+    @classmethod
+    def ensure_lib(cls):
+        """The class's library, loaded at the first use (an engine, or a classmethod that needs no engine)."""
+        if cls._lib is None and cls._load is not None:
+            cls._lib = cls._load()
+        return cls._lib
 
     def __init__(self, cfg: MMConfig, tuning=None):
         """tuning: {field of include/mm_engine.h's mm_tuning: value} for THIS engine (mm_engine_create_ex); fields
@@ -257,7 +265,7 @@ class EngineBase:
     @classmethod
     def tuning_record(cls, tuning=None):
         """A buffer holding mm_tuning_default() with `tuning` laid over it by mm_tuning_set."""
-        lib, pre = cls._lib, cls._prefix
+        lib, pre = cls.ensure_lib(), cls._prefix
         rec = (C.c_uint32 * cls.TUNING_WORDS)()
         rec[0] = 4 * cls.TUNING_WORDS
         dflt, setf = getattr(lib, pre + "tuning_default"), getattr(lib, pre + "tuning_set")
@@ -275,7 +283,7 @@ class EngineBase:
     @classmethod
     def tuning_names(cls):
         """The fields of mm_tuning, in order (mm_tuning_name)."""
-        fn = getattr(cls._lib, cls._prefix + "tuning_name")
+        fn = getattr(cls.ensure_lib(), cls._prefix + "tuning_name")
         fn.argtypes, fn.restype = [C.c_uint32], C.c_char_p
         out = []
         while True:

@@ -396,7 +396,10 @@ __global__ __launch_bounds__(TT_CH) void kt_build(TeamParams P)
         bb = s_base[lane];
         for (int w = 0; w < wave; ++w) bb += s_wc[w][lane];
         for (int r2 = 0; r2 < lane; ++r2) off += s_tot[r2];
-        P.blkbase[po + (size_t)lane * P.blk_stride + (pos >> 6)] = bb;
+        // (a role's row holds blk_stride = pstride / 64 blocks.  The last chunk's waves behind the stride — a pool whose
+        // capacity is no multiple of TT_CH, nearly full with one chain — used to write their base into the NEXT role's first
+        // blocks, racing with the chunk those belong to: tests/test_boundaries.py, chains of k x TT_CH + 1 players)
+        if ((pos >> 6) < P.blk_stride) P.blkbase[po + (size_t)lane * P.blk_stride + (pos >> 6)] = bb;
     }
     const uint32_t mybb = (uint32_t)__shfl((int)bb, (int)role), myoff = (uint32_t)__shfl((int)off, (int)role);
     if (pos < m) {
@@ -734,6 +737,8 @@ static __device__ __forceinline__ void tf_chunk(const TeamParams& P, const uint3
     //      What the scans read: per role, the sub-queue from the first entry behind the chunk's first position, as
     //      long as the chunk's own players of the role plus TF_PAD (where a scan that succeeds normally ends);
     //      longer scans go on in HBM ----
+    // (the last chunk's waves behind the stride — pos >> 6 >= blk_stride, so pos >= pstride >= capacity >= m — read a word of
+    // the next role's row here: inside the group's pstride words, and unused, these positions hold nobody; kt_build writes none)
     const uint32_t bbv = (uint32_t)lane < nr ? P.blkbase[po + (size_t)lane * P.blk_stride + (pos >> 6)] : 0u;
     if (tid < 64) {                                           // one lane per role: every load of the set-up in flight at once
         const bool on = (uint32_t)lane < nr;

@@ -55,10 +55,10 @@ class Engine(EngineBase):
     """One engine = one HIP stream + its device-resident queues and open lobbies."""
 
     _prefix = "mm_"
+    _load = staticmethod(load_library)
 
     def __init__(self, cfg: MMConfig, tuning=None):
-        if Engine._lib is None:
-            Engine._lib = load_library()
+        Engine.ensure_lib()
         super().__init__(cfg, tuning)
 
     def enqueue_device(self, d_rating, d_cons):

@@ -18,10 +18,10 @@ def load():
 
 class EmuEngine(EngineBase):
     _prefix = "mm_"
+    _load = staticmethod(load)
 
     def __init__(self, cfg, tuning=None):
-        if EmuEngine._lib is None:
-            EmuEngine._lib = load()
+        EmuEngine.ensure_lib()
         super().__init__(cfg, tuning)
 
 
@@ -38,7 +38,8 @@ class EmuEngineSmall(EngineBase):
     _prefix = "mm_"
     _lib = None
 
+    _load = staticmethod(load_small)
+
     def __init__(self, cfg, tuning=None):
-        if EmuEngineSmall._lib is None:
-            EmuEngineSmall._lib = load_small()
+        EmuEngineSmall.ensure_lib()
         super().__init__(cfg, tuning)

@@ -103,6 +103,22 @@ def assert_exact_scores(m, mode, rating_of, tag=""):
     assert bad.size == 0, (tag, "score", int(bad[0]), float(got[bad[0]]), float(want[bad[0]]), m.slots[bad[0]].tolist())
 
 
+def assert_exact_scores_any(m, mode, rating_of, tag=""):
+    """assert_exact_scores on every lobby of a tick of up to 20 000 lobbies; a longer list is checked whole by the
+    same rule in numpy (team sums as int64, the quotient in double — exact or not a dyadic rational, so its rounding to
+    f32 is the nearest f32 — compared to the bit) and by assert_exact_scores on 20 000 lobbies spread over it."""
+    rows = np.arange(len(m))
+    if len(m) > 20000:
+        ts = int(mode.team_size)
+        sums = np.asarray(rating_of)[m.slots].reshape(len(m), -1, ts).sum(axis=2)
+        want = ((sums.max(axis=1) - sums.min(axis=1)).astype(np.float64) / ts).astype(np.float32)
+        bad = np.flatnonzero(want.view(np.uint32) != np.asarray(m.score, np.float32).view(np.uint32))
+        assert bad.size == 0, (tag, "score", int(bad[0]), float(m.score[bad[0]]), float(want[bad[0]]))
+        rows = np.unique(np.linspace(0, len(m) - 1, 20000).astype(np.int64))
+    sub = type(m)(m.slots[rows], m.score[rows], m.group[rows], m.pass_[rows], m.stats)
+    assert_exact_scores(sub, mode, rating_of, tag)
+
+
 def assert_same_state(ea, eb, cfg, tag=""):
     """Queue depth, queue ORDER (requeue ordering, worker.ex:239-248 -> requeue/worker.ex:51-54: the
     survivors of a tick in the order the broker would deliver them next) and the stored lobby."""

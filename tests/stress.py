@@ -2,7 +2,7 @@
 """Test infrastructure (it drives the oracle, so it lives under tests/).  Randomised differential stress on a real GPU: HIP engine vs oracle over many seeded
 scenarios (pool sizes that hit the LDS-resident walk, the tiled rounds and the hand-over
 between them; windows from 0 to wider than the rating span; 1..64 regions; multi-tick with
-arrivals and cancels).  Usage: python tests/stress.py [seconds] [seed] [team] [--fuzz-knobs] [--wide]
+arrivals and cancels).  Usage: python tests/stress.py [seconds] [seed] [team] [--fuzz-knobs] [--wide] [--edges]
 
 --fuzz-knobs (round 6): every scenario's engine is created with a random COMBINATION of the engine's tuning fields
 (include/mm_engine.h mm_tuning, passed per engine through mm_engine_create_ex) off their defaults — batch sizes, the
@@ -15,6 +15,10 @@ function of the scenario's seed alone (MM_STRESS_ONLY=<seed> replays scenario AN
 overlapping, gapped; default group anywhere), 1-16 modes (1v1 and team modes, up to 256 chains), ratings spanning the
 whole table and beyond it; scores checked exactly (helpers.exact_scores).  Its draws come from a stream of their own:
 without the flag every seed gives the scenario it always gave.
+
+--edges: chains of EXACT length instead — one or two rating groups, every batch sized so that a chain starts its tick at
+B + d players, B from the boundary tables of tests/geometry.py (the lengths at which the kernels and the host loop switch
+behaviour, read from the source and computed from the drawn tuning), d from -2 .. 2.  A stream of its own as well.
 
 MM_STRESS_ENGINE=emu_small runs the same scenarios without a GPU on the fiber-shim build of the
 kernel source with the tiny tile geometry (tests/emu/), pool sizes divided by 16 so that they
@@ -30,7 +34,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 
-from helpers import assert_exact_scores, assert_same_state, assert_same_tick  # noqa: E402
+from helpers import assert_exact_scores, assert_exact_scores_any, assert_same_state, assert_same_tick  # noqa: E402
 from microservice_matchmaking_amd import Engine, cons_make, make_config, mode_1v1, mode_team  # noqa: E402
 from microservice_matchmaking_amd._abi import NO_SLOT  # noqa: E402
 from oracle.oracle import OracleEngine  # noqa: E402
@@ -178,6 +182,92 @@ def wide_main(budget, seed0):
     print("gpu_stress --wide: %d scenarios ok (seeds %d..%d)" % (n_done, seed0 * 100003, seed0 * 100003 + k - 1))
 
 
+def edges_main(budget, seed0, count=None):
+    """--edges: chains of exact length.  One or two rating groups, every batch sized so that ONE chain starts its tick at
+    B + d players — B from the boundary tables of the running engine (tests/geometry.py: read from the source, computed from
+    the DRAWN tuning with --fuzz-knobs, whose pair_ptiles / pair_tiles_max / pair_group_min move boundaries), d from
+    -2 .. 2 — predicates and cancels as in the default family.  Draws come from a stream of their own.  `count`: that
+    many scenarios instead of a time budget."""
+    import geometry
+    t_end = time.time() + budget
+    n_done = 0
+    k = 0
+    only = os.environ.get("MM_STRESS_ONLY")
+    while time.time() < t_end and (count is None or k < count):
+        seed = seed0 * 100003 + k
+        k += 1
+        if only:
+            if k > 1:
+                break
+            seed = int(only)
+        rng = np.random.default_rng([seed, 0x65646765])
+        team = bool(rng.integers(0, 3) == 0)
+        tuning = draw_tuning(seed, [TEAM_KNOBS if team else PAIR_KNOBS])
+        geo = geometry.geometry(Engine, small=SCALE > 1, tuning=tuning)
+        table = geometry.team_boundaries(geo) if team else geometry.pair_boundaries(geo)
+        # what a scenario may cost: the oracle walks a chain on one thread; the shim pays for every pass of every tile
+        top = (1 << 18) if SCALE == 1 else 10 * geo["PK_T"]
+        table = [e for e in table if 8 <= e[0] <= top]
+        if team:
+            window = int(rng.choice([25, 150, 600, 10 ** 6]))
+            modes = [mode_team(2, 2, window, (1, 1)) if rng.integers(0, 2) else mode_team(5, 2, window, (1, 1, 1, 1, 1))]
+            regions, party = 1, False
+        else:
+            window = int(rng.choice([0, 1, 3, 10, 25, 60, 200, 1000, 10 ** 6]))
+            regions = int(rng.choice([1, 2, 4, 8, 64]))
+            party = bool(rng.integers(0, 4) == 0)
+            modes = [mode_1v1(window=window, region_filter=regions > 1, party_filter=party)]
+        nr = modes[0]["n_roles"]
+        two = bool(rng.integers(0, 2))
+        groups = [(0, 2499, "low"), (2500, 5000, "high")] if two else [(0, 5000, "all")]
+        aim = int(rng.integers(0, len(groups)))                     # the group whose chain is aimed at the boundary
+        targets = [int(table[rng.integers(0, len(table))][0]) + int(rng.integers(-2, 3)) for _ in range(int(rng.integers(1, 4)))]
+        cfg = make_config(modes, capacity=2 * max(targets) + 4096, groups=groups, default_group=0, timing=False)
+        tag = "edges seed %d team=%d w=%d regions=%d party=%d groups=%d aim=%d targets=%s tuning=%s" % (
+            seed, team, window, regions, party, len(groups), aim, targets, tuning)
+        if os.environ.get("MM_STRESS_VERBOSE"):
+            print(tag, flush=True)
+        rating_of = np.zeros(cfg.capacity, np.int64)
+        with (Engine(cfg, tuning) if tuning else Engine(cfg)) as a, OracleEngine(cfg) as b:
+            live = np.zeros(0, np.uint32)
+            for j, target in enumerate(targets):
+                # cancels first (they are purged at the head of the tick), then the batch that brings the aimed chain —
+                # the ORACLE's depth minus the cancelled players still in it — to the target exactly
+                if live.size > 10 and rng.integers(0, 3) == 0:
+                    cs = rng.choice(live, size=max(1, live.size // 50), replace=False)
+                    a.cancel(cs)
+                    b.cancel(cs)
+                    live = np.setdiff1d(live, cs)
+                qs = np.intersect1d(b.queue_slots(0, aim), live)
+                if qs.size > target:                                 # an earlier target left more: the surplus gives up as well
+                    cs = rng.choice(qs, size=qs.size - target, replace=False)
+                    a.cancel(cs)
+                    b.cancel(cs)
+                    live = np.setdiff1d(live, cs)
+                n = max(0, target - qs.size)
+                lo, hi = groups[aim][0], groups[aim][1]
+                rating = rng.integers(lo, hi + 1, size=n).astype(np.int32)
+                if two:                                              # a few players for the other chain as well
+                    other = groups[1 - aim]
+                    rating = np.concatenate([rating, rng.integers(other[0], other[1] + 1, size=int(rng.integers(0, 40))).astype(np.int32)])
+                    rating = rating[rng.permutation(rating.size)]
+                n = rating.size
+                cons = cons_make(0, rng.integers(0, regions, size=n), rng.integers(0, 3 if party else 1, size=n), rng.integers(0, nr, size=n))
+                sa, sb = a.enqueue(rating, cons), b.enqueue(rating, cons)
+                assert np.array_equal(sa, sb), tag
+                rating_of[sa] = rating
+                live = np.concatenate([live, sa])
+                # the family's point: the aimed chain starts this tick (behind the purge) at the target, exactly
+                assert np.intersect1d(b.queue_slots(0, aim), live).size == target, (tag, j)
+                ma, mb = a.tick(0), b.tick(0)
+                assert_same_tick(ma, mb, tag + " tick %d" % j)
+                assert_exact_scores_any(ma, cfg.modes[0], rating_of, tag + " tick %d" % j)
+                live = np.setdiff1d(live, ma.slots.ravel())
+                assert_same_state(a, b, cfg, tag)
+        n_done += 1
+    print("gpu_stress --edges%s: %d scenarios ok (seeds %d..%d)" % (" --fuzz-knobs" if FUZZ else "", n_done, seed0 * 100003, seed0 * 100003 + k - 1))
+
+
 def team_main(budget, seed0):
     """Team modes only: long chains take mm_team.inc, short ones and cancel ticks k_walk."""
     t_end = time.time() + budget
@@ -240,6 +330,8 @@ def main(argv=None):
     seed0 = int(ARGV[1]) if len(ARGV) > 1 else 1
     if "--wide" in argv:
         return wide_main(budget, seed0)
+    if "--edges" in argv:
+        return edges_main(budget, seed0)
     if len(ARGV) > 2 and ARGV[2] == "team":
         return team_main(budget, seed0)
     t_end = time.time() + budget

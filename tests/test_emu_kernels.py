@@ -242,3 +242,20 @@ def test_shim_randomised_stress_with_fuzzed_knobs(what, monkeypatch, capsys):
     mod.main(["25", "11" if what == "pair" else "12"] + (["team"] if what == "team" else []) + ["--fuzz-knobs"])
     out = capsys.readouterr().out
     assert "--fuzz-knobs" in out and "scenarios ok" in out, out
+
+
+def test_shim_exact_length_stress_with_fuzzed_knobs(monkeypatch, capsys):
+    """tests/stress.py --edges --fuzz-knobs on the fiber-shim build: eight seeded scenarios whose chains start their ticks at
+    B + d players, B from the boundary tables of tests/geometry.py computed from the DRAWN tuning (the table of the default
+    tuning is tests/test_boundaries.py's; the device's share: test_gpu_exact_length_stress_with_fuzzed_knobs)."""
+    import importlib.util
+    import os
+    monkeypatch.setenv("MM_STRESS_ENGINE", "emu_small")
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "stress.py")
+    spec = importlib.util.spec_from_file_location("shim_stress_edges", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    monkeypatch.setattr(mod, "FUZZ", True)
+    mod.edges_main(600.0, 13, count=8)
+    out = capsys.readouterr().out
+    assert "--edges --fuzz-knobs: 8 scenarios ok" in out, out

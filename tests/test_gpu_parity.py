@@ -391,6 +391,22 @@ def test_gpu_randomised_stress_with_fuzzed_knobs(gpu_cls, what, capsys):
     assert "--fuzz-knobs" in out and "scenarios ok" in out, out
 
 
+def test_gpu_exact_length_stress_with_fuzzed_knobs(gpu_cls, capsys):
+    """Twenty seconds of tests/stress.py --edges --fuzz-knobs: chains that start their ticks at B + d players, B from the
+    boundary tables of tests/geometry.py computed from the drawn tuning (pair_ptiles, pair_tiles_max and pair_group_min move
+    the boundaries), d from -2 .. 2; every tick bit-exact against the oracle.  The table of the default tuning, length by
+    length: tests/test_boundaries.py."""
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "stress.py")
+    spec = importlib.util.spec_from_file_location("gpu_stress_edges", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    mod.main(["20", "8", "--edges", "--fuzz-knobs"])
+    out = capsys.readouterr().out
+    assert "--edges --fuzz-knobs" in out and "scenarios ok" in out, out
+
+
 def test_gpu_pair_second_route_level_forced(gpu_cls, oracle_cls, monkeypatch):
     """kp_group (the second level of the route, by default only for chains of 64+ tiles: the 10M pool) on every tiled
     chain of a 300k pool — MM_PAIR_GROUP=4: groups at 8192-position tiles while the chains shrink through all the
