@@ -2,7 +2,7 @@
 """Test infrastructure (it drives the oracle, so it lives under tests/).  Randomised differential stress on a real GPU: HIP engine vs oracle over many seeded
 scenarios (pool sizes that hit the LDS-resident walk, the tiled rounds and the hand-over
 between them; windows from 0 to wider than the rating span; 1..64 regions; multi-tick with
-arrivals and cancels).  Usage: python tests/stress.py [seconds] [seed] [team] [--fuzz-knobs] [--wide] [--edges]
+arrivals and cancels).  Usage: python tests/stress.py [seconds] [seed] [team] [--fuzz-knobs] [--wide] [--edges] [--patterns]
 
 --fuzz-knobs (round 6): every scenario's engine is created with a random COMBINATION of the engine's tuning fields
 (include/mm_engine.h mm_tuning, passed per engine through mm_engine_create_ex) off their defaults — batch sizes, the
@@ -19,6 +19,11 @@ without the flag every seed gives the scenario it always gave.
 --edges: chains of EXACT length instead — one or two rating groups, every batch sized so that a chain starts its tick at
 B + d players, B from the boundary tables of tests/geometry.py (the lengths at which the kernels and the host loop switch
 behaviour, read from the source and computed from the drawn tuning), d from -2 .. 2.  A stream of its own as well.
+
+--patterns: STRUCTURED arrival orders instead of i.i.d. draws — the first batch is a family of tests/patterns.py (nested,
+shifted, sorted, runs, interleaved, blocked head, dead tiles, alive share; with `team`: dense, nested, shifted members,
+scarce / sorted / missing roles) with its parameter from the geometry tables of the drawn tuning; later batches are
+another pattern or a random pool; cancels are a whole range, every m-th player or random.  A stream of its own.
 
 MM_STRESS_ENGINE=emu_small runs the same scenarios without a GPU on the fiber-shim build of the
 kernel source with the tiny tile geometry (tests/emu/), pool sizes divided by 16 so that they
@@ -268,6 +273,118 @@ def edges_main(budget, seed0, count=None):
     print("gpu_stress --edges%s: %d scenarios ok (seeds %d..%d)" % (" --fuzz-knobs" if FUZZ else "", n_done, seed0 * 100003, seed0 * 100003 + k - 1))
 
 
+def patterns_main(budget, seed0, team=False, count=None):
+    """--patterns: see the module docstring.  The first tick of the first pattern is also held against the family's
+    closed form (lobbies; the pass structure and pairs where it has one) on the ORACLE's side."""
+    import geometry
+    import patterns
+    t_end = time.time() + budget
+    n_done = 0
+    k = 0
+    only = os.environ.get("MM_STRESS_ONLY")
+    while time.time() < t_end and (count is None or k < count):
+        seed = seed0 * 100003 + k
+        k += 1
+        if only:
+            if k > 1:
+                break
+            seed = int(only)
+        rng = np.random.default_rng([seed, 0x70617474])
+        tuning = draw_tuning(seed, [TEAM_KNOBS if team else PAIR_KNOBS])
+        geo = geometry.geometry(Engine, small=SCALE > 1, tuning=tuning)
+        # what a scenario may cost: the oracle walks a chain on one thread, the shim pays for every pass of every tile
+        max_players, max_passes = ((1 << 17), 6000) if SCALE == 1 else (5 * geo["PK_T"], 600)
+        cases = [patterns.draw(rng, geo, team, max_players, max_passes)]
+        later = []                                               # after the first pattern: another pattern or a random pool
+        for _ in range(int(rng.integers(0, 3))):
+            later.append(patterns.draw(rng, geo, team, max_players, max_passes) if rng.integers(0, 2) else int(scaled(rng.choice([100, 3000, 20000]))))
+        m = cases[0].mode
+        mode = mode_1v1(window=m[1], region_filter=m[2]) if m[0] == "1v1" else mode_team(m[1], m[2], m[3], m[4])
+        nr = mode["n_roles"]
+        two = bool(rng.integers(0, 2))
+        groups = [patterns.GROUP + ("all",)] + ([(patterns.GROUP[1] + 1, patterns.GROUP[1] + 5000, "other")] if two else [])
+        total = cases[0].players + sum(x if isinstance(x, int) else x.players for x in later)
+        cfg = make_config([mode], capacity=total + 4096 + (scaled(30000) if two else 0), groups=groups, default_group=0, timing=False)
+        tag = "patterns seed %d team=%d first=%s later=%s groups=%d tuning=%s" % (
+            seed, team, cases[0], [x if isinstance(x, int) else str(x) for x in later], len(groups), tuning)
+        if os.environ.get("MM_STRESS_VERBOSE"):
+            print(tag, flush=True)
+        rating_of = np.zeros(cfg.capacity, np.int64)
+        with (Engine(cfg, tuning) if tuning else Engine(cfg)) as a, OracleEngine(cfg) as b:
+            live = np.zeros(0, np.uint32)
+            ticks = 0
+
+            def enqueue(rating, cons):
+                nonlocal live
+                sa, sb = a.enqueue(rating, cons), b.enqueue(rating, cons)
+                assert np.array_equal(sa, sb), tag
+                rating_of[sa] = rating
+                live = np.concatenate([live, sa])
+                return sa
+
+            def cancel(cs):
+                nonlocal live
+                cs = np.asarray(cs, np.uint32)
+                a.cancel(cs)
+                b.cancel(cs)
+                live = np.setdiff1d(live, cs)
+
+            def tick(expect=None):
+                nonlocal live, ticks
+                ma, mb = a.tick(0), b.tick(0)
+                if expect is not None:                            # the pattern did not degenerate: the oracle's side of the closed form
+                    g0 = mb.group == 0
+                    assert int(g0.sum()) == expect.lobbies, (tag, "closed form: lobbies", int(g0.sum()), expect.lobbies)
+                    if expect.passes is not None:
+                        assert np.bincount(mb.pass_[g0].astype(np.int64), minlength=expect.n_passes).tolist() == expect.per_pass, (tag, "closed form: lobbies per pass")
+                        if not two:
+                            assert mb.stats["pairs"] == expect.pairs and mb.stats["passes_max"] == expect.n_passes, (tag, "closed form: pairs, passes")
+                assert_same_tick(ma, mb, tag + " tick %d" % ticks)
+                assert_exact_scores_any(ma, cfg.modes[0], rating_of, tag + " tick %d" % ticks)
+                live = np.setdiff1d(live, ma.slots.ravel())
+                assert_same_state(a, b, cfg, tag + " tick %d" % ticks)
+                ticks += 1
+
+            def play(case, closed_form):
+                """The case's own script: enqueues, its structured cancels, its ticks."""
+                mine = np.zeros(0, np.uint32)
+                first = closed_form
+                for step in case.steps:
+                    if step[0] == "enqueue":
+                        cs = step[2]
+                        if not closed_form:                       # a later family's roles folded into the ones this mode knows
+                            cs = (cs & np.uint32(0xFFF0FFFF)) | ((((cs >> np.uint32(16)) & np.uint32(0xF)) % np.uint32(nr)) << np.uint32(16))
+                        mine = np.concatenate([mine, enqueue(step[1], cs)])
+                        if first and two:                         # a random pool for the other chain rides along
+                            n2 = int(scaled(rng.choice([50, 3000, 30000])))
+                            enqueue((groups[1][0] + rng.integers(0, 300, size=n2)).astype(np.int32), cons_make(0, 0, 0, rng.integers(0, nr, size=n2)))
+                        first = False
+                    elif step[0] == "cancel":
+                        cancel(mine[step[1]])
+                    else:
+                        tick(step[1] if closed_form else None)
+
+            play(cases[0], True)
+            for x in later:
+                if live.size > 10:                                # structured or random cancels among those still waiting
+                    kind = int(rng.integers(0, 4))
+                    q = np.intersect1d(b.queue_slots(0, 0), live)
+                    if kind == 0 and q.size > 4:                  # a whole range of the queue
+                        lo = int(rng.integers(0, q.size - 1))
+                        cancel(b.queue_slots(0, 0)[lo:lo + int(rng.integers(1, max(2, q.size // 3)))])
+                    elif kind == 1 and q.size > 4:                # every m-th queued player
+                        cancel(b.queue_slots(0, 0)[int(rng.integers(0, 3))::int(rng.integers(2, 9))])
+                    elif kind == 2:
+                        cancel(rng.choice(live, size=max(1, live.size // 50), replace=False))
+                if isinstance(x, int):
+                    enqueue(rng.integers(0, 5001, size=x).astype(np.int32), cons_make(0, rng.integers(0, 4, size=x), 0, rng.integers(0, nr, size=x)))
+                    tick()
+                else:
+                    play(x, False)                                # (its players under THIS scenario's mode: parity only)
+        n_done += 1
+    print("gpu_stress --patterns%s%s: %d scenarios ok (seeds %d..%d)" % (" team" if team else "", " --fuzz-knobs" if FUZZ else "", n_done, seed0 * 100003, seed0 * 100003 + k - 1))
+
+
 def team_main(budget, seed0):
     """Team modes only: long chains take mm_team.inc, short ones and cancel ticks k_walk."""
     t_end = time.time() + budget
@@ -332,6 +449,8 @@ def main(argv=None):
         return wide_main(budget, seed0)
     if "--edges" in argv:
         return edges_main(budget, seed0)
+    if "--patterns" in argv:
+        return patterns_main(budget, seed0, team=len(ARGV) > 2 and ARGV[2] == "team")
     if len(ARGV) > 2 and ARGV[2] == "team":
         return team_main(budget, seed0)
     t_end = time.time() + budget
