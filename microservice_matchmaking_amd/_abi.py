@@ -22,6 +22,7 @@ MM_MAX_LOBBY = 16
 MM_MODE_REGION_FILTER = 1
 MM_MODE_PARTY_FILTER = 2
 MM_CFG_TIMING = 1
+MM_WAIT_HIST = 33
 NO_SLOT = 0xFFFFFFFF
 
 STATUS_NAMES = {
@@ -91,6 +92,16 @@ class MMPathStats(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "size"}
+
+
+class MMWaitGroup(C.Structure):
+    """include/mm_wait.h mm_wait_group: the waiting players of one (mode, rating group) and their ages."""
+    _fields_ = [("waiting", C.c_uint32), ("oldest_age", C.c_uint32), ("age_sum", C.c_uint64),
+                ("hist", C.c_uint32 * MM_WAIT_HIST), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {"waiting": int(self.waiting), "oldest_age": int(self.oldest_age), "age_sum": int(self.age_sum),
+                "hist": np.asarray(self.hist[:], dtype=np.uint32)}
 
 
 class MMError(RuntimeError):
@@ -211,6 +222,19 @@ def bind(lib, prefix):
         f("snapshot").restype = C.c_int
         f("restore").argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         f("restore").restype = C.c_int
+    if hasattr(lib, prefix + "clock_set"):                # include/mm_wait.h: the product only (an expiry is a cancel to the oracle)
+        f("clock_set").argtypes = [C.c_void_p, C.c_uint32]
+        f("clock_set").restype = C.c_int
+        f("clock_get").argtypes = [C.c_void_p, u32p, u32p]
+        f("clock_get").restype = C.c_int
+        f("expire").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, u32p]
+        f("expire").restype = C.c_int
+        f("expired").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        f("expired").restype = C.c_int
+        f("wait_stats").argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MMWaitGroup)]
+        f("wait_stats").restype = C.c_int
+        f("matches_wait").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        f("matches_wait").restype = C.c_int
     return lib
 
 
@@ -385,6 +409,7 @@ class EngineBase:
         st = MMStats()
         self._check(self._fn("tick")(self._h, mode, C.byref(n), C.byref(st)), "tick")
         n = int(n.value)
+        self._last_tick = (mode, n)
         L = self.lobby_size(mode)
         if reuse:
             have = getattr(self, "_reuse", None)
@@ -429,6 +454,41 @@ class EngineBase:
     def restore(self, blob: bytes):
         buf = np.frombuffer(blob, dtype=np.uint8)
         self._check(self._fn("restore")(self._h, _ptr(buf), C.c_uint64(buf.size)), "restore")
+
+    # include/mm_wait.h: the clock -----------------------------------------------------
+    def clock_set(self, now):
+        """Sets the engine's clock (the first call switches stamps, expiry and wait times on)."""
+        self._check(self._fn("clock_set")(self._h, int(now) & 0xFFFFFFFF), "clock_set")
+
+    def clock(self):
+        """(now, enabled)."""
+        now, on = C.c_uint32(), C.c_uint32()
+        self._check(self._fn("clock_get")(self._h, C.byref(now), C.byref(on)), "clock_get")
+        return int(now.value), bool(on.value)
+
+    def expire(self, mode, max_age):
+        """mm_expire + mm_expired: every waiting player of `mode` older than max_age leaves as if cancelled.
+        -> (slots, group, age), rating group ascending, stored lobby then queue order within a group."""
+        n = C.c_uint32()
+        self._check(self._fn("expire")(self._h, mode, int(max_age) & 0xFFFFFFFF, C.byref(n)), "expire")
+        k = int(n.value)
+        slots, group, age = (np.empty(k, dtype=np.uint32) for _ in range(3))
+        self._check(self._fn("expired")(self._h, 0, k, _ptr(slots), _ptr(group), _ptr(age)), "expired")
+        return slots, group, age
+
+    def wait_stats(self, mode=0):
+        """mm_wait_stats: one dict per rating group (waiting, oldest_age, age_sum, hist[33])."""
+        out = (MMWaitGroup * MM_MAX_GROUPS)()
+        self._check(self._fn("wait_stats")(self._h, mode, out), "wait_stats")
+        return [out[g].as_dict() for g in range(self.cfg.n_groups)]
+
+    def matches_wait(self):
+        """mm_matches_wait for this object's last tick(): (n, L) uint32 laid out like Matches.slots — the clock at
+        that tick minus each seated player's stamp."""
+        mode, n = getattr(self, "_last_tick", (0, 0))
+        out = np.empty((n, self.lobby_size(mode)), dtype=np.uint32)
+        self._check(self._fn("matches_wait")(self._h, 0, n, _ptr(out)), "matches_wait")
+        return out
 
     def lobby_state(self, mode, group):
         n = C.c_uint32()

@@ -20,6 +20,8 @@
 //   k_bucket_count / k_bucket_scan / k_bucket_scatter   stable multi-way partition of an
 //           arrival batch into chain tails (A1 bucketing); HBM streaming, wave-ballot ranks.
 //   k_cancel, k_purge   ActiveUser.remove_user + the "vanish when popped" rule.
+//   k_wait_*   the clock (include/mm_wait.h): expiry selection as a stable stream compaction over the mode's queues,
+//           wait statistics, the waits of a tick's matched players.  DESIGN.md §4.6.
 //   k_walk   one workgroup per chain: LDS-staged tiles of the queue, wave-0 first-fit chain
 //           (ballot + ffs arg-min over queue position), in-place survivor compaction.
 //           The chain is inherently sequential (each match decides the next anchor), so
@@ -49,6 +51,7 @@
 #include <vector>
 
 #include "../../include/mm_engine.h"
+#include "../../include/mm_wait.h"
 #include <mm_gfx950.h>
 
 // ------------------------------------------------------------------------------------
@@ -260,7 +263,8 @@ __global__ __launch_bounds__(BK_THREADS) void k_bucket_scatter(uint32_t n, const
                                                                uint32_t* __restrict__ q_cons,
                                                                uint32_t* __restrict__ q_slot,
                                                                uint8_t* __restrict__ state,
-                                                               uint32_t* __restrict__ out_slot)
+                                                               uint32_t* __restrict__ out_slot,
+                                                               uint32_t* __restrict__ stamp, uint32_t now)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t row = (blockIdx.x * BK_WAVES + wave) * n_chains;
@@ -299,6 +303,7 @@ __global__ __launch_bounds__(BK_THREADS) void k_bucket_scatter(uint32_t n, const
                     q_cons[o] = cn;
                     q_slot[o] = slot;
                     state[slot] = MM_ST_LIVE;
+                    if (stamp) stamp[slot] = now;   // the clock (include/mm_wait.h); NULL until the owner sets it
                 }
             }
             lc_add(cur, c0, (uint32_t)__popcll(m), lane);
@@ -383,6 +388,272 @@ __global__ __launch_bounds__(256) void k_reset(uint32_t n_chains, ChainDev* __re
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t words = (uint32_t)(sizeof(ChainDev) / 4);
     if (i < n_chains * words) ((uint32_t*)chains)[i] = 0;
+}
+
+// ------------------------------------------------------------------------------------
+// the clock (include/mm_wait.h): expiry selection, wait statistics
+// ------------------------------------------------------------------------------------
+// The waiting players of a mode are walked in ONE order by every kernel here — rating group ascending; within a group
+// the stored lobby's seats as mm_lobby_state lists them, then the queue from head to tail — cut into chunks of WT_CHUNK
+// queue entries, one workgroup per chunk (a chain of 300 000 players is 147 workgroups, not k_purge's one).  A group
+// has at least one chunk: an empty queue may still have a stored lobby, and the group's first chunk carries its seats.
+// mm_expire is count / scan / scatter over that order, the shape of k_bucket_*: per-wave counts, one exclusive scan
+// down the (chunk, wave) rows, then every wave writes its selected entries at base + wave-ballot rank — a stable
+// compaction, so the list is in queue order.  Per entry: q_slot streamed, stamp[slot] and state[slot] gathered.
+#define WT_THREADS 256
+#define WT_WAVES 4
+#define WT_PER_WAVE 512                       // queue entries per wave per chunk
+#define WT_CHUNK (WT_WAVES * WT_PER_WAVE)     // queue entries per workgroup
+#define WT_ROWS (WT_WAVES + 1)                // counters per chunk: the stored lobby's seats, then one per wave
+#define WT_SEATS (MM_MAX_TEAMS * 8)           // seats a LobbyDev has room for
+
+struct WaitGroupDev {                         // mm_wait_group (include/mm_wait.h) with a type atomicAdd takes
+    uint32_t waiting, oldest_age;
+    unsigned long long age_sum;
+    uint32_t hist[33];
+    uint32_t pad;
+};
+
+struct WaitParams {
+    uint32_t mode, n_groups, capacity, teams;
+    uint32_t now, max_age;
+    uint32_t max_chunks;                      // chunks `rows` has room for
+    const ChainDev* chains;
+    const uint32_t* q_slot;
+    const uint32_t* stamp;
+    uint8_t* state;
+    uint32_t* rows;                           // [chunk][WT_ROWS]; behind them the total ([max_chunks * WT_ROWS])
+    uint32_t* out_slot;                       // the expired, in order: slot | rating group | age
+    uint32_t* out_group;
+    uint32_t* out_age;
+    WaitGroupDev* stats;                      // [n_groups], zeroed by the host
+};
+
+static __device__ __forceinline__ uint32_t wait_chunks_of(uint32_t len) { return len ? (len + WT_CHUNK - 1u) / WT_CHUNK : 1u; }
+
+// Chunk b of the mode -> its rating group, the chunk's number inside the group and the queue's length.  false: past the
+// last chunk.  The same for every thread of a workgroup.
+static __device__ __forceinline__ bool wait_chunk(const WaitParams& P, uint32_t b, uint32_t& g, uint32_t& k, uint32_t& len)
+{
+    if (b >= P.max_chunks) return false;
+    uint32_t base = 0;
+    for (g = 0; g < P.n_groups; ++g) {
+        len = dev_min_u32(P.chains[P.mode * P.n_groups + g].len, P.capacity);
+        const uint32_t nb = wait_chunks_of(len);
+        if (b < base + nb) { k = b - base; return true; }
+        base += nb;
+    }
+    return false;
+}
+
+// The idx-th seated player of a stored lobby in mm_lobby_state's order (team by team), MM_NO_SLOT past the last.
+static __device__ __forceinline__ uint32_t wait_seat(const LobbyDev& lb, uint32_t teams, uint32_t idx)
+{
+    for (uint32_t t = 0; t < teams && t < MM_MAX_TEAMS; ++t) {
+        const uint32_t c = dev_min_u32(lb.cnt[t], 8u);
+        if (idx < c) return lb.slot[t][idx];
+        idx -= c;
+    }
+    return MM_NO_SLOT;
+}
+
+// Is the player in `sl` waiting (LIVE: not cancelled, not expired before), and for how long?
+static __device__ __forceinline__ bool wait_age(const WaitParams& P, uint32_t sl, uint32_t& age)
+{
+    if (sl >= P.capacity || P.state[sl] != MM_ST_LIVE) return false;
+    age = P.now - P.stamp[sl];
+    return true;
+}
+
+// A wave's WT_PER_WAVE queue entries from w0 on: the slots, then their ages — every load of a level issued before the
+// first one is used (the gathers are latency, not bandwidth).  Bit r of the result: this lane's entry r is waiting.
+#define WT_ITERS (WT_PER_WAVE / 64)
+static __device__ __forceinline__ uint32_t wait_load(const WaitParams& P, size_t qo, uint32_t w0, uint32_t len, int lane,
+                                                     uint32_t (&sl)[WT_ITERS], uint32_t (&age)[WT_ITERS])
+{
+    uint32_t live = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < WT_ITERS; ++r) {
+        const uint32_t i = w0 + r * 64 + lane;
+        sl[r] = i < len ? P.q_slot[qo + i] : MM_NO_SLOT;
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < WT_ITERS; ++r) {
+        age[r] = 0;
+        if (wait_age(P, sl[r], age[r])) live |= 1u << r;
+    }
+    return live;
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_wait_fill(uint32_t n, uint32_t* __restrict__ stamp, uint32_t now)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) stamp[i] = now;
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_wait_count(WaitParams P)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        uint32_t cnt = 0;
+        if (w0 < len) {
+            uint32_t sl[WT_ITERS], age[WT_ITERS];
+            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r)
+                cnt += (uint32_t)__popcll(__ballot(((live >> r) & 1u) && age[r] > P.max_age));
+        }
+        if (lane == 0) P.rows[(size_t)b * WT_ROWS + 1u + wave] = cnt;
+        if (wave == 0) {
+            uint32_t age = 0;
+            const bool sel = k == 0u && (uint32_t)lane < WT_SEATS &&
+                             wait_age(P, wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane), age) && age > P.max_age;
+            const unsigned long long m = __ballot(sel);
+            if (lane == 0) P.rows[(size_t)b * WT_ROWS] = (uint32_t)__popcll(m);
+        }
+    }
+}
+
+// Exclusive scan down the rows of k_wait_count, in place; the total behind them.  One workgroup.
+__global__ __launch_bounds__(WT_THREADS) void k_wait_scan(WaitParams P)
+{
+    __shared__ uint32_t wtot[WT_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t chunks = 0;
+    for (uint32_t g = 0; g < P.n_groups; ++g) chunks += wait_chunks_of(dev_min_u32(P.chains[P.mode * P.n_groups + g].len, P.capacity));
+    chunks = dev_min_u32(chunks, P.max_chunks);
+    const uint32_t n_rows = chunks * WT_ROWS;
+    const uint32_t per = (n_rows + WT_THREADS - 1) / WT_THREADS;
+    const uint32_t r0 = dev_min_u32(tid * per, n_rows), r1 = dev_min_u32(r0 + per, n_rows);
+    uint32_t s = 0;
+    for (uint32_t r = r0; r < r1; ++r) s += P.rows[r];
+    const uint32_t incl = wave_incl_scan(s, lane);
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    uint32_t run = incl - s;
+    for (int w = 0; w < wave; ++w) run += wtot[w];
+    for (uint32_t r = r0; r < r1; ++r) {
+        const uint32_t h = P.rows[r];
+        P.rows[r] = run;
+        run += h;
+    }
+    if (tid == 0) {
+        uint32_t total = 0;
+        for (int w = 0; w < WT_WAVES; ++w) total += wtot[w];
+        P.rows[(size_t)P.max_chunks * WT_ROWS] = total;
+    }
+}
+
+// Every selected player at its rank, and marked as k_cancel marks a slot.  A slot is in one queue or one lobby, once:
+// the mark a thread sets is read by nobody else, so the selection is the one k_wait_count counted.
+__global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        uint32_t base = P.rows[(size_t)b * WT_ROWS + 1u + wave];
+        if (w0 < len) {
+            uint32_t sl[WT_ITERS], age[WT_ITERS];
+            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) {
+                const bool sel = ((live >> r) & 1u) && age[r] > P.max_age;
+                const unsigned long long m = __ballot(sel);
+                const uint32_t at = base + (uint32_t)__popcll(m & lt);
+                if (sel && at < P.capacity) {
+                    P.out_slot[at] = sl[r];
+                    P.out_group[at] = g;
+                    P.out_age[at] = age[r];
+                    P.state[sl[r]] = MM_ST_CANCELLED;
+                }
+                base += (uint32_t)__popcll(m);
+            }
+        }
+        if (wave == 0) {
+            uint32_t age = 0, sl = MM_NO_SLOT;
+            if (k == 0u && (uint32_t)lane < WT_SEATS) sl = wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane);
+            const bool sel = wait_age(P, sl, age) && age > P.max_age;
+            const unsigned long long m = __ballot(sel);
+            const uint32_t at = P.rows[(size_t)b * WT_ROWS] + (uint32_t)__popcll(m & lt);
+            if (sel && at < P.capacity) {
+                P.out_slot[at] = sl;
+                P.out_group[at] = g;
+                P.out_age[at] = age;
+                P.state[sl] = MM_ST_CANCELLED;
+            }
+        }
+    }
+}
+
+static __device__ __forceinline__ uint32_t wait_bucket(uint32_t age) { return age ? 64u - (uint32_t)__clzll((long long)age) : 0u; }
+
+// mm_wait_stats: one streaming pass over the same chunks.  Counts, sums and maxima in registers, reduced per wave; the
+// histogram in LDS; a workgroup merges its chunk into the group's record with one atomic per non-empty field.
+__global__ __launch_bounds__(WT_THREADS) void k_wait_stats(WaitParams P)
+{
+    __shared__ uint32_t s_hist[33];
+    __shared__ uint32_t s_cnt, s_max;
+    __shared__ unsigned long long s_sum;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        if (tid < 33) s_hist[tid] = 0;
+        if (tid == 0) { s_cnt = 0; s_max = 0; s_sum = 0; }
+        __syncthreads();
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        uint32_t cnt = 0, mx = 0;
+        unsigned long long sum = 0;
+        if (wave == 0 && k == 0u && (uint32_t)lane < WT_SEATS) {
+            uint32_t age = 0;
+            if (wait_age(P, wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane), age)) {
+                cnt = 1; mx = age; sum = age;
+                atomicAdd(&s_hist[wait_bucket(age)], 1u);
+            }
+        }
+        if (w0 < len) {
+            uint32_t sl[WT_ITERS], age[WT_ITERS];
+            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r)
+                if ((live >> r) & 1u) {
+                    ++cnt;
+                    mx = age[r] > mx ? age[r] : mx;
+                    sum += age[r];
+                    atomicAdd(&s_hist[wait_bucket(age[r])], 1u);
+                }
+        }
+        for (int d = 32; d >= 1; d >>= 1) {
+            const uint32_t c2 = (uint32_t)__shfl((int)cnt, lane ^ d), m2 = (uint32_t)__shfl((int)mx, lane ^ d);
+            const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)sum, lane ^ d), hi = (uint32_t)__shfl((int)(uint32_t)(sum >> 32), lane ^ d);
+            cnt += c2;
+            mx = m2 > mx ? m2 : mx;
+            sum += ((unsigned long long)hi << 32) | lo;
+        }
+        if (lane == 0 && cnt) {
+            atomicAdd(&s_cnt, cnt);
+            atomicMax(&s_max, mx);
+            atomicAdd(&s_sum, sum);
+        }
+        __syncthreads();
+        WaitGroupDev* const out = P.stats + g;
+        if (tid < 33 && s_hist[tid]) atomicAdd(&out->hist[tid], s_hist[tid]);
+        if (tid == 64 && s_cnt) {
+            atomicAdd(&out->waiting, s_cnt);
+            atomicMax(&out->oldest_age, s_max);
+            atomicAdd(&out->age_sum, s_sum);
+        }
+        __syncthreads();
+    }
 }
 
 // ------------------------------------------------------------------------------------
@@ -886,7 +1157,22 @@ __global__ __launch_bounds__(256) void k_pack_results(PackArgs A, const uint32_t
     pk[(size_t)A.total * A.L + i] = __float_as_uint(out_score[(size_t)g * A.out_rec_stride + j]);
     pk[(size_t)A.total * (A.L + 1u) + i] = out_pass[(size_t)g * A.out_rec_stride + j];
 }
-#define MM_PACK_MAX 8192u            // lobbies of a tick up to which its match list is packed on the device
+// mm_matches_wait (include/mm_wait.h): how long every player of the tick's lobbies had waited, gathered over the groups'
+// emission logs into one piece laid out like mm_matches' slots (emission order, L words a lobby).  Runs at the end of a
+// tick, only while the clock is on: afterwards a matched slot is free and a later enqueue stamps it again.
+__global__ __launch_bounds__(256) void k_wait_matched(PackArgs A, const uint32_t* __restrict__ out_slots,
+                                                      const uint32_t* __restrict__ stamp, uint32_t capacity, uint32_t now,
+                                                      uint32_t* __restrict__ wait)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;   // one thread per seat: coalesced loads of the logs, coalesced stores
+    if (i >= A.total * A.L) return;
+    const uint32_t lobby = i / A.L;
+    uint32_t g = 0;
+    while (g + 1u < A.n_groups && lobby >= A.pre[g + 1u]) ++g;
+    const uint32_t sl = out_slots[(size_t)g * A.out_slot_stride + (size_t)(i - A.pre[g] * A.L)];
+    wait[i] = sl < capacity ? now - stamp[sl] : 0u;
+}
+#define MM_PACK_MAX 8192u           // lobbies of a tick up to which its match list is packed on the device
 
 // The TAIL of a big tick's match list — what the last kernels of the walk emitted, after the last early send — straight
 // into the engine's pinned host buffers, each lobby at its final place (the buffers are device-accessible: hipHostMalloc).
@@ -1073,6 +1359,18 @@ struct mm_engine {
     bool poisoned;             // a tick failed half way: everything but reset / restore / destroy answers MM_ERR_STATE
     uint32_t fault_tick;       // MM_DEBUG_FAIL_TICK=k: the k-th mm_tick of this engine fails after its walk (test hook)
     uint32_t ticks_seen;
+    // the clock (include/mm_wait.h): nothing below is allocated, and no kernel of it runs, before the first mm_clock_set
+    bool clock_on;
+    uint32_t clock_now;
+    uint32_t* d_stamp;         // [capacity] the clock when the slot's player was enqueued
+    uint32_t* d_wt_rows;       // [wt_max_chunks][WT_ROWS] + 1: k_wait_count's counters / k_wait_scan's ranks, the total behind them
+    uint32_t wt_max_chunks;
+    uint32_t* d_wt_out;        // [3][capacity] the last mm_expire's list on the device: slot | rating group | age
+    WaitGroupDev* d_wt_stats;  // [MM_MAX_GROUPS]
+    uint32_t* d_wt_matched;    // waits of the last tick's matched players (k_wait_matched)
+    std::vector<uint32_t> x_slot, x_group, x_age;   // the last mm_expire's list (mm_expired)
+    uint32_t* h_mwait;         // pinned, as large as d_wt_matched: mm_matches_wait, emission order, r_L words a lobby
+    uint32_t mw_n;             // lobbies of the last tick h_mwait covers (0: the clock was off at that tick)
 };
 
 // Named ranges for a profiler's timeline (the reference logs nothing per attempt).  MM_ROCTX=1 makes
@@ -1335,6 +1633,12 @@ extern "C" void mm_engine_destroy(mm_engine* e)
     (void)hipFree(e->d_pk_grec);
     (void)hipFree(e->d_pk_pbar);
     (void)hipFree(e->d_pack);
+    (void)hipFree(e->d_stamp);
+    (void)hipFree(e->d_wt_rows);
+    (void)hipFree(e->d_wt_out);
+    (void)hipFree(e->d_wt_stats);
+    (void)hipFree(e->d_wt_matched);
+    if (e->h_mwait) (void)hipHostFree(e->h_mwait);
     if (e->h_pchains) (void)hipHostFree(e->h_pchains);
     if (e->h_look_seq) (void)hipHostFree(e->h_look_seq);
     if (e->h_tchains) (void)hipHostFree(e->h_tchains);
@@ -1513,6 +1817,9 @@ extern "C" int mm_engine_create_ex(const mm_config* cfg, const mm_tuning* tuning
         e->live_upper = 0;
         e->poisoned = false;
         e->ticks_seen = 0;
+        e->clock_on = false;
+        e->clock_now = 0;
+        e->mw_n = 0;
         {
             // the tuning record (include/mm_engine.h, mm_tuning): validated by the caller below; the engine keeps it (mm_tuning_get)
             // and its working copies — some of which change while it runs (pair_persist after a PF_XCD stop)
@@ -1705,6 +2012,8 @@ extern "C" int mm_reset(mm_engine* e)
         e->next_slot = 0;
         e->cancel_pending = 0;
         e->r_n = 0;
+        e->mw_n = 0;
+        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear();   // (the clock itself goes on: include/mm_wait.h)
         e->live_upper = 0;
         std::fill(e->tk_last_len.begin(), e->tk_last_len.end(), 0u);
         const int rc = engine_reset_device(e);
@@ -1761,7 +2070,7 @@ static int enqueue_device_impl(mm_engine* e, uint32_t n, const int32_t* d_rating
                        e->d_wave_hist, e->d_chains, e->cfg.capacity);
     hipLaunchKernelGGL(k_bucket_scatter, dim3(blocks), dim3(BK_THREADS), 0, e->stream, n, d_rating, d_cons, d_group, B,
                        e->n_chains, e->d_wave_hist, e->next_slot, d_slot_sel, e->d_q_rating, e->d_q_cons, e->d_q_slot,
-                       e->d_state, d_out_slot);
+                       e->d_state, d_out_slot, e->clock_on ? e->d_stamp : (uint32_t*)NULL, e->clock_now);
     HIPCHK(e, hipGetLastError());
     if (timing) HIPCHK(e, hipEventRecord(e->ev[1], e->stream));
     HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, e->d_counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
@@ -2743,6 +3052,7 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
     const bool timing = (cfg.flags & MM_CFG_TIMING) != 0;
     const bool purge = e->cancel_pending > 0;
     e->r_n = 0;
+    e->mw_n = 0;
     e->r_L = M.L;
     {   // mm_path_stats_get: this tick's record (the totals go on)
         const uint32_t tot = e->ps.team_flags_late_total;
@@ -2928,6 +3238,20 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
     e->r_released.resize(nrel);
     if (nrel)
         HIPCHK(e, hipMemcpyAsync(e->r_released.data(), e->d_released, nrel * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    if (e->clock_on && total > 0u) {
+        // mm_matches_wait: the waits of the matched, while their stamps are still theirs (the emission logs are final:
+        // the stream was synchronised above).  Queued BEHIND the match list's tail, so the list reaches the host as early
+        // as without the clock; the copy goes into pinned memory and is covered by this tick's last synchronisation
+        PackArgs A;
+        memset(&A, 0, sizeof(A));
+        A.n_groups = G; A.L = M.L; A.total = total; A.out_slot_stride = e->out_slot_stride; A.out_rec_stride = e->out_rec_stride;
+        for (uint32_t g = 0; g < G; ++g) A.pre[g + 1u] = A.pre[g] + e->h_chains[mode * G + g].n_out;
+        const uint32_t words = total * M.L;
+        hipLaunchKernelGGL(k_wait_matched, dim3((words + 255u) / 256u), dim3(256), 0, e->stream, A, e->d_out_slots, e->d_stamp,
+                           cfg.capacity, e->clock_now, e->d_wt_matched);
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipMemcpyAsync(e->h_mwait, e->d_wt_matched, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    }
     {
         int src = results_absorb(e, M.L);
         if (src) return src;
@@ -2949,6 +3273,7 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
         e->live_upper = e->live_upper >= gone ? e->live_upper - gone : 0;
     }
     e->r_n = total;
+    e->mw_n = e->clock_on ? total : 0u;
     if (n_matches) *n_matches = total;
     if (e->ps.paths & MM_PATH_PAIR) {            // mm_path_stats_get: the chain with the most passes, by launch shape
         // ... among the chains the pair path walked: one k_walk took (PairChain.fast == 0: a rating span beyond the packed key)
@@ -3128,6 +3453,7 @@ extern "C" int mm_lobby_state(mm_engine* e, uint32_t mode, uint32_t group, uint3
 // ------------------------------------------------------------------------------------
 // pool snapshot / restore
 // ------------------------------------------------------------------------------------
+static int wait_alloc(mm_engine* e);
 struct SnapHeader {
     uint32_t magic, version, abi, header_bytes;
     uint32_t capacity, n_groups, n_modes, n_chains;
@@ -3172,6 +3498,7 @@ extern "C" int mm_snapshot_size(mm_engine* e, uint64_t* bytes)
         if (rc) return rc;
         uint64_t n = sizeof(SnapHeader) + e->cfg.capacity + (uint64_t)e->n_chains * sizeof(ChainDev);
         for (uint32_t c = 0; c < e->n_chains; ++c) n += (uint64_t)e->h_chains[c].len * 12u;
+        if (e->clock_on) n += 4u + (uint64_t)e->cfg.capacity * 4u;   // version 2: the clock and the stamps behind the v1 payload
         *bytes = n;
         return MM_OK;
     } catch (const std::bad_alloc&) {
@@ -3195,7 +3522,7 @@ extern "C" int mm_snapshot(mm_engine* e, void* buf, uint64_t cap, uint64_t* writ
         SnapHeader h;
         memset(&h, 0, sizeof(h));
         h.magic = MM_SNAP_MAGIC;
-        h.version = 1;
+        h.version = e->clock_on ? 2u : 1u;                    // an engine that never set its clock writes what it always wrote
         h.abi = MM_ABI_VERSION;
         h.header_bytes = (uint32_t)sizeof(SnapHeader);
         h.capacity = e->cfg.capacity;
@@ -3222,6 +3549,11 @@ extern "C" int mm_snapshot(mm_engine* e, void* buf, uint64_t cap, uint64_t* writ
             HIPCHK(e, hipMemcpyAsync(out + off + len * 8u, e->d_q_slot + c * cap_q, len * 4u, hipMemcpyDeviceToHost, e->stream));
             off += len * 12u;
         }
+        if (e->clock_on) {                                                       // include/mm_wait.h: the clock, then stamp[capacity]
+            memcpy(out + off, &e->clock_now, 4u);
+            HIPCHK(e, hipMemcpyAsync(out + off + 4u, e->d_stamp, cap_q * 4u, hipMemcpyDeviceToHost, e->stream));
+            off += 4u + cap_q * 4u;
+        }
         HIPCHK(e, hipStreamSynchronize(e->stream));
         h.payload_hash = snap_hash(out + sizeof(SnapHeader), (size_t)need - sizeof(SnapHeader), 0xCBF29CE484222325ull);
         memcpy(out, &h, sizeof(h));
@@ -3242,7 +3574,7 @@ extern "C" int mm_restore(mm_engine* e, const void* buf, uint64_t bytes)
         const unsigned char* in = (const unsigned char*)buf;
         SnapHeader h;
         memcpy(&h, in, sizeof(h));
-        if (h.magic != MM_SNAP_MAGIC || h.version != 1u || h.abi != MM_ABI_VERSION || h.header_bytes != sizeof(SnapHeader) ||
+        if (h.magic != MM_SNAP_MAGIC || (h.version != 1u && h.version != 2u) || h.abi != MM_ABI_VERSION || h.header_bytes != sizeof(SnapHeader) ||
             h.chain_bytes != sizeof(ChainDev) || h.total_bytes != bytes || h.capacity != e->cfg.capacity ||
             h.n_groups != e->cfg.n_groups || h.n_modes != e->cfg.n_modes || h.n_chains != e->n_chains ||
             h.cfg_hash != snap_cfg_hash(e->cfg))
@@ -3259,9 +3591,15 @@ extern "C" int mm_restore(mm_engine* e, const void* buf, uint64_t bytes)
             if (cd.len > h.capacity) return MM_ERR_INVALID_ARG;
             need += (uint64_t)cd.len * 12u;
         }
+        if (h.version == 2u) need += 4u + (uint64_t)h.capacity * 4u;
         if (need != bytes) return MM_ERR_INVALID_ARG;
         int rc = mm_reset(e);
         if (rc) return rc;
+        e->clock_on = false;                                 // a version-1 snapshot has no clock: the feature is off again
+        if (h.version == 2u) {
+            rc = wait_alloc(e);
+            if (rc) return rc;
+        }
         memcpy(e->h_state.data(), in + sizeof(SnapHeader), h.capacity);
         HIPCHK(e, hipMemcpyAsync(e->d_state, e->h_state.data(), h.capacity, hipMemcpyHostToDevice, e->stream));
         memcpy(e->h_chains, in + off, (size_t)h.n_chains * sizeof(ChainDev));
@@ -3281,7 +3619,13 @@ extern "C" int mm_restore(mm_engine* e, const void* buf, uint64_t bytes)
             HIPCHK(e, hipMemcpyAsync(e->d_q_slot + c * cap_q, in + off + len * 8u, len * 4u, hipMemcpyHostToDevice, e->stream));
             off += len * 12u;
         }
+        if (h.version == 2u)
+            HIPCHK(e, hipMemcpyAsync(e->d_stamp, in + off + 4u, cap_q * 4u, hipMemcpyHostToDevice, e->stream));
         HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (h.version == 2u) {
+            memcpy(&e->clock_now, in + off, 4u);
+            e->clock_on = true;
+        }
         e->next_slot = h.next_slot;
         e->cancel_pending = h.cancel_pending;
         e->live_upper = h.live_upper;
@@ -3291,6 +3635,209 @@ extern "C" int mm_restore(mm_engine* e, const void* buf, uint64_t bytes)
     } catch (...) {
         return MM_ERR_INTERNAL;
     }
+}
+
+// ------------------------------------------------------------------------------------
+// the clock (include/mm_wait.h)
+// ------------------------------------------------------------------------------------
+static_assert(sizeof(WaitGroupDev) == sizeof(mm_wait_group) && offsetof(WaitGroupDev, age_sum) == offsetof(mm_wait_group, age_sum) &&
+              offsetof(WaitGroupDev, hist) == offsetof(mm_wait_group, hist) && MM_WAIT_HIST == 33u, "WaitGroupDev is mm_wait_group");
+
+// The device arrays of the feature, at the first mm_clock_set (or a version-2 mm_restore).
+static int wait_alloc(mm_engine* e)
+{
+    if (e->d_stamp) return MM_OK;
+    (void)hipFree(e->d_wt_rows); (void)hipFree(e->d_wt_out); (void)hipFree(e->d_wt_stats); (void)hipFree(e->d_wt_matched);   // (an earlier attempt that ran out of memory)
+    if (e->h_mwait) (void)hipHostFree(e->h_mwait);
+    e->d_wt_rows = NULL; e->d_wt_out = NULL; e->d_wt_stats = NULL; e->d_wt_matched = NULL; e->h_mwait = NULL;
+    const size_t cap = e->cfg.capacity;
+    // the queues of one mode hold at most `capacity` players between them: sum of ceil(len / WT_CHUNK) <= capacity / WT_CHUNK + groups
+    e->wt_max_chunks = (uint32_t)(cap / WT_CHUNK + e->cfg.n_groups + 1u);
+    HIPCHK(e, hipMalloc((void**)&e->d_wt_rows, ((size_t)e->wt_max_chunks * WT_ROWS + 1u) * sizeof(uint32_t)));
+    HIPCHK(e, hipMalloc((void**)&e->d_wt_out, 3u * cap * sizeof(uint32_t)));
+    HIPCHK(e, hipMalloc((void**)&e->d_wt_stats, MM_MAX_GROUPS * sizeof(WaitGroupDev)));
+    HIPCHK(e, hipMalloc((void**)&e->d_wt_matched, (cap + (size_t)MM_MAX_LOBBY * MM_MAX_GROUPS + 64u) * sizeof(uint32_t)));
+    HIPCHK(e, hipHostMalloc((void**)&e->h_mwait, (cap + (size_t)MM_MAX_LOBBY * MM_MAX_GROUPS + 64u) * sizeof(uint32_t), hipHostMallocDefault));
+    HIPCHK(e, hipMalloc((void**)&e->d_stamp, cap * sizeof(uint32_t)));   // last: its presence says all of them are there
+    return MM_OK;
+}
+
+static WaitParams wait_params(const mm_engine* e, uint32_t mode, uint32_t max_age)
+{
+    WaitParams P;
+    memset(&P, 0, sizeof(P));
+    P.mode = mode;
+    P.n_groups = e->cfg.n_groups;
+    P.capacity = e->cfg.capacity;
+    P.teams = e->cfg.modes[mode].teams;
+    P.now = e->clock_now;
+    P.max_age = max_age;
+    P.max_chunks = e->wt_max_chunks;
+    P.chains = e->d_chains;
+    P.q_slot = e->d_q_slot;
+    P.stamp = e->d_stamp;
+    P.state = e->d_state;
+    P.rows = e->d_wt_rows;
+    P.out_slot = e->d_wt_out;
+    P.out_group = e->d_wt_out + e->cfg.capacity;
+    P.out_age = e->d_wt_out + 2u * (size_t)e->cfg.capacity;
+    P.stats = e->d_wt_stats;
+    return P;
+}
+
+// Workgroups for a pass over the mode's chunks: enough for everybody who can be queued (live_upper bounds the players of
+// all modes), never more than there are chunks; the kernels stride over the chunks, so a smaller grid is only slower.
+static uint32_t wait_grid(const mm_engine* e)
+{
+    const unsigned long long want = e->live_upper / WT_CHUNK + e->cfg.n_groups;
+    return (uint32_t)(want < e->wt_max_chunks ? want : e->wt_max_chunks);
+}
+
+extern "C" int mm_clock_set(mm_engine* e, uint32_t now)
+{
+    try {
+        if (!e) return MM_ERR_INVALID_ARG;
+        if (e->poisoned) return MM_ERR_STATE;
+        if (e->clock_on) {
+            if ((int32_t)(now - e->clock_now) < 0) return MM_ERR_RANGE;
+            e->clock_now = now;
+            return MM_OK;
+        }
+        ON_ENGINE_DEVICE(e);
+        int rc = wait_alloc(e);
+        if (rc) return rc;
+        // whoever waits already has waited since now (a slot nobody holds gets its stamp when it is handed out)
+        const uint32_t cap = e->cfg.capacity;
+        hipLaunchKernelGGL(k_wait_fill, dim3((cap + WT_THREADS - 1u) / WT_THREADS), dim3(WT_THREADS), 0, e->stream, cap, e->d_stamp, now);
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        e->clock_now = now;
+        e->clock_on = true;
+        return MM_OK;
+    } catch (const std::bad_alloc&) {
+        return MM_ERR_OOM;
+    } catch (...) {
+        return MM_ERR_INTERNAL;
+    }
+}
+
+extern "C" int mm_clock_get(const mm_engine* e, uint32_t* now, uint32_t* enabled)
+{
+    if (!e) return MM_ERR_INVALID_ARG;
+    if (now) *now = e->clock_now;
+    if (enabled) *enabled = e->clock_on ? 1u : 0u;
+    return MM_OK;
+}
+
+// *marked_on_device: k_wait_scatter has been queued — from there on the device's ActiveUser mirror may hold marks the
+// host's does not know yet, and a failure must not leave the engine usable (mm_expire below).
+static int expire_impl(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t* n_expired, bool* marked_on_device)
+{
+    {
+        const WaitParams P = wait_params(e, mode, max_age);
+        const uint32_t grid = wait_grid(e);
+        uint32_t* const d_total = e->d_wt_rows + (size_t)e->wt_max_chunks * WT_ROWS;
+        hipLaunchKernelGGL(k_wait_count, dim3(grid), dim3(WT_THREADS), 0, e->stream, P);
+        hipLaunchKernelGGL(k_wait_scan, dim3(1), dim3(WT_THREADS), 0, e->stream, P);
+        HIPCHK(e, hipGetLastError());
+        *marked_on_device = true;
+        hipLaunchKernelGGL(k_wait_scatter, dim3(grid), dim3(WT_THREADS), 0, e->stream, P);
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        const uint32_t k = e->h_counters[1];
+        if (k > e->cfg.capacity) return MM_ERR_INTERNAL;
+        if (k == 0u) return MM_OK;
+        e->x_slot.resize(k); e->x_group.resize(k); e->x_age.resize(k);
+        HIPCHK(e, hipMemcpyAsync(e->x_slot.data(), P.out_slot, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipMemcpyAsync(e->x_group.data(), P.out_group, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipMemcpyAsync(e->x_age.data(), P.out_age, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        // the host mirrors, as mm_cancel leaves them for these slots
+        uint32_t marked = 0;
+        for (uint32_t i = 0; i < k; ++i) {
+            const uint32_t sl = e->x_slot[i];
+            if (sl < e->cfg.capacity && e->h_state[sl] == MM_ST_LIVE) { e->h_state[sl] = MM_ST_CANCELLED; ++marked; }
+        }
+        e->cancel_pending += k;
+        if (n_expired) *n_expired = k;
+        return marked == k ? MM_OK : MM_ERR_INTERNAL;         // (the device's ActiveUser mirror and the host's disagree)
+    }
+}
+
+extern "C" int mm_expire(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t* n_expired)
+{
+    if (!e || mode >= e->cfg.n_modes) return MM_ERR_INVALID_ARG;
+    if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
+    ON_ENGINE_DEVICE(e);
+    RoctxRange rr("mm_expire");
+    e->x_slot.clear(); e->x_group.clear(); e->x_age.clear();
+    if (n_expired) *n_expired = 0;
+    bool marked_on_device = false;
+    int rc;
+    try {
+        rc = expire_impl(e, mode, max_age, n_expired, &marked_on_device);
+    } catch (const std::bad_alloc&) {
+        rc = MM_ERR_OOM;
+    } catch (...) {
+        rc = MM_ERR_INTERNAL;
+    }
+    if (rc != MM_OK) {
+        // no half-filled list for mm_expired; and once the marks may be on the device while h_state and cancel_pending do
+        // not have them, the pool is as undefined as after a tick that failed half way: mm_reset or mm_restore (mm_engine.h)
+        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear();
+        if (n_expired) *n_expired = 0;
+        if (marked_on_device) {
+            (void)hipStreamSynchronize(e->stream);
+            e->poisoned = true;
+        }
+    }
+    return rc;
+}
+
+extern "C" int mm_expired(mm_engine* e, uint32_t first, uint32_t count, uint32_t* slots, uint32_t* group, uint32_t* age)
+{
+    if (!e) return MM_ERR_INVALID_ARG;
+    if (e->poisoned) return MM_ERR_STATE;
+    const size_t n = e->x_slot.size();
+    if (first > n || count > n - first) return MM_ERR_RANGE;
+    if (count == 0) return MM_OK;
+    if (slots) memcpy(slots, &e->x_slot[first], (size_t)count * sizeof(uint32_t));
+    if (group) memcpy(group, &e->x_group[first], (size_t)count * sizeof(uint32_t));
+    if (age) memcpy(age, &e->x_age[first], (size_t)count * sizeof(uint32_t));
+    return MM_OK;
+}
+
+extern "C" int mm_wait_stats(mm_engine* e, uint32_t mode, mm_wait_group* per_group)
+{
+    try {
+        if (!e || !per_group || mode >= e->cfg.n_modes) return MM_ERR_INVALID_ARG;
+        if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
+        ON_ENGINE_DEVICE(e);
+        RoctxRange rr("mm_wait_stats");
+        const WaitParams P = wait_params(e, mode, 0u);
+        const uint32_t G = e->cfg.n_groups;
+        HIPCHK(e, hipMemsetAsync(e->d_wt_stats, 0, G * sizeof(WaitGroupDev), e->stream));
+        hipLaunchKernelGGL(k_wait_stats, dim3(wait_grid(e)), dim3(WT_THREADS), 0, e->stream, P);
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipMemcpyAsync(per_group, e->d_wt_stats, G * sizeof(mm_wait_group), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        return MM_OK;
+    } catch (const std::bad_alloc&) {
+        return MM_ERR_OOM;
+    } catch (...) {
+        return MM_ERR_INTERNAL;
+    }
+}
+
+extern "C" int mm_matches_wait(mm_engine* e, uint32_t first, uint32_t count, uint32_t* wait)
+{
+    if (!e) return MM_ERR_INVALID_ARG;
+    if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
+    if (first > e->mw_n || count > e->mw_n - first) return MM_ERR_RANGE;
+    if (count == 0 || !wait) return MM_OK;
+    memcpy(wait, &e->h_mwait[(size_t)first * e->r_L], (size_t)count * e->r_L * sizeof(uint32_t));
+    return MM_OK;
 }
 
 extern "C" int mm_last_hip_error(const mm_engine* e) { return e ? e->last_hip : 0; }

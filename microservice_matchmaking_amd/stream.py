@@ -45,13 +45,18 @@ def stream_schedule(qps, seconds, tick_ms, seed):
     return out
 
 
-def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=True, batches=None):
+def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=True, batches=None, ttl_ms=None):
     """Drive `search` (a sharding.ShardedSearch: one engine + the chains this rank owns) through
     the schedule.  Returns a dict with per-mode latency arrays (real, floor), matched players,
     per-tick cost and a digest per chain of everything it emitted, in order.
     `batches`: the arrivals of every tick of the schedule, made by the caller before the clock starts
     (stream_batch(n, seed, ...) per entry — at 200 000 players a tick numpy needs longer than the 10 ms period to
-    draw them, and a leg would fall behind because of the host, not the engine)."""
+    draw them, and a leg would fall behind because of the host, not the engine).
+    `ttl_ms`: a search time-out (include/mm_wait.h; the reference has none).  Every period the engine's clock is set to the
+    period's end in milliseconds, every mode expires whoever has waited longer than ttl_ms, then the modes tick.  The result
+    then also holds `expired` (players per mode), `wait_ms` (per mode, the engine's own figure for every matched player:
+    clock at its tick minus clock at its enqueue — whole periods, beside `real` and `floor`) and `depth_max` (per mode,
+    the deepest the queues were after a tick).  None: no clock, nothing of this runs."""
     assert batches is None or len(batches) == len(schedule)
     cfg = search.cfg
     n_modes, n_groups = int(cfg.n_modes), int(cfg.n_groups)
@@ -65,6 +70,9 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
     matched = 0
     first = 0
     full_at_s = None
+    expired = [0] * n_modes
+    wait_ms = [[] for _ in range(n_modes)]
+    depth_max = [0] * n_modes
     # (a generation-2 collection of the interpreter's heap is a pause of tens of milliseconds in one tick of a real-time
     # run: nothing here makes reference cycles, so the collector rests until the stream is over)
     import gc
@@ -86,6 +94,8 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
                     if left > 0.0006:
                         time.sleep(left - 0.0004)
             t0 = time.perf_counter()
+            if ttl_ms is not None:
+                search.engine.clock_set(int(round(t_close * 1e3)))  # this period's arrivals are stamped with its end
             try:
                 search.enqueue(rating, cons, first_global_index=first)
             except MMError as ex:
@@ -97,9 +107,16 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
                 full_at_s = t_open
                 break
             first += n
+            if ttl_ms is not None:
+                for md in range(n_modes):
+                    expired[md] += int(search.engine.expire(md, int(ttl_ms))[0].size)
             for md in range(n_modes):
                 m = search.tick(md)
                 t1 = time.perf_counter()
+                if ttl_ms is not None:
+                    if len(m):
+                        wait_ms[md].append(search.engine.matches_wait().ravel().astype(np.float64))
+                    depth_max[md] = max(depth_max[md], int(search.engine.queue_depth(md).sum()))
                 if len(m):
                     ids = search.global_ids(m)
                     flat = ids.ravel()
@@ -118,12 +135,15 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
     elapsed = time.perf_counter() - t_start
     depth = [search.engine.queue_depth(md).astype(np.int64) for md in range(n_modes)]
     cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0)
-    return {
+    out = {
         "real": [cat(x) for x in real], "floor": [cat(x) for x in floor],
         "matched": matched, "elapsed": elapsed, "tick_cost": np.asarray(tick_cost),
         "depth": depth, "digests": {k: h.hexdigest() for k, h in hashers.items()}, "lobbies": emitted,
         "arrivals": total, "ingested": first, "full_at_s": full_at_s,
     }
+    if ttl_ms is not None:
+        out.update({"expired": expired, "wait_ms": [cat(x) for x in wait_ms], "depth_max": depth_max})
+    return out
 
 
 def latency_summary(real, floor):

@@ -1,0 +1,146 @@
+#!/usr/bin/env python
+"""What the engine clock (include/mm_wait.h) costs on BASELINE cfg-2's pool (1M players, 1v1, +-25 rating, region
+filter): mm_expire at 0 %, 1 % and 50 % expired, mm_wait_stats, the tick with the clock on beside the same tick with it
+off, the enqueue with stamps beside the enqueue without.  Medians over --steps steps (at least 20); both variants of a
+pair run in the same process, step by step in turns.  The yardstick for mm_expire and mm_wait_stats is `bucket_ms`, the
+HIP-event time of bucketing the same 1M players, measured here: both move about the same bytes per player.
+
+mm_expire and mm_wait_stats are timed on the host around the call (what the owner waits for: launches, the
+synchronisation, and for mm_expire the copy of the list and the host mirror's update); the kernels' own durations come
+from a kernel trace of this script (rocprofv3 --kernel-trace --stats -- python tools/bench_wait.py --steps 20).
+
+Usage (GPU box, repo root):  python tools/bench_wait.py [--steps 30] [--players 1000000] > profiles/wait_1m.json"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def med(xs):
+    return float(np.median(np.asarray(xs, dtype=np.float64)))
+
+
+def spread(xs):
+    a = np.asarray(xs, dtype=np.float64)
+    return {"median": float(np.median(a)), "p10": float(np.percentile(a, 10)), "p90": float(np.percentile(a, 90)), "n": int(a.size)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--players", type=int, default=1_000_000)
+    ap.add_argument("--clock-first", action="store_true",
+                    help="create the engine with the clock before the one without (two engines are two sets of allocations: "
+                         "does a difference between their ticks follow the clock or the engine's place in memory?)")
+    args = ap.parse_args()
+    assert args.steps >= 20, "medians of at least 20 steps"
+    import torch
+    assert torch.cuda.is_available(), "needs a GPU; there is no CPU path"
+    from bench import kernel_source_hash
+    from microservice_matchmaking_amd import Engine, make_config, mode_1v1
+    from microservice_matchmaking_amd.synth import make_pool
+
+    n = args.players
+    cap = 1 << (n - 1).bit_length()
+    cfg = make_config([mode_1v1(window=25, region_filter=True)], capacity=cap, timing=True)
+    rating, cons = make_pool(n, seed=1)
+    d_rating = torch.from_numpy(rating).cuda()
+    d_cons = torch.from_numpy(cons.view(np.int32)).cuda()
+    if args.clock_first:
+        on, off = Engine(cfg), Engine(cfg)
+    else:
+        off, on = Engine(cfg), Engine(cfg)
+    on.clock_set(1)
+
+    # ---- enqueue and tick, clock off / on, in turns -------------------------------------------------------------------
+    rows = {"off": {"bucket_ms": [], "enqueue_total_ms": [], "tick_total_ms": [], "walk_ms": [], "step_ms": []},
+            "on": {"bucket_ms": [], "enqueue_total_ms": [], "tick_total_ms": [], "walk_ms": [], "step_ms": []}}
+    lobbies = {}
+    now = 1
+    for k in range(args.warmup + args.steps):
+        for name, eng in (("off", off), ("on", on)) if k % 2 == 0 else (("on", on), ("off", off)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.reset()
+            if name == "on":
+                now += 10
+                eng.clock_set(now)
+            eng.enqueue_device(d_rating, d_cons)
+            m = eng.tick(0, reuse=True)
+            t1 = time.perf_counter()
+            if k >= args.warmup:
+                r = rows[name]
+                r["bucket_ms"].append(eng.last_enqueue_stats["bucket_ms"])
+                r["enqueue_total_ms"].append(eng.last_enqueue_stats["total_ms"])
+                r["tick_total_ms"].append(m.stats["total_ms"])
+                r["walk_ms"].append(m.stats["walk_ms"])
+                r["step_ms"].append((t1 - t0) * 1e3)
+            lobbies[name] = len(m)
+    assert lobbies["on"] == lobbies["off"]
+    w = on.matches_wait()
+    assert w.shape == (lobbies["on"], 2) and not w.any()      # stamped and matched under the same clock
+
+    # ---- mm_expire at 0 %, 1 %, 50 % and mm_wait_stats over the whole pool ---------------------------------------------
+    expire = {}
+    stats_ms = []
+    for label, frac in (("0pct", 0.0), ("1pct", 0.01), ("50pct", 0.5)):
+        old = int(n * frac)
+        d_r0, d_c0, d_r1, d_c1 = d_rating[:old], d_cons[:old], d_rating[old:], d_cons[old:]
+        call, got = [], None
+        for k in range(args.warmup + args.steps):
+            on.reset()
+            now += 10
+            on.clock_set(now)
+            if old:
+                on.enqueue_device(d_r0, d_c0)
+            now += 100
+            on.clock_set(now)
+            on.enqueue_device(d_r1, d_c1)
+            if label == "0pct":
+                t0 = time.perf_counter()
+                st = on.wait_stats(0)
+                t1 = time.perf_counter()
+                assert sum(g["waiting"] for g in st) == n
+                if k >= args.warmup:
+                    stats_ms.append((t1 - t0) * 1e3)
+            t0 = time.perf_counter()
+            got = on.expire(0, 50)
+            t1 = time.perf_counter()
+            assert got[0].size == old
+            if k >= args.warmup:
+                call.append((t1 - t0) * 1e3)
+        expire[label] = {"expired": old, "call_ms": spread(call)}
+
+    bucket = med(rows["off"]["bucket_ms"])
+    out = {
+        "workload": "cfg-2: %d players, 1v1, +-25 rating + region filter, uniform ratings, capacity %d" % (n, cap),
+        "source_hash": kernel_source_hash(), "steps": args.steps, "warmup": args.warmup,
+        "device": torch.cuda.get_device_name(0), "created_first": "clock on" if args.clock_first else "clock off",
+        "enqueue": {"bucket_ms_clock_off": spread(rows["off"]["bucket_ms"]), "bucket_ms_clock_on": spread(rows["on"]["bucket_ms"]),
+                    "total_ms_clock_off": spread(rows["off"]["enqueue_total_ms"]), "total_ms_clock_on": spread(rows["on"]["enqueue_total_ms"])},
+        "tick": {"total_ms_clock_off": spread(rows["off"]["tick_total_ms"]), "total_ms_clock_on": spread(rows["on"]["tick_total_ms"]),
+                 "walk_ms_clock_off": spread(rows["off"]["walk_ms"]), "walk_ms_clock_on": spread(rows["on"]["walk_ms"]),
+                 "step_ms_clock_off": spread(rows["off"]["step_ms"]), "step_ms_clock_on": spread(rows["on"]["step_ms"]),
+                 "lobbies": lobbies["on"],
+                 "note": "clock on: the tick also gathers the matched players' waits (k_wait_matched) and copies them to the host"},
+        "expire": expire,
+        "wait_stats": {"call_ms": spread(stats_ms)},
+        "yardstick": {"bucket_ms": bucket,
+                      "expire_call_over_bucket": {k: v["call_ms"]["median"] / bucket for k, v in expire.items()},
+                      "wait_stats_call_over_bucket": med(stats_ms) / bucket,
+                      "note": "call_ms is host time around the call (launches + synchronisation + copies), bucket_ms the HIP-event "
+                              "time of three kernels: the kernels' own durations are in the kernel trace of this script"},
+    }
+    print(json.dumps(out, indent=1))
+    off.close()
+    on.close()
+
+
+if __name__ == "__main__":
+    main()
