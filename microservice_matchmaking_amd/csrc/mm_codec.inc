@@ -246,13 +246,9 @@ extern "C" int mm_decode_players(const mm_config* cfg, const mm_codec_cfg* cc, c
                                  int32_t* rating, uint32_t* cons, uint8_t* group, uint8_t* status,
                                  uint32_t* id_off, uint32_t* id_len)
 {
-    try {                                              // nothing unwinds into a NIF frame
+    return guarded([&]() -> int {                      // nothing unwinds into a NIF frame
         return decode_players_impl(cfg, cc, buf, off, n, rating, cons, group, status, id_off, id_len);
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 static int decode_players_impl(const mm_config* cfg, const mm_codec_cfg* cc, const char* buf, const uint64_t* off, uint32_t n,
@@ -612,7 +608,7 @@ extern "C" int mm_encode_lobby(const char* game_mode, uint32_t teams, uint32_t t
 {
     if (!game_mode || !payload || !payload_len || !written || (cap && !out)) return MM_ERR_INVALID_ARG;
     if (teams < 1 || teams > MM_MAX_TEAMS || team_size < 1 || teams * team_size > MM_MAX_LOBBY) return MM_ERR_INVALID_ARG;
-    try {
+    return guarded([&]() -> int {
         EncOut o{out, cap, 0};
         // descending keys on every level: "teams" > "game-mode"; "team 2" > "team 1" (fewer than ten teams)
         o.put("{\"teams\":{", 10);
@@ -639,9 +635,5 @@ extern "C" int mm_encode_lobby(const char* game_mode, uint32_t teams, uint32_t t
         o.ch('}');
         *written = o.n;
         return o.n <= cap ? MM_OK : MM_ERR_RANGE;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }

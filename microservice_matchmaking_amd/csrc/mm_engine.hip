@@ -20,8 +20,8 @@
 //   k_bucket_count / k_bucket_scan / k_bucket_scatter   stable multi-way partition of an
 //           arrival batch into chain tails (A1 bucketing); HBM streaming, wave-ballot ranks.
 //   k_cancel, k_purge   ActiveUser.remove_user + the "vanish when popped" rule.
-//   k_wait_*   the clock (include/mm_wait.h): expiry selection as a stable stream compaction over the mode's queues,
-//           wait statistics, the waits of a tick's matched players.  DESIGN.md §4.6.
+//   mm_wait.inc   the clock (include/mm_wait.h), k_wait_*: expiry selection as a stable stream compaction over the mode's
+//           queues, wait statistics; k_wait_matched (the waits of a tick's matched players) is here.  DESIGN.md §4.6.
 //   k_walk   one workgroup per chain: LDS-staged tiles of the queue, wave-0 first-fit chain
 //           (ballot + ffs arg-min over queue position), in-place survivor compaction.
 //           The chain is inherently sequential (each match decides the next anchor), so
@@ -34,6 +34,13 @@
 //   mm_team.inc   the team-mode walk: per pass, role sub-queues and F[a] = the player the
 //           cursor picks after a's lobby, for every queued a at once, then a pointer chase
 //           (kt_build / kt_f / kt_f2 / kt_chase / kt_fc / kt_late).  DESIGN.md §4.4.
+//   mm_codec.inc  include/mm_codec.h: the enqueue-side codec (host code).
+//
+// Host side, from `struct mm_engine` on: HIPCHK / MMTRY / guarded (one guard of each kind), the engine's memory (dev_alloc /
+// pin_alloc / mem_release: every buffer recorded in mm_engine::mem, freed by mm_engine_destroy), k_tune (every knob's row: name,
+// environment variable, default, range, what was measured) and mm_engine::tn (the one copy of the knobs), create / destroy,
+// enqueue / cancel, the match list's way to the host, pair_walk / team_walk with their report_*
+// functions (MM_PAIR_DEBUG), mm_tick / tick_impl with path_stats_*, snapshot / restore, the clock's host functions.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -393,268 +400,14 @@ __global__ __launch_bounds__(256) void k_reset(uint32_t n_chains, ChainDev* __re
 // ------------------------------------------------------------------------------------
 // the clock (include/mm_wait.h): expiry selection, wait statistics
 // ------------------------------------------------------------------------------------
-// The waiting players of a mode are walked in ONE order by every kernel here — rating group ascending; within a group
-// the stored lobby's seats as mm_lobby_state lists them, then the queue from head to tail — cut into chunks of WT_CHUNK
-// queue entries, one workgroup per chunk (a chain of 300 000 players is 147 workgroups, not k_purge's one).  A group
-// has at least one chunk: an empty queue may still have a stored lobby, and the group's first chunk carries its seats.
-// mm_expire is count / scan / scatter over that order, the shape of k_bucket_*: per-wave counts, one exclusive scan
-// down the (chunk, wave) rows, then every wave writes its selected entries at base + wave-ballot rank — a stable
-// compaction, so the list is in queue order.  Per entry: q_slot streamed, stamp[slot] and state[slot] gathered.
+// the chunk geometry of mm_wait.inc's kernels (the host sizes buffers and grids by it; tests read WT_CHUNK from this file)
 #define WT_THREADS 256
 #define WT_WAVES 4
 #define WT_PER_WAVE 512                       // queue entries per wave per chunk
 #define WT_CHUNK (WT_WAVES * WT_PER_WAVE)     // queue entries per workgroup
 #define WT_ROWS (WT_WAVES + 1)                // counters per chunk: the stored lobby's seats, then one per wave
 #define WT_SEATS (MM_MAX_TEAMS * 8)           // seats a LobbyDev has room for
-
-struct WaitGroupDev {                         // mm_wait_group (include/mm_wait.h) with a type atomicAdd takes
-    uint32_t waiting, oldest_age;
-    unsigned long long age_sum;
-    uint32_t hist[33];
-    uint32_t pad;
-};
-
-struct WaitParams {
-    uint32_t mode, n_groups, capacity, teams;
-    uint32_t now, max_age;
-    uint32_t max_chunks;                      // chunks `rows` has room for
-    const ChainDev* chains;
-    const uint32_t* q_slot;
-    const uint32_t* stamp;
-    uint8_t* state;
-    uint32_t* rows;                           // [chunk][WT_ROWS]; behind them the total ([max_chunks * WT_ROWS])
-    uint32_t* out_slot;                       // the expired, in order: slot | rating group | age
-    uint32_t* out_group;
-    uint32_t* out_age;
-    WaitGroupDev* stats;                      // [n_groups], zeroed by the host
-};
-
-static __device__ __forceinline__ uint32_t wait_chunks_of(uint32_t len) { return len ? (len + WT_CHUNK - 1u) / WT_CHUNK : 1u; }
-
-// Chunk b of the mode -> its rating group, the chunk's number inside the group and the queue's length.  false: past the
-// last chunk.  The same for every thread of a workgroup.
-static __device__ __forceinline__ bool wait_chunk(const WaitParams& P, uint32_t b, uint32_t& g, uint32_t& k, uint32_t& len)
-{
-    if (b >= P.max_chunks) return false;
-    uint32_t base = 0;
-    for (g = 0; g < P.n_groups; ++g) {
-        len = dev_min_u32(P.chains[P.mode * P.n_groups + g].len, P.capacity);
-        const uint32_t nb = wait_chunks_of(len);
-        if (b < base + nb) { k = b - base; return true; }
-        base += nb;
-    }
-    return false;
-}
-
-// The idx-th seated player of a stored lobby in mm_lobby_state's order (team by team), MM_NO_SLOT past the last.
-static __device__ __forceinline__ uint32_t wait_seat(const LobbyDev& lb, uint32_t teams, uint32_t idx)
-{
-    for (uint32_t t = 0; t < teams && t < MM_MAX_TEAMS; ++t) {
-        const uint32_t c = dev_min_u32(lb.cnt[t], 8u);
-        if (idx < c) return lb.slot[t][idx];
-        idx -= c;
-    }
-    return MM_NO_SLOT;
-}
-
-// Is the player in `sl` waiting (LIVE: not cancelled, not expired before), and for how long?
-static __device__ __forceinline__ bool wait_age(const WaitParams& P, uint32_t sl, uint32_t& age)
-{
-    if (sl >= P.capacity || P.state[sl] != MM_ST_LIVE) return false;
-    age = P.now - P.stamp[sl];
-    return true;
-}
-
-// A wave's WT_PER_WAVE queue entries from w0 on: the slots, then their ages — every load of a level issued before the
-// first one is used (the gathers are latency, not bandwidth).  Bit r of the result: this lane's entry r is waiting.
-#define WT_ITERS (WT_PER_WAVE / 64)
-static __device__ __forceinline__ uint32_t wait_load(const WaitParams& P, size_t qo, uint32_t w0, uint32_t len, int lane,
-                                                     uint32_t (&sl)[WT_ITERS], uint32_t (&age)[WT_ITERS])
-{
-    uint32_t live = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < WT_ITERS; ++r) {
-        const uint32_t i = w0 + r * 64 + lane;
-        sl[r] = i < len ? P.q_slot[qo + i] : MM_NO_SLOT;
-    }
-#pragma unroll
-    for (uint32_t r = 0; r < WT_ITERS; ++r) {
-        age[r] = 0;
-        if (wait_age(P, sl[r], age[r])) live |= 1u << r;
-    }
-    return live;
-}
-
-__global__ __launch_bounds__(WT_THREADS) void k_wait_fill(uint32_t n, uint32_t* __restrict__ stamp, uint32_t now)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) stamp[i] = now;
-}
-
-__global__ __launch_bounds__(WT_THREADS) void k_wait_count(WaitParams P)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
-        uint32_t cnt = 0;
-        if (w0 < len) {
-            uint32_t sl[WT_ITERS], age[WT_ITERS];
-            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
-#pragma unroll
-            for (uint32_t r = 0; r < WT_ITERS; ++r)
-                cnt += (uint32_t)__popcll(__ballot(((live >> r) & 1u) && age[r] > P.max_age));
-        }
-        if (lane == 0) P.rows[(size_t)b * WT_ROWS + 1u + wave] = cnt;
-        if (wave == 0) {
-            uint32_t age = 0;
-            const bool sel = k == 0u && (uint32_t)lane < WT_SEATS &&
-                             wait_age(P, wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane), age) && age > P.max_age;
-            const unsigned long long m = __ballot(sel);
-            if (lane == 0) P.rows[(size_t)b * WT_ROWS] = (uint32_t)__popcll(m);
-        }
-    }
-}
-
-// Exclusive scan down the rows of k_wait_count, in place; the total behind them.  One workgroup.
-__global__ __launch_bounds__(WT_THREADS) void k_wait_scan(WaitParams P)
-{
-    __shared__ uint32_t wtot[WT_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t chunks = 0;
-    for (uint32_t g = 0; g < P.n_groups; ++g) chunks += wait_chunks_of(dev_min_u32(P.chains[P.mode * P.n_groups + g].len, P.capacity));
-    chunks = dev_min_u32(chunks, P.max_chunks);
-    const uint32_t n_rows = chunks * WT_ROWS;
-    const uint32_t per = (n_rows + WT_THREADS - 1) / WT_THREADS;
-    const uint32_t r0 = dev_min_u32(tid * per, n_rows), r1 = dev_min_u32(r0 + per, n_rows);
-    uint32_t s = 0;
-    for (uint32_t r = r0; r < r1; ++r) s += P.rows[r];
-    const uint32_t incl = wave_incl_scan(s, lane);
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    uint32_t run = incl - s;
-    for (int w = 0; w < wave; ++w) run += wtot[w];
-    for (uint32_t r = r0; r < r1; ++r) {
-        const uint32_t h = P.rows[r];
-        P.rows[r] = run;
-        run += h;
-    }
-    if (tid == 0) {
-        uint32_t total = 0;
-        for (int w = 0; w < WT_WAVES; ++w) total += wtot[w];
-        P.rows[(size_t)P.max_chunks * WT_ROWS] = total;
-    }
-}
-
-// Every selected player at its rank, and marked as k_cancel marks a slot.  A slot is in one queue or one lobby, once:
-// the mark a thread sets is read by nobody else, so the selection is the one k_wait_count counted.
-__global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
-        uint32_t base = P.rows[(size_t)b * WT_ROWS + 1u + wave];
-        if (w0 < len) {
-            uint32_t sl[WT_ITERS], age[WT_ITERS];
-            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
-#pragma unroll
-            for (uint32_t r = 0; r < WT_ITERS; ++r) {
-                const bool sel = ((live >> r) & 1u) && age[r] > P.max_age;
-                const unsigned long long m = __ballot(sel);
-                const uint32_t at = base + (uint32_t)__popcll(m & lt);
-                if (sel && at < P.capacity) {
-                    P.out_slot[at] = sl[r];
-                    P.out_group[at] = g;
-                    P.out_age[at] = age[r];
-                    P.state[sl[r]] = MM_ST_CANCELLED;
-                }
-                base += (uint32_t)__popcll(m);
-            }
-        }
-        if (wave == 0) {
-            uint32_t age = 0, sl = MM_NO_SLOT;
-            if (k == 0u && (uint32_t)lane < WT_SEATS) sl = wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane);
-            const bool sel = wait_age(P, sl, age) && age > P.max_age;
-            const unsigned long long m = __ballot(sel);
-            const uint32_t at = P.rows[(size_t)b * WT_ROWS] + (uint32_t)__popcll(m & lt);
-            if (sel && at < P.capacity) {
-                P.out_slot[at] = sl;
-                P.out_group[at] = g;
-                P.out_age[at] = age;
-                P.state[sl] = MM_ST_CANCELLED;
-            }
-        }
-    }
-}
-
-static __device__ __forceinline__ uint32_t wait_bucket(uint32_t age) { return age ? 64u - (uint32_t)__clzll((long long)age) : 0u; }
-
-// mm_wait_stats: one streaming pass over the same chunks.  Counts, sums and maxima in registers, reduced per wave; the
-// histogram in LDS; a workgroup merges its chunk into the group's record with one atomic per non-empty field.
-__global__ __launch_bounds__(WT_THREADS) void k_wait_stats(WaitParams P)
-{
-    __shared__ uint32_t s_hist[33];
-    __shared__ uint32_t s_cnt, s_max;
-    __shared__ unsigned long long s_sum;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
-        if (tid < 33) s_hist[tid] = 0;
-        if (tid == 0) { s_cnt = 0; s_max = 0; s_sum = 0; }
-        __syncthreads();
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
-        uint32_t cnt = 0, mx = 0;
-        unsigned long long sum = 0;
-        if (wave == 0 && k == 0u && (uint32_t)lane < WT_SEATS) {
-            uint32_t age = 0;
-            if (wait_age(P, wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane), age)) {
-                cnt = 1; mx = age; sum = age;
-                atomicAdd(&s_hist[wait_bucket(age)], 1u);
-            }
-        }
-        if (w0 < len) {
-            uint32_t sl[WT_ITERS], age[WT_ITERS];
-            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
-#pragma unroll
-            for (uint32_t r = 0; r < WT_ITERS; ++r)
-                if ((live >> r) & 1u) {
-                    ++cnt;
-                    mx = age[r] > mx ? age[r] : mx;
-                    sum += age[r];
-                    atomicAdd(&s_hist[wait_bucket(age[r])], 1u);
-                }
-        }
-        for (int d = 32; d >= 1; d >>= 1) {
-            const uint32_t c2 = (uint32_t)__shfl((int)cnt, lane ^ d), m2 = (uint32_t)__shfl((int)mx, lane ^ d);
-            const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)sum, lane ^ d), hi = (uint32_t)__shfl((int)(uint32_t)(sum >> 32), lane ^ d);
-            cnt += c2;
-            mx = m2 > mx ? m2 : mx;
-            sum += ((unsigned long long)hi << 32) | lo;
-        }
-        if (lane == 0 && cnt) {
-            atomicAdd(&s_cnt, cnt);
-            atomicMax(&s_max, mx);
-            atomicAdd(&s_sum, sum);
-        }
-        __syncthreads();
-        WaitGroupDev* const out = P.stats + g;
-        if (tid < 33 && s_hist[tid]) atomicAdd(&out->hist[tid], s_hist[tid]);
-        if (tid == 64 && s_cnt) {
-            atomicAdd(&out->waiting, s_cnt);
-            atomicMax(&out->oldest_age, s_max);
-            atomicAdd(&out->age_sum, s_sum);
-        }
-        __syncthreads();
-    }
-}
+#include "mm_wait.inc"
 
 // ------------------------------------------------------------------------------------
 // the walk kernel: Search.Worker.consume/5 to quiescence, one workgroup per chain
@@ -1207,7 +960,7 @@ __global__ __launch_bounds__(256) void k_results_tail(TailArgs A, const uint32_t
 // kernel, which stores them into the engine's PINNED host buffer (fine-grained: the stores go out over the link as they
 // are performed) and then, with a release at system scope, the look's sequence number; the host polls that word in its
 // own memory and goes on the moment it arrives — no copy command, no signal, no wake-up.  What it is worth: see
-// mm_engine_create (look_poll).
+// k_tune (look_poll).
 __global__ __launch_bounds__(256) void k_look(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst_host, uint32_t nwords,
                                               uint32_t* seq_host, uint32_t seq)
 {
@@ -1233,8 +986,11 @@ static __device__ __forceinline__ bool team_chain_is_fast(const struct TeamChain
 // host side: the C ABI
 // ------------------------------------------------------------------------------------
 
+struct MemBlock { void* p; bool pinned; };   // a buffer the engine owns: hipMalloc'ed, or hipHostMalloc'ed (pinned)
+
 struct mm_engine {
     mm_config cfg;
+    std::vector<MemBlock> mem;          // every d_* and pinned h_* buffer below (dev_alloc / pin_alloc)
     uint32_t n_chains;
     hipStream_t stream;
     hipEvent_t ev[4];
@@ -1275,39 +1031,23 @@ struct mm_engine {
     uint16_t* d_pk_exa[2];
     uint32_t* d_pk_bitsp[2];
     uint32_t* d_pk_headp[2];
-    bool pair_persist;         // MM_PAIR_PERSIST=0: never several passes per launch (kp_rounds); one launch per pass as before (A/B)
-    uint32_t pair_ptiles;      // MM_PAIR_PTILES: tiles of the longest chain a kp_rounds batch may have (one workgroup per CU of ONE XCD: 32)
+    // run-time state of kp_rounds (the knobs are in `tn`)
+    bool kp_rounds_off;        // a chain found itself on two XCDs (PF_XCD): never several passes per launch again on this engine
     uint32_t pair_pcool;       // batches for which kp_rounds stays off after a launch that gave up (a time-out: somebody else holds the CUs)
     uint32_t pair_pstops;      // launches that gave up so far (diagnostics)
-    uint32_t pair_pinject;     // MM_PAIR_PINJECT: PairParams.pinject (tests)
-    uint32_t pair_pbatch;      // MM_PAIR_PBATCH: passes per kp_rounds launch at most (it ends earlier when the longest chain wants its compaction)
-    uint32_t pair_ptimeout[2]; // MM_PAIR_PTIMEOUT_US: what a workgroup waits at the first / at a later barrier, in 100 MHz ticks
     unsigned long long* d_pk_pbar;   // [group] arrival words, then [group] XCD masks (one allocation)
     uint32_t round_ctr;
     uint32_t* d_pk_tilectl;
     uint32_t* d_pack;          // the packed match list of a small tick (k_pack_results)
     uint4* d_pk_grec;          // second level of the route (kp_group)
     uint32_t pk_gstride;
-    uint32_t pair_nxseg;       // MM_PAIR_NXSEG: anchors per workgroup of kp_nx_init (0: 256)
-    uint32_t pair_nxstage;     // MM_PAIR_NXSTAGE: entries it stages in LDS, anchors included (0: NXI_STAGE)
-    bool pair_xcd;             // MM_PAIR_XCD=0: kp_round on the plain (tile, group) grid (A/B)
-    uint32_t pair_group_min;   // MM_PAIR_GROUP: tiles of the longest chain from which a batch runs with the second level (0 = never)
     PairChain* h_pchains;      // pinned
     uint32_t* h_look_seq;      // pinned: the sequence number of the last look whose records have arrived (k_look)
     uint32_t look_seq;
-    bool results_tail_kernel;  // MM_RESULTS_TAIL=0: the tail of a tick's match list as copy commands, as before (A/B)
-    bool look_poll;            // MM_LOOK_POLL=0: looks as a D2H copy + stream synchronisation, as before (A/B)
     uint32_t ps_hand[4][MM_MAX_GROUPS];   // per rating group at the pair path's last look: passes, lobbies, kp_rounds passes, kp_rounds hops
     mm_path_stats ps;          // mm_path_stats_get: the launch shapes and fall-backs of the last tick (totals carried over)
-    mm_tuning tn;              // the record the engine was created with (mm_tuning_get); the working copies are the fields around here
-    uint32_t team_fwait, team_fix_max, team_fix_t8, team_fix_t4, team_pull_xcd, team_nowait;   // MM_TEAM_* knobs of kt_f / kt_fc, read once at create
+    mm_tuning tn;              // every knob, as the engine was created with it and never changed (mm_tuning_get; the rows of k_tune say what each is)
     uint32_t pk_bits_stride, pk_max_tiles, pk_stride;
-    uint32_t pair_batch;       // MM_PAIR_BATCH: tiled rounds launched per host look at the chains
-    bool force_generic;        // MM_FORCE_GENERIC=1: always walk with k_walk (A/B testing)
-    bool pair_debug;           // MM_PAIR_DEBUG=1: print the pair path's diagnostics per tick
-    uint32_t pair_tune;        // MM_PAIR_TUNE: PairParams.tune
-    bool pair_tile_fixed;      // MM_PAIR_TILE=max: every batch with the largest tile length (A/B)
-    uint32_t pair_tiles_max;   // MM_PAIR_TILES: tiles of the longest chain a batch may have before the next larger tile length is taken
     unsigned long long live_upper;   // upper bound of queued players (grid sizing)
     // team path (mm_team.inc): shares the pair path's arrays, plus
     TeamChain* d_tchains;
@@ -1320,17 +1060,9 @@ struct mm_engine {
     uint32_t* d_tk_chunkB;     // [group][role][tk_chunk_stride] chunk populations when kt_build last ran
     uint32_t* d_tk_fdone;      // [group][tk_chunk_stride] kt_fc: the launch (team_seq) whose kt_f chunk has stored its F
     uint32_t team_seq;         // kt_chase / kt_fc launches of this engine so far (never 0: it names a launch to its workgroups)
-    uint32_t team_emit_max;    // MM_TEAM_EMIT_MAX
-    uint32_t team_split;       // MM_TEAM_SPLIT: the stored lobby's fill in kt_f's launch (the lobby-rich passes)
     uint32_t* d_tk_sqi;        // [group][pk_stride] position -> sub-queue entry
-    uint32_t team_rebuild;     // MM_TEAM_REBUILD: kt_build runs in the first two passes of a tick and every this many after
     uint32_t tk_memb;          // largest lobby of a team mode, less the anchor
-    uint32_t team_f2;          // MM_TEAM_F2: passes of a tick that compose F with itself (0 = never)
     uint32_t tk_chunk_stride;
-    uint32_t team_batch;       // MM_TEAM_BATCH: passes launched per host look at the chains
-    uint32_t team_cap;         // MM_TEAM_CAP: TeamParams.scan_cap
-    uint32_t team_late;        // MM_TEAM_LATE: lobbies per pass at or under which kt_late takes the chains over (0 = never)
-    uint32_t team_late0;       // MM_TEAM_LATE0: arrivals of a mode since its last tick at or under which kt_late walks the tick from its first pass
     std::vector<uint32_t> tk_last_len;   // [chain] queue + stored lobby after the chain's last tick (what a quiescent tick left)
     uint32_t dbg_last_w, dbg_last_c;   // MM_PAIR_DEBUG + MM_TEAM_BATCH=1: per-pass deltas of the F counters
     // host
@@ -1355,10 +1087,8 @@ struct mm_engine {
     uint32_t r_sent[MM_MAX_GROUPS];     // lobbies of the running tick already on their way / arrived
     uint32_t r_marked[MM_MAX_GROUPS];   // ... whose players' slots are FREE in h_state already
     bool r_based;
-    bool results_early;        // MM_RESULTS_EARLY=0: the whole match list after the walk (A/B)
     bool poisoned;             // a tick failed half way: everything but reset / restore / destroy answers MM_ERR_STATE
-    uint32_t fault_tick;       // MM_DEBUG_FAIL_TICK=k: the k-th mm_tick of this engine fails after its walk (test hook)
-    uint32_t ticks_seen;
+    uint32_t ticks_seen;       // mm_ticks of this engine so far (tn.fail_tick)
     // the clock (include/mm_wait.h): nothing below is allocated, and no kernel of it runs, before the first mm_clock_set
     bool clock_on;
     uint32_t clock_now;
@@ -1426,6 +1156,59 @@ static double host_now_ms(void)
             return _rc == hipErrorOutOfMemory ? MM_ERR_OOM : MM_ERR_HIP; \
         }                                                 \
     } while (0)
+
+// ... and a status of our own (MM_ERR_*): the caller returns what the callee returned
+#define MMTRY(expr)                \
+    do {                           \
+        const int _st = (expr);    \
+        if (_st) return _st;       \
+    } while (0)
+
+// The body of an exported function: nothing may unwind into the caller (a NIF frame, a ctypes call).
+template <class F>
+static int guarded(F&& body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return MM_ERR_OOM;
+    } catch (...) {
+        return MM_ERR_INTERNAL;
+    }
+}
+
+// The engine's memory.  Every device and pinned buffer is allocated through dev_alloc / pin_alloc — one hipMalloc or
+// hipHostMalloc each, never a slice of a larger block: under the CPU shim each is a heap block of its own, which is what
+// lets AddressSanitizer see a kernel run past one — and recorded in mm_engine::mem.  mm_engine_destroy frees what is
+// recorded; mem_release gives one buffer back early (the ones that regrow, a failed attempt).
+static int mem_take(mm_engine* e, void** out, size_t bytes, bool pinned)
+{
+    e->mem.push_back({ NULL, pinned });            // the record first: no room for it fails before the block exists
+    void* p = NULL;
+    const hipError_t rc = pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+    if (rc != hipSuccess) {
+        e->mem.pop_back();
+        e->last_hip = (int)rc;
+        return rc == hipErrorOutOfMemory ? MM_ERR_OOM : MM_ERR_HIP;
+    }
+    e->mem.back().p = p;
+    *out = p;
+    return MM_OK;
+}
+template <class T> static int dev_alloc(mm_engine* e, T*& p, size_t bytes) { return mem_take(e, (void**)&p, bytes, false); }
+template <class T> static int pin_alloc(mm_engine* e, T*& p, size_t bytes) { return mem_take(e, (void**)&p, bytes, true); }
+static void mem_free(const MemBlock& b) { (void)(b.pinned ? hipHostFree(b.p) : hipFree(b.p)); }
+template <class T>
+static void mem_release(mm_engine* e, T*& p)
+{
+    for (size_t i = 0; p && i < e->mem.size(); ++i)
+        if (e->mem[i].p == (void*)p) {
+            mem_free(e->mem[i]);
+            e->mem.erase(e->mem.begin() + (ptrdiff_t)i);
+            break;
+        }
+    p = NULL;
+}
 
 // HIP's current device is per-THREAD state, and the callers this ABI is shaped for do not keep a
 // thread: a dirty NIF runs on whichever dirty scheduler is free (native/mm_nif.c), the resource
@@ -1594,59 +1377,7 @@ extern "C" void mm_engine_destroy(mm_engine* e)
     if (!e) return;
     DeviceScope dev_scope(e->cfg.device);   // frees and the stream belong to the engine's device
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    (void)hipFree(e->d_q_rating);
-    (void)hipFree(e->d_q_cons);
-    (void)hipFree(e->d_q_slot);
-    (void)hipFree(e->d_chains);
-    (void)hipFree(e->d_state);
-    (void)hipFree(e->d_released);
-    (void)hipFree(e->d_counters);
-    (void)hipFree(e->d_wave_hist);
-    (void)hipFree(e->d_in_rating);
-    (void)hipFree(e->d_in_cons);
-    (void)hipFree(e->d_in_group);
-    (void)hipFree(e->d_in_slot);
-    (void)hipFree(e->d_in_sel);
-    (void)hipFree(e->d_out_slots);
-    (void)hipFree(e->d_out_score);
-    (void)hipFree(e->d_out_pass);
-    (void)hipFree(e->d_pchains);
-    (void)hipFree(e->d_tchains);
-    (void)hipFree(e->d_tk_chunk);
-    (void)hipFree(e->d_tk_fv2);
-    (void)hipFree(e->d_tk_fpos);
-    (void)hipFree(e->d_tk_memb);
-    (void)hipFree(e->d_tk_bitsB);
-    (void)hipFree(e->d_tk_chunkB);
-    (void)hipFree(e->d_tk_fdone);
-    (void)hipFree(e->d_tk_sqi);
-    for (int b = 0; b < 2; ++b) {
-        (void)hipFree(e->d_pk_key[b]); (void)hipFree(e->d_pk_oidx[b]);
-        (void)hipFree(e->d_pk_nx16[b]); (void)hipFree(e->d_pk_bits[b]);
-    }
-    (void)hipFree(e->d_pk_scratch);
-    (void)hipFree(e->d_pk_wpre);
-    (void)hipFree(e->d_pk_g16);
-    (void)hipFree(e->d_pk_rec1);
-    for (int b = 0; b < 2; ++b) { (void)hipFree(e->d_pk_exa[b]); (void)hipFree(e->d_pk_bitsp[b]); (void)hipFree(e->d_pk_headp[b]); }
-    (void)hipFree(e->d_pk_tilectl);
-    (void)hipFree(e->d_pk_grec);
-    (void)hipFree(e->d_pk_pbar);
-    (void)hipFree(e->d_pack);
-    (void)hipFree(e->d_stamp);
-    (void)hipFree(e->d_wt_rows);
-    (void)hipFree(e->d_wt_out);
-    (void)hipFree(e->d_wt_stats);
-    (void)hipFree(e->d_wt_matched);
-    if (e->h_mwait) (void)hipHostFree(e->h_mwait);
-    if (e->h_pchains) (void)hipHostFree(e->h_pchains);
-    if (e->h_look_seq) (void)hipHostFree(e->h_look_seq);
-    if (e->h_tchains) (void)hipHostFree(e->h_tchains);
-    if (e->h_rslots) (void)hipHostFree(e->h_rslots);
-    if (e->h_rscore) (void)hipHostFree(e->h_rscore);
-    if (e->h_rpass) (void)hipHostFree(e->h_rpass);
-    if (e->h_chains) (void)hipHostFree(e->h_chains);
-    if (e->h_counters) (void)hipHostFree(e->h_counters);
+    for (const MemBlock& b : e->mem) mem_free(b);
     for (int i = 0; i < 4; ++i)
         if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
     for (int i = 0; i < 2; ++i)
@@ -1675,39 +1406,52 @@ static int engine_reset_device(mm_engine* e)
 struct TuneDesc { const char* name; const char* env; uint32_t off, def, lo, hi, kind; };   // kind 1: zero or a power of two in [lo, hi]
 #define MM_TD(f, envname, def, lo, hi, kind) { #f, envname, (uint32_t)offsetof(mm_tuning, f), def, lo, hi, kind }
 static const TuneDesc k_tune[] = {
-    MM_TD(force_generic, "MM_FORCE_GENERIC", 0u, 0u, 1u, 0u),
-    MM_TD(debug, "MM_PAIR_DEBUG", 0u, 0u, 1u, 0u),
-    MM_TD(results_early, "MM_RESULTS_EARLY", 1u, 0u, 1u, 0u),
-    MM_TD(results_tail, "MM_RESULTS_TAIL", 1u, 0u, 1u, 0u),
+    MM_TD(force_generic, "MM_FORCE_GENERIC", 0u, 0u, 1u, 0u),             // 1: always walk with k_walk (A/B testing)
+    MM_TD(debug, "MM_PAIR_DEBUG", 0u, 0u, 1u, 0u),                        // 1: print the pair and team paths' diagnostics per tick
+    MM_TD(results_early, "MM_RESULTS_EARLY", 1u, 0u, 1u, 0u),             // 0: the whole match list after the walk (A/B)
+    MM_TD(results_tail, "MM_RESULTS_TAIL", 1u, 0u, 1u, 0u),               // 0: the tail of a tick's match list as copy commands, as before (A/B)
+    // look_poll, 0: looks as a D2H copy + stream synchronisation.  OFF by default.  Measured (profiles/r05_ab_look_poll.txt,
+    // cfg-2 / cfg-3, 40 steps, twice each on one box): the median step gains 0.03 ms of 10.1 (1v1) and 0.05 ms of 8.5 (5v5) — the
+    // copy + synchronisation of a look is NOT where a tick's time goes — and every polled 1v1 run had ONE step of 17 ms: a host
+    // thread that spins for the whole tick is what a container's CPU quota throttles first (a dirty scheduler of the BEAM would
+    // fare no better).
     MM_TD(look_poll, "MM_LOOK_POLL", 0u, 0u, 1u, 0u),
-    MM_TD(fail_tick, "MM_DEBUG_FAIL_TICK", 0u, 0u, 0xFFFFFFFFu, 0u),
-    MM_TD(pair_persist, "MM_PAIR_PERSIST", 1u, 0u, 1u, 0u),
-    MM_TD(pair_ptiles, "MM_PAIR_PTILES", 32u, 1u, 32u, 0u),
-    MM_TD(pair_pbatch, "MM_PAIR_PBATCH", 48u, 1u, 4096u, 0u),
-    MM_TD(pair_batch, "MM_PAIR_BATCH", 48u, 1u, 4096u, 0u),
-    MM_TD(pair_ptimeout_us, "MM_PAIR_PTIMEOUT_US", 5000u, 0u, 1000000u, 0u),
-    MM_TD(pair_pinject, "MM_PAIR_PINJECT", 0u, 0u, 0xFFFFFFFFu, 0u),
-    MM_TD(pair_tiles_max, "MM_PAIR_TILES", PK_TILES_MAX, 1u, 4096u, 0u),
-    MM_TD(pair_tile_fixed, "MM_PAIR_TILE", 0u, 0u, 1u, 0u),
-    MM_TD(pair_xcd, "MM_PAIR_XCD", 1u, 0u, 1u, 0u),
-    MM_TD(pair_group_min, "MM_PAIR_GROUP", PK_GROUP_MIN, 0u, 0xFFFFFFFFu, 0u),
-    MM_TD(pair_nxseg, "MM_PAIR_NXSEG", 0u, 64u, NXI_SEG, 1u),
-    MM_TD(pair_nxstage, "MM_PAIR_NXSTAGE", 0u, 0u, 0xFFFFFFFFu, 0u),
-    MM_TD(pair_tune, "MM_PAIR_TUNE", 0u, 0u, 0xFFFFFFFFu, 0u),
-    MM_TD(team_batch, "MM_TEAM_BATCH", 16u, 1u, 4096u, 0u),
-    MM_TD(team_f2, "MM_TEAM_F2", 32u, 0u, 0xFFFFFFFFu, 0u),
-    MM_TD(team_rebuild, "MM_TEAM_REBUILD", 8u, 1u, 4096u, 0u),
-    MM_TD(team_emit_max, "MM_TEAM_EMIT_MAX", TC_EMIT_MAX, 1u, TC_EMIT_MAX, 0u),
-    MM_TD(team_split, "MM_TEAM_SPLIT", 1u, 0u, 1u, 0u),
-    MM_TD(team_fwait, "MM_TEAM_FWAIT", 1u << 14, 0u, 0xFFFFFFFFu, 0u),
-    MM_TD(team_fix_max, "MM_TEAM_FIXMAX", 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u),
-    MM_TD(team_fix_t8, "MM_TEAM_FIXT8", 10u, 0u, 0xFFFFFFFFu, 0u),
+    MM_TD(fail_tick, "MM_DEBUG_FAIL_TICK", 0u, 0u, 0xFFFFFFFFu, 0u),      // k: the k-th mm_tick of the engine fails after its walk (test hook)
+    MM_TD(pair_persist, "MM_PAIR_PERSIST", 1u, 0u, 1u, 0u),               // 0: never several passes per launch (kp_rounds); one launch per pass as before (A/B)
+    MM_TD(pair_ptiles, "MM_PAIR_PTILES", 32u, 1u, 32u, 0u),               // tiles of the longest chain a kp_rounds batch may have (one workgroup per CU of ONE XCD: 32)
+    // passes per kp_rounds launch at most (it ends earlier when the longest chain wants its compaction)
+    MM_TD(pair_pbatch, "MM_PAIR_PBATCH", 48u, 1u, 4096u, 0u),             // 48 / 64 / 96 measured: 95.7 / 94.6 / 93.5 M matched players/s (round 4)
+    // tiled rounds launched per host look at the chains
+    MM_TD(pair_batch, "MM_PAIR_BATCH", 48u, 1u, 4096u, 0u),               // 16 / 32 / 48 / 64 measured: 48 by 1-2 %
+    MM_TD(pair_ptimeout_us, "MM_PAIR_PTIMEOUT_US", 5000u, 0u, 1000000u, 0u),   // what a workgroup of kp_rounds waits at a barrier (pair_walk: PairParams.ptimeout0 / 1)
+    MM_TD(pair_pinject, "MM_PAIR_PINJECT", 0u, 0u, 0xFFFFFFFFu, 0u),      // PairParams.pinject (tests)
+    MM_TD(pair_tiles_max, "MM_PAIR_TILES", PK_TILES_MAX, 1u, 4096u, 0u),  // tiles of the longest chain a batch may have before the next larger tile length is taken
+    MM_TD(pair_tile_fixed, "MM_PAIR_TILE", 0u, 0u, 1u, 0u),               // 1 (=max): every batch with the largest tile length (A/B)
+    MM_TD(pair_xcd, "MM_PAIR_XCD", 1u, 0u, 1u, 0u),                       // 0: kp_round on the plain (tile, group) grid (A/B)
+    MM_TD(pair_group_min, "MM_PAIR_GROUP", PK_GROUP_MIN, 0u, 0xFFFFFFFFu, 0u),   // tiles of the longest chain from which a batch runs with the second level (0 = never)
+    MM_TD(pair_nxseg, "MM_PAIR_NXSEG", 0u, 64u, NXI_SEG, 1u),             // anchors per workgroup of kp_nx_init (0: from 256 up, by the pool)
+    MM_TD(pair_nxstage, "MM_PAIR_NXSTAGE", 0u, 0u, 0xFFFFFFFFu, 0u),      // entries it stages in LDS, anchors included (0: NXI_STAGE)
+    MM_TD(pair_tune, "MM_PAIR_TUNE", 0u, 0u, 0xFFFFFFFFu, 0u),            // PairParams.tune
+    MM_TD(team_batch, "MM_TEAM_BATCH", 16u, 1u, 4096u, 0u),               // passes launched per host look at the chains
+    // passes of a tick that compose F with itself (0 = never)
+    MM_TD(team_f2, "MM_TEAM_F2", 32u, 0u, 0xFFFFFFFFu, 0u),               // 24 / 40 measured within 0.1 ms of each other
+    // kt_build runs in the first two passes of a tick and every this many after
+    MM_TD(team_rebuild, "MM_TEAM_REBUILD", 8u, 1u, 4096u, 0u),            // 4 / 6 / 8 measured within 0.1 ms of each other, 16: +0.9 ms, every pass: +1.4 ms
+    MM_TD(team_emit_max, "MM_TEAM_EMIT_MAX", TC_EMIT_MAX, 1u, TC_EMIT_MAX, 0u),   // emitter workgroups per chain and launch at most (kt_pack resets vis[] for this many workers: TV_AHEAD)
+    MM_TD(team_split, "MM_TEAM_SPLIT", 1u, 0u, 1u, 0u),                   // the stored lobby's fill in kt_f's launch (the lobby-rich passes)
+    MM_TD(team_fwait, "MM_TEAM_FWAIT", 1u << 14, 0u, 0xFFFFFFFFu, 0u),    // ~5 ms of polls, then the chaser helps itself
+    MM_TD(team_fix_max, "MM_TEAM_FIXMAX", 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u),   // (measured: mending always wins once a task is a quarter wave's)
+    MM_TD(team_fix_t8, "MM_TEAM_FIXT8", 10u, 0u, 0xFFFFFFFFu, 0u),        // this and the three below: MM_TEAM_* knobs of kt_f / kt_fc
     MM_TD(team_fix_t4, "MM_TEAM_FIXT4", 64u, 0u, 0xFFFFFFFFu, 0u),
     MM_TD(team_pull_xcd, "MM_TEAM_PULLX", 1u, 0u, 1u, 0u),
     MM_TD(team_nowait, "MM_TEAM_NOWAIT", 0u, 0u, 0xFFFFFFFFu, 0u),
+    // team_late: lobbies per pass at or under which kt_late takes the chains over (0 = never).
+    // measured on cfg-3 (profiles/r03_ab_team_late.txt): 0: 12.99 ms, 3: 12.50, 6: 12.46, 12: 12.76, 20: 13.67, 40: 15.73 per tick,
+    // and again with one launch per pass (kt_fc): 0: 10.9, 6: 9.89, 12: 10.01, 20: 10.6 — a look-up costs the chaser ~4 us
+    // (dependent trips to memory at ~1.2 us each), so it only beats a pass kernel while a pass seats a handful of lobbies
     MM_TD(team_late, "MM_TEAM_LATE", 6u, 0u, 0xFFFFFFFFu, 0u),
-    MM_TD(team_late0, "MM_TEAM_LATE0", 512u, 0u, 0xFFFFFFFFu, 0u),
-    MM_TD(team_cap, "MM_TEAM_CAP", TT_SCAN_CAP, 1u, 4096u, 0u),
+    MM_TD(team_late0, "MM_TEAM_LATE0", 512u, 0u, 0xFFFFFFFFu, 0u),        // arrivals of a mode since its last tick at or under which kt_late walks the tick from its first pass
+    MM_TD(team_cap, "MM_TEAM_CAP", TT_SCAN_CAP, 1u, 4096u, 0u),           // TeamParams.scan_cap; <= 4096: kt_f notes members as 13-bit sub-queue offsets (TF_REL_BITS)
 };
 #undef MM_TD
 static const uint32_t k_tune_n = (uint32_t)(sizeof(k_tune) / sizeof(k_tune[0]));
@@ -1779,13 +1523,116 @@ extern "C" int mm_tuning_get(const mm_engine* e, mm_tuning* t)
 
 extern "C" int mm_engine_create(const mm_config* cfg, mm_engine** out) { return mm_engine_create_ex(cfg, NULL, out); }
 
+// Everything of a new engine that can fail: the stream, the events, the buffers (sizes from cfg), the first launches.
+// Whatever it had got when it fails, mm_engine_destroy gives back.
+static int engine_init(mm_engine* e)
+{
+    const mm_config* const cfg = &e->cfg;
+    const size_t cap = cfg->capacity;
+    ON_ENGINE_DEVICE(e);                           // the caller's device is put back when create returns
+    HIPCHK(e, hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    for (int i = 0; i < 4; ++i) HIPCHK(e, hipEventCreate(&e->ev[i]));
+    for (int i = 0; i < 2; ++i) HIPCHK(e, hipEventCreate(&e->ev_nx[i]));
+    for (uint32_t i = 0; i < cfg->n_groups; ++i) HIPCHK(e, hipEventCreate(&e->ev_grp[i]));
+    if (copy_stream_acquire(cfg->device, &e->copy_stream)) { e->copy_stream = nullptr; return MM_ERR_HIP; }
+    HIPCHK(e, hipEventCreate(&e->ev_copy));
+    MMTRY(dev_alloc(e, e->d_q_rating, e->n_chains * cap * sizeof(int32_t)));
+    MMTRY(dev_alloc(e, e->d_q_cons, e->n_chains * cap * sizeof(uint32_t)));
+    MMTRY(dev_alloc(e, e->d_q_slot, e->n_chains * cap * sizeof(uint32_t)));
+    MMTRY(dev_alloc(e, e->d_chains, e->n_chains * sizeof(ChainDev)));
+    MMTRY(dev_alloc(e, e->d_state, cap));
+    MMTRY(dev_alloc(e, e->d_released, (cap + 64) * sizeof(uint32_t)));
+    MMTRY(dev_alloc(e, e->d_pack, (size_t)MM_PACK_MAX * (MM_MAX_LOBBY + 2u) * sizeof(uint32_t)));
+    MMTRY(dev_alloc(e, e->d_counters, 2 * sizeof(uint32_t)));
+    // emission logs: a group can emit at most (cap + lobby) / 2 lobbies of >= 2 players
+    e->out_slot_stride = (uint32_t)(cap + 64);
+    e->out_rec_stride = (uint32_t)(cap / 2 + 16);
+    MMTRY(dev_alloc(e, e->d_out_slots, (size_t)cfg->n_groups * e->out_slot_stride * sizeof(uint32_t)));
+    MMTRY(dev_alloc(e, e->d_out_score, (size_t)cfg->n_groups * e->out_rec_stride * sizeof(float)));
+    MMTRY(dev_alloc(e, e->d_out_pass, (size_t)cfg->n_groups * e->out_rec_stride * sizeof(uint32_t)));
+    {
+        e->pk_stride = (uint32_t)((cap + 63) & ~(size_t)63);
+        const size_t gc = (size_t)cfg->n_groups * e->pk_stride;
+        e->pk_bits_stride = (uint32_t)(cap / 32 + 4);
+        MMTRY(dev_alloc(e, e->d_pchains, cfg->n_groups * sizeof(PairChain)));
+        e->pk_max_tiles = (uint32_t)(cap / (PK_TMAX / 4u) + 2);   // tiles of the smallest tile length
+        for (int b = 0; b < 2; ++b) {
+            MMTRY(dev_alloc(e, e->d_pk_key[b], (gc + 64) * sizeof(uint32_t)));
+            MMTRY(dev_alloc(e, e->d_pk_oidx[b], gc * sizeof(uint32_t)));
+            MMTRY(dev_alloc(e, e->d_pk_nx16[b], (gc + 64) * sizeof(uint16_t)));
+            MMTRY(dev_alloc(e, e->d_pk_bits[b], (size_t)cfg->n_groups * e->pk_bits_stride * sizeof(uint32_t)));
+        }
+        MMTRY(dev_alloc(e, e->d_pk_scratch, gc * sizeof(uint32_t)));
+        MMTRY(dev_alloc(e, e->d_pk_g16, (gc + 64) * sizeof(uint16_t)));
+        MMTRY(dev_alloc(e, e->d_pk_rec1, gc * sizeof(uint32_t)));
+        for (int b = 0; b < 2; ++b) {
+            MMTRY(dev_alloc(e, e->d_pk_exa[b], (gc + 64) * sizeof(uint16_t)));
+            MMTRY(dev_alloc(e, e->d_pk_bitsp[b], (size_t)cfg->n_groups * e->pk_bits_stride * sizeof(uint32_t)));
+            MMTRY(dev_alloc(e, e->d_pk_headp[b], (size_t)cfg->n_groups * e->pk_max_tiles * sizeof(uint32_t)));
+        }
+        MMTRY(dev_alloc(e, e->d_pk_wpre, (size_t)cfg->n_groups * e->pk_bits_stride * sizeof(uint16_t)));
+        MMTRY(dev_alloc(e, e->d_pk_tilectl, (size_t)TC_N * cfg->n_groups * e->pk_max_tiles * sizeof(uint32_t)));
+        MMTRY(dev_alloc(e, e->d_pk_pbar, (size_t)MM_MAX_GROUPS * 2u * sizeof(unsigned long long) + 64u));
+        // two tiles' worth of entries per group of PK_GS tiles, whatever the tile length of the batch
+        e->pk_gstride = (uint32_t)(2u * (e->pk_stride / PK_GS) + 4u * PK_TMAX);
+        MMTRY(dev_alloc(e, e->d_pk_grec, (size_t)cfg->n_groups * e->pk_gstride * sizeof(uint4)));
+        // an entry carries the round it was made in (the walk takes one of its own round only): no stamp to start with
+        HIPCHK(e, hipMemsetAsync(e->d_pk_grec, 0xFF, (size_t)cfg->n_groups * e->pk_gstride * sizeof(uint4), e->stream));
+        MMTRY(pin_alloc(e, e->h_pchains, cfg->n_groups * sizeof(PairChain)));
+        // a tick emits at most (cap + lobby) / 2 lobbies per group, cap + lobbies-in-progress players overall
+        // (+ one lobby of slack per group: a group's region is sized by the players it holds when the tick begins)
+        MMTRY(pin_alloc(e, e->h_rslots, (cap + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(uint32_t)));
+        MMTRY(pin_alloc(e, e->h_rscore, (cap / 2 + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(float)));
+        MMTRY(pin_alloc(e, e->h_rpass, (cap / 2 + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(uint32_t)));
+        HIPCHK(e, hipMemsetAsync(e->d_pchains, 0, cfg->n_groups * sizeof(PairChain), e->stream));
+        e->tk_chunk_stride = (uint32_t)(e->pk_stride / TT_CH + 2);
+        MMTRY(dev_alloc(e, e->d_tchains, cfg->n_groups * sizeof(TeamChain)));
+        MMTRY(dev_alloc(e, e->d_tk_chunk, (size_t)cfg->n_groups * MM_MAX_ROLES * e->tk_chunk_stride * sizeof(uint32_t)));
+        MMTRY(dev_alloc(e, e->d_tk_fv2, gc * sizeof(uint32_t)));
+        e->tk_memb = 0;
+        for (uint32_t k = 0; k < cfg->n_modes; ++k) {
+            const uint32_t L = cfg->modes[k].teams * cfg->modes[k].team_size;
+            if (L > 2u && L - 1u > e->tk_memb) e->tk_memb = L - 1u;
+        }
+        if (e->tk_memb) {
+            MMTRY(dev_alloc(e, e->d_tk_fpos, gc * sizeof(uint32_t)));
+            MMTRY(dev_alloc(e, e->d_tk_memb, gc * e->tk_memb * sizeof(uint16_t)));
+            MMTRY(dev_alloc(e, e->d_tk_bitsB, (size_t)cfg->n_groups * e->pk_bits_stride * sizeof(uint32_t)));
+            MMTRY(dev_alloc(e, e->d_tk_chunkB, (size_t)cfg->n_groups * MM_MAX_ROLES * e->tk_chunk_stride * sizeof(uint32_t)));
+            MMTRY(dev_alloc(e, e->d_tk_sqi, gc * sizeof(uint32_t)));
+            MMTRY(dev_alloc(e, e->d_tk_fdone, (size_t)cfg->n_groups * e->tk_chunk_stride * sizeof(uint32_t)));
+            HIPCHK(e, hipMemsetAsync(e->d_tk_fdone, 0, (size_t)cfg->n_groups * e->tk_chunk_stride * sizeof(uint32_t), e->stream));
+        }
+        MMTRY(pin_alloc(e, e->h_tchains, cfg->n_groups * sizeof(TeamChain)));
+        HIPCHK(e, hipMemsetAsync(e->d_tchains, 0, cfg->n_groups * sizeof(TeamChain), e->stream));
+    }
+    MMTRY(pin_alloc(e, e->h_chains, e->n_chains * sizeof(ChainDev)));
+    MMTRY(pin_alloc(e, e->h_look_seq, 64));
+    *e->h_look_seq = 0;
+    MMTRY(pin_alloc(e, e->h_counters, 2 * sizeof(uint32_t)));
+    e->h_state.assign(cap, MM_ST_FREE);
+    e->tk_last_len.assign(e->n_chains, 0u);
+    if (e->tk_memb) {
+        // the first launch of a kernel is slow (8 ms for kt_late in a stream's first late tick): take it here, on
+        // chain records that say "not walked" (the workgroups return at once)
+        TeamParams W;
+        memset(&W, 0, sizeof(W));
+        W.n_groups = cfg->n_groups;
+        W.tchains = e->d_tchains;
+        W.chains = e->d_chains;
+        hipLaunchKernelGGL(kt_late, dim3(cfg->n_groups), dim3(TL_THREADS), 0, e->stream, W);
+        hipLaunchKernelGGL(kt_fc, dim3(cfg->n_groups), dim3(TT_CH), 0, e->stream, W);
+        HIPCHK(e, hipGetLastError());
+    }
+    return engine_reset_device(e);
+}
+
 extern "C" int mm_engine_create_ex(const mm_config* cfg, const mm_tuning* tuning, mm_engine** out)
 {
-    try {
+    return guarded([&]() -> int {
         if (!cfg || !out) return MM_ERR_INVALID_ARG;
         *out = NULL;
-        int rc = cfg_validate(cfg);
-        if (rc) return rc;
+        MMTRY(cfg_validate(cfg));
         mm_tuning tn;
         tune_defaults(&tn);
         if (tuning) {
@@ -1802,210 +1649,23 @@ extern "C" int mm_engine_create_ex(const mm_config* cfg, const mm_tuning* tuning
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev)
             return MM_ERR_NO_DEVICE;
         roctx_init();
-        mm_engine* e = new (std::nothrow) mm_engine();
+        mm_engine* e = new (std::nothrow) mm_engine();   // every field zero: no buffer, no clock, nothing poisoned
         if (!e) return MM_ERR_OOM;
         e->cfg = *cfg;
         e->tn = tn;
         e->n_chains = cfg->n_modes * cfg->n_groups;
-        e->last_hip = 0;
-        e->next_slot = 0;
-        e->cancel_pending = 0;
-        e->r_n = 0;
         e->r_L = 2;
-        e->in_cap = 0;
-        e->wave_hist_rows = 0;
-        e->live_upper = 0;
-        e->poisoned = false;
-        e->ticks_seen = 0;
-        e->clock_on = false;
-        e->clock_now = 0;
-        e->mw_n = 0;
-        {
-            // the tuning record (include/mm_engine.h, mm_tuning): validated by the caller below; the engine keeps it (mm_tuning_get)
-            // and its working copies — some of which change while it runs (pair_persist after a PF_XCD stop)
-            const mm_tuning& t = e->tn;
-            e->fault_tick = t.fail_tick;
-            e->force_generic = t.force_generic != 0u;
-            e->pair_debug = t.debug != 0u;
-            e->pair_tune = t.pair_tune;
-            e->pair_tile_fixed = t.pair_tile_fixed != 0u;
-            e->pair_tiles_max = t.pair_tiles_max;
-            e->pair_xcd = t.pair_xcd != 0u;
-            e->pair_group_min = t.pair_group_min;
-            e->round_ctr = 0;
-            e->pair_persist = t.pair_persist != 0u;
-            e->pair_ptiles = t.pair_ptiles;
-            e->pair_pinject = t.pair_pinject;
-            // the first barrier of a launch is where a workgroup that found no CU is waited for (another engine's launch in the
-            // way ends within a millisecond or two); behind it everybody is on the chip and only slow, never absent
-            // — 5 ms, half a tick period of the stream (20 ms until round 5: two whole periods of spinning whenever somebody
-            // else held the CUs, and kp_round is a cheap way on); 40 x that behind it (200 ms), as before.  In 100 MHz ticks.
-            e->pair_ptimeout[0] = t.pair_ptimeout_us * 100u;
-            e->pair_ptimeout[1] = e->pair_ptimeout[0] * 40u;
-            e->pair_pcool = 0;
-            e->pair_pstops = 0;
-            e->pair_nxseg = t.pair_nxseg;
-            e->pair_nxstage = t.pair_nxstage;
-            e->pair_pbatch = t.pair_pbatch;       // 48 / 64 / 96 measured: 95.7 / 94.6 / 93.5 M matched players/s (round 4)
-            e->pair_batch = t.pair_batch;         // 16 / 32 / 48 / 64 measured: 48 by 1-2 %
-            e->team_batch = t.team_batch;
-            e->team_f2 = t.team_f2;               // 24 / 40 measured within 0.1 ms of each other
-            e->team_rebuild = t.team_rebuild;     // 4 / 6 / 8 measured within 0.1 ms of each other, 16: +0.9 ms, every pass: +1.4 ms
-            e->team_emit_max = t.team_emit_max;   // emitter workgroups per chain and launch at most (kt_pack resets vis[] for this many workers: TV_AHEAD)
-            e->team_split = t.team_split;
-            e->team_fwait = t.team_fwait;         // ~5 ms of polls, then the chaser helps itself
-            e->team_fix_max = t.team_fix_max;     // (measured: mending always wins once a task is a quarter wave's)
-            e->team_fix_t8 = t.team_fix_t8;
-            e->team_fix_t4 = t.team_fix_t4;
-            e->team_pull_xcd = t.team_pull_xcd;
-            e->team_nowait = t.team_nowait;
-            memset(&e->ps, 0, sizeof(e->ps));
-            e->ps.mode = 0xFFFFFFFFu;
-            e->team_seq = 0;
-            e->team_late0 = t.team_late0;
-            e->tk_last_len.assign(e->n_chains, 0u);
-            e->results_early = t.results_early != 0u;
-            // measured on cfg-3 (profiles/r03_ab_team_late.txt): 0: 12.99 ms, 3: 12.50, 6: 12.46, 12: 12.76, 20: 13.67, 40: 15.73 per tick,
-            // and again with one launch per pass (kt_fc): 0: 10.9, 6: 9.89, 12: 10.01, 20: 10.6 — a look-up costs the chaser ~4 us
-            // (dependent trips to memory at ~1.2 us each), so it only beats a pass kernel while a pass seats a handful of lobbies
-            e->team_late = t.team_late;
-            e->team_cap = t.team_cap;             // <= 4096: kt_f notes members as 13-bit sub-queue offsets (TF_REL_BITS)
-            // look_poll OFF by default.  Measured (profiles/r05_ab_look_poll.txt, cfg-2 / cfg-3, 40 steps, twice each on one box): the
-            // median step gains 0.03 ms of 10.1 (1v1) and 0.05 ms of 8.5 (5v5) — the copy + synchronisation of a look is NOT where a
-            // tick's time goes — and every polled 1v1 run had ONE step of 17 ms: a host thread that spins for the whole tick is what a
-            // container's CPU quota throttles first (a dirty scheduler of the BEAM would fare no better).
-            e->look_poll = t.look_poll != 0u;
-            e->results_tail_kernel = t.results_tail != 0u;
-        }
-        const size_t cap = cfg->capacity;
-    #define CREATE_CHK(call)                                                 \
-        do {                                                                 \
-            hipError_t _rc = (call);                                         \
-            if (_rc != hipSuccess) {                                         \
-                int code = _rc == hipErrorOutOfMemory ? MM_ERR_OOM : MM_ERR_HIP; \
-                mm_engine_destroy(e);                                        \
-                return code;                                                 \
-            }                                                                \
-        } while (0)
-        DeviceScope dev_scope(cfg->device);        // the caller's device is put back when create returns
-        if (!dev_scope.ok) {
-            mm_engine_destroy(e);
-            return MM_ERR_HIP;
-        }
-        CREATE_CHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-        for (int i = 0; i < 4; ++i) CREATE_CHK(hipEventCreate(&e->ev[i]));
-        for (int i = 0; i < 2; ++i) CREATE_CHK(hipEventCreate(&e->ev_nx[i]));
-        e->ev_nx_set = false;
-        for (uint32_t i = 0; i < cfg->n_groups; ++i) CREATE_CHK(hipEventCreate(&e->ev_grp[i]));
-        if (copy_stream_acquire(cfg->device, &e->copy_stream)) { e->copy_stream = nullptr; mm_engine_destroy(e); return MM_ERR_HIP; }
-        CREATE_CHK(hipEventCreate(&e->ev_copy));
-        e->ev_copy_pending = false;
-        e->r_based = false;
-        memset(e->r_cnt, 0, sizeof(e->r_cnt));
-        memset(e->r_pre, 0, sizeof(e->r_pre));
-        CREATE_CHK(hipMalloc((void**)&e->d_q_rating, e->n_chains * cap * sizeof(int32_t)));
-        CREATE_CHK(hipMalloc((void**)&e->d_q_cons, e->n_chains * cap * sizeof(uint32_t)));
-        CREATE_CHK(hipMalloc((void**)&e->d_q_slot, e->n_chains * cap * sizeof(uint32_t)));
-        CREATE_CHK(hipMalloc((void**)&e->d_chains, e->n_chains * sizeof(ChainDev)));
-        CREATE_CHK(hipMalloc((void**)&e->d_state, cap));
-        CREATE_CHK(hipMalloc((void**)&e->d_released, (cap + 64) * sizeof(uint32_t)));
-        CREATE_CHK(hipMalloc((void**)&e->d_pack, (size_t)MM_PACK_MAX * (MM_MAX_LOBBY + 2u) * sizeof(uint32_t)));
-        CREATE_CHK(hipMalloc((void**)&e->d_counters, 2 * sizeof(uint32_t)));
-        // emission logs: a group can emit at most (cap + lobby) / 2 lobbies of >= 2 players
-        e->out_slot_stride = (uint32_t)(cap + 64);
-        e->out_rec_stride = (uint32_t)(cap / 2 + 16);
-        CREATE_CHK(hipMalloc((void**)&e->d_out_slots, (size_t)cfg->n_groups * e->out_slot_stride * sizeof(uint32_t)));
-        CREATE_CHK(hipMalloc((void**)&e->d_out_score, (size_t)cfg->n_groups * e->out_rec_stride * sizeof(float)));
-        CREATE_CHK(hipMalloc((void**)&e->d_out_pass, (size_t)cfg->n_groups * e->out_rec_stride * sizeof(uint32_t)));
-        {
-            e->pk_stride = (uint32_t)((cap + 63) & ~(size_t)63);
-            const size_t gc = (size_t)cfg->n_groups * e->pk_stride;
-            e->pk_bits_stride = (uint32_t)(cap / 32 + 4);
-            CREATE_CHK(hipMalloc((void**)&e->d_pchains, cfg->n_groups * sizeof(PairChain)));
-            e->pk_max_tiles = (uint32_t)(cap / (PK_TMAX / 4u) + 2);   // tiles of the smallest tile length
-            for (int b = 0; b < 2; ++b) {
-                CREATE_CHK(hipMalloc((void**)&e->d_pk_key[b], (gc + 64) * sizeof(uint32_t)));
-                CREATE_CHK(hipMalloc((void**)&e->d_pk_oidx[b], gc * sizeof(uint32_t)));
-                CREATE_CHK(hipMalloc((void**)&e->d_pk_nx16[b], (gc + 64) * sizeof(uint16_t)));
-                CREATE_CHK(hipMalloc((void**)&e->d_pk_bits[b], (size_t)cfg->n_groups * e->pk_bits_stride * sizeof(uint32_t)));
-            }
-            CREATE_CHK(hipMalloc((void**)&e->d_pk_scratch, gc * sizeof(uint32_t)));
-            CREATE_CHK(hipMalloc((void**)&e->d_pk_g16, (gc + 64) * sizeof(uint16_t)));
-            CREATE_CHK(hipMalloc((void**)&e->d_pk_rec1, gc * sizeof(uint32_t)));
-            for (int b = 0; b < 2; ++b) {
-                CREATE_CHK(hipMalloc((void**)&e->d_pk_exa[b], (gc + 64) * sizeof(uint16_t)));
-                CREATE_CHK(hipMalloc((void**)&e->d_pk_bitsp[b], (size_t)cfg->n_groups * e->pk_bits_stride * sizeof(uint32_t)));
-                CREATE_CHK(hipMalloc((void**)&e->d_pk_headp[b], (size_t)cfg->n_groups * e->pk_max_tiles * sizeof(uint32_t)));
-            }
-            CREATE_CHK(hipMalloc((void**)&e->d_pk_wpre, (size_t)cfg->n_groups * e->pk_bits_stride * sizeof(uint16_t)));
-            CREATE_CHK(hipMalloc((void**)&e->d_pk_tilectl, (size_t)TC_N * cfg->n_groups * e->pk_max_tiles * sizeof(uint32_t)));
-            CREATE_CHK(hipMalloc((void**)&e->d_pk_pbar, (size_t)MM_MAX_GROUPS * 2u * sizeof(unsigned long long) + 64u));
-            // two tiles' worth of entries per group of PK_GS tiles, whatever the tile length of the batch
-            e->pk_gstride = (uint32_t)(2u * (e->pk_stride / PK_GS) + 4u * PK_TMAX);
-            CREATE_CHK(hipMalloc((void**)&e->d_pk_grec, (size_t)cfg->n_groups * e->pk_gstride * sizeof(uint4)));
-            // an entry carries the round it was made in (the walk takes one of its own round only): no stamp to start with
-            CREATE_CHK(hipMemsetAsync(e->d_pk_grec, 0xFF, (size_t)cfg->n_groups * e->pk_gstride * sizeof(uint4), e->stream));
-            CREATE_CHK(hipHostMalloc((void**)&e->h_pchains, cfg->n_groups * sizeof(PairChain), hipHostMallocDefault));
-            // a tick emits at most (cap + lobby) / 2 lobbies per group, cap + lobbies-in-progress players overall
-            // (+ one lobby of slack per group: a group's region is sized by the players it holds when the tick begins)
-            CREATE_CHK(hipHostMalloc((void**)&e->h_rslots, (cap + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(uint32_t), hipHostMallocDefault));
-            CREATE_CHK(hipHostMalloc((void**)&e->h_rscore, (cap / 2 + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(float), hipHostMallocDefault));
-            CREATE_CHK(hipHostMalloc((void**)&e->h_rpass, (cap / 2 + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(uint32_t), hipHostMallocDefault));
-            CREATE_CHK(hipMemsetAsync(e->d_pchains, 0, cfg->n_groups * sizeof(PairChain), e->stream));
-            e->tk_chunk_stride = (uint32_t)(e->pk_stride / TT_CH + 2);
-            CREATE_CHK(hipMalloc((void**)&e->d_tchains, cfg->n_groups * sizeof(TeamChain)));
-            CREATE_CHK(hipMalloc((void**)&e->d_tk_chunk, (size_t)cfg->n_groups * MM_MAX_ROLES * e->tk_chunk_stride * sizeof(uint32_t)));
-            CREATE_CHK(hipMalloc((void**)&e->d_tk_fv2, gc * sizeof(uint32_t)));
-            e->tk_memb = 0;
-            for (uint32_t k = 0; k < cfg->n_modes; ++k) {
-                const uint32_t L = cfg->modes[k].teams * cfg->modes[k].team_size;
-                if (L > 2u && L - 1u > e->tk_memb) e->tk_memb = L - 1u;
-            }
-            if (e->tk_memb) {
-                CREATE_CHK(hipMalloc((void**)&e->d_tk_fpos, gc * sizeof(uint32_t)));
-                CREATE_CHK(hipMalloc((void**)&e->d_tk_memb, gc * e->tk_memb * sizeof(uint16_t)));
-                CREATE_CHK(hipMalloc((void**)&e->d_tk_bitsB, (size_t)cfg->n_groups * e->pk_bits_stride * sizeof(uint32_t)));
-                CREATE_CHK(hipMalloc((void**)&e->d_tk_chunkB, (size_t)cfg->n_groups * MM_MAX_ROLES * e->tk_chunk_stride * sizeof(uint32_t)));
-                CREATE_CHK(hipMalloc((void**)&e->d_tk_sqi, gc * sizeof(uint32_t)));
-                CREATE_CHK(hipMalloc((void**)&e->d_tk_fdone, (size_t)cfg->n_groups * e->tk_chunk_stride * sizeof(uint32_t)));
-                CREATE_CHK(hipMemsetAsync(e->d_tk_fdone, 0, (size_t)cfg->n_groups * e->tk_chunk_stride * sizeof(uint32_t), e->stream));
-            }
-            CREATE_CHK(hipHostMalloc((void**)&e->h_tchains, cfg->n_groups * sizeof(TeamChain), hipHostMallocDefault));
-            CREATE_CHK(hipMemsetAsync(e->d_tchains, 0, cfg->n_groups * sizeof(TeamChain), e->stream));
-        }
-        CREATE_CHK(hipHostMalloc((void**)&e->h_chains, e->n_chains * sizeof(ChainDev), hipHostMallocDefault));
-        CREATE_CHK(hipHostMalloc((void**)&e->h_look_seq, 64, hipHostMallocDefault));
-        *e->h_look_seq = 0;
-        e->look_seq = 0;
-        CREATE_CHK(hipHostMalloc((void**)&e->h_counters, 2 * sizeof(uint32_t), hipHostMallocDefault));
-        e->h_state.assign(cap, MM_ST_FREE);
-        if (e->tk_memb) {
-            // the first launch of a kernel is slow (8 ms for kt_late in a stream's first late tick): take it here, on
-            // chain records that say "not walked" (the workgroups return at once)
-            TeamParams W;
-            memset(&W, 0, sizeof(W));
-            W.n_groups = cfg->n_groups;
-            W.tchains = e->d_tchains;
-            W.chains = e->d_chains;
-            hipLaunchKernelGGL(kt_late, dim3(cfg->n_groups), dim3(TL_THREADS), 0, e->stream, W);
-            hipLaunchKernelGGL(kt_fc, dim3(cfg->n_groups), dim3(TT_CH), 0, e->stream, W);
-            CREATE_CHK(hipGetLastError());
-        }
-    #undef CREATE_CHK
-        rc = engine_reset_device(e);
+        e->ps.mode = 0xFFFFFFFFu;
+        const int rc = guarded([&]() -> int { return engine_init(e); });
         if (rc) { mm_engine_destroy(e); return rc; }
         *out = e;
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int mm_reset(mm_engine* e)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e) return MM_ERR_INVALID_ARG;
         ON_ENGINE_DEVICE(e);
         std::fill(e->h_state.begin(), e->h_state.end(), (uint8_t)MM_ST_FREE);
@@ -2019,11 +1679,7 @@ extern "C" int mm_reset(mm_engine* e)
         const int rc = engine_reset_device(e);
         if (rc == MM_OK) e->poisoned = false;
         return rc;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 static int ensure_staging(mm_engine* e, size_t n)
@@ -2031,17 +1687,17 @@ static int ensure_staging(mm_engine* e, size_t n)
     if (n <= e->in_cap) return MM_OK;
     size_t cap = e->in_cap ? e->in_cap : 4096;
     while (cap < n) cap *= 2;
-    (void)hipFree(e->d_in_rating); e->d_in_rating = NULL;
-    (void)hipFree(e->d_in_cons); e->d_in_cons = NULL;
-    (void)hipFree(e->d_in_group); e->d_in_group = NULL;
-    (void)hipFree(e->d_in_slot); e->d_in_slot = NULL;
-    (void)hipFree(e->d_in_sel); e->d_in_sel = NULL;
+    mem_release(e, e->d_in_rating);
+    mem_release(e, e->d_in_cons);
+    mem_release(e, e->d_in_group);
+    mem_release(e, e->d_in_slot);
+    mem_release(e, e->d_in_sel);
     e->in_cap = 0;
-    HIPCHK(e, hipMalloc((void**)&e->d_in_rating, cap * sizeof(int32_t)));
-    HIPCHK(e, hipMalloc((void**)&e->d_in_cons, cap * sizeof(uint32_t)));
-    HIPCHK(e, hipMalloc((void**)&e->d_in_group, cap));
-    HIPCHK(e, hipMalloc((void**)&e->d_in_slot, cap * sizeof(uint32_t)));
-    HIPCHK(e, hipMalloc((void**)&e->d_in_sel, cap * sizeof(uint32_t)));
+    MMTRY(dev_alloc(e, e->d_in_rating, cap * sizeof(int32_t)));
+    MMTRY(dev_alloc(e, e->d_in_cons, cap * sizeof(uint32_t)));
+    MMTRY(dev_alloc(e, e->d_in_group, cap));
+    MMTRY(dev_alloc(e, e->d_in_slot, cap * sizeof(uint32_t)));
+    MMTRY(dev_alloc(e, e->d_in_sel, cap * sizeof(uint32_t)));
     e->in_cap = cap;
     return MM_OK;
 }
@@ -2054,10 +1710,9 @@ static int enqueue_device_impl(mm_engine* e, uint32_t n, const int32_t* d_rating
     const uint32_t blocks = (n + BK_CHUNK - 1) / BK_CHUNK;
     const size_t rows = (size_t)blocks * BK_WAVES;
     if (rows > e->wave_hist_rows) {
-        (void)hipFree(e->d_wave_hist);
-        e->d_wave_hist = NULL;
+        mem_release(e, e->d_wave_hist);
         e->wave_hist_rows = 0;
-        HIPCHK(e, hipMalloc((void**)&e->d_wave_hist, rows * e->n_chains * sizeof(uint32_t)));
+        MMTRY(dev_alloc(e, e->d_wave_hist, rows * e->n_chains * sizeof(uint32_t)));
         e->wave_hist_rows = rows;
     }
     const BucketCfg B = make_bucket_cfg(e->cfg);
@@ -2122,7 +1777,7 @@ static int pick_free_slots(const mm_engine* e, uint32_t n, std::vector<uint32_t>
 extern "C" int mm_enqueue(mm_engine* e, uint32_t n, const int32_t* rating, const uint32_t* cons,
                           const uint8_t* group, uint32_t* out_slot, mm_enqueue_stats* st)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e || (n && (!rating || !cons))) return MM_ERR_INVALID_ARG;
         if (e->poisoned) return MM_ERR_STATE;
         ON_ENGINE_DEVICE(e);
@@ -2136,8 +1791,7 @@ extern "C" int mm_enqueue(mm_engine* e, uint32_t n, const int32_t* rating, const
         if (group)
             for (uint32_t i = 0; i < n; ++i)
                 if (group[i] >= e->cfg.n_groups) return MM_ERR_INVALID_ARG;
-        int rc = ensure_staging(e, n);
-        if (rc) return rc;
+        MMTRY(ensure_staging(e, n));
         if (!contiguous)
             HIPCHK(e, hipMemcpyAsync(e->d_in_sel, sel.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
         HIPCHK(e, hipMemcpyAsync(e->d_in_rating, rating, n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
@@ -2148,9 +1802,8 @@ extern "C" int mm_enqueue(mm_engine* e, uint32_t n, const int32_t* rating, const
         std::vector<uint32_t> tmp;
         uint32_t* slots = out_slot;
         if (!slots) { tmp.resize(n); slots = tmp.data(); }
-        rc = enqueue_device_impl(e, n, e->d_in_rating, e->d_in_cons, group ? e->d_in_group : NULL,
-                                 contiguous ? NULL : e->d_in_sel, e->d_in_slot, &rejected, &bms, slots);   // syncs: `sel` outlives the copy
-        if (rc) return rc;
+        MMTRY(enqueue_device_impl(e, n, e->d_in_rating, e->d_in_cons, group ? e->d_in_group : NULL,
+                                  contiguous ? NULL : e->d_in_sel, e->d_in_slot, &rejected, &bms, slots));   // syncs: `sel` outlives the copy
         for (uint32_t i = 0; i < n; ++i)
             if (slots[i] != MM_NO_SLOT) e->h_state[slots[i]] = MM_ST_LIVE;
         e->next_slot = contiguous ? (uint32_t)(((unsigned long long)e->next_slot + n) % e->cfg.capacity)
@@ -2163,17 +1816,13 @@ extern "C" int mm_enqueue(mm_engine* e, uint32_t n, const int32_t* rating, const
             st->total_ms = (float)(host_now_ms() - t0);
         }
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int mm_enqueue_device(mm_engine* e, uint32_t n, const int32_t* d_rating, const uint32_t* d_cons,
                                  uint32_t* first_slot, mm_enqueue_stats* st)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e || (n && (!d_rating || !d_cons))) return MM_ERR_INVALID_ARG;
         if (e->poisoned) return MM_ERR_STATE;
         ON_ENGINE_DEVICE(e);
@@ -2184,10 +1833,8 @@ extern "C" int mm_enqueue_device(mm_engine* e, uint32_t n, const int32_t* d_rati
         if (!ring_range_free(e, n)) return MM_ERR_FULL;
         uint32_t rejected = 0;
         float bms = 0.f;
-        int rc = ensure_staging(e, n);                       // the slot column (d_in_slot) of the batch
-        if (rc) return rc;
-        rc = enqueue_device_impl(e, n, d_rating, d_cons, NULL, NULL, e->d_in_slot, &rejected, &bms);
-        if (rc) return rc;
+        MMTRY(ensure_staging(e, n));                       // the slot column (d_in_slot) of the batch
+        MMTRY(enqueue_device_impl(e, n, d_rating, d_cons, NULL, NULL, e->d_in_slot, &rejected, &bms));
         const uint32_t cap = e->cfg.capacity;
         const uint32_t a = e->next_slot, n1 = n < cap - a ? n : cap - a;
         if (rejected == 0u) {
@@ -2211,16 +1858,12 @@ extern "C" int mm_enqueue_device(mm_engine* e, uint32_t n, const int32_t* d_rati
             st->total_ms = (float)(host_now_ms() - t0);
         }
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int mm_cancel(mm_engine* e, uint32_t n, const uint32_t* slot)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e || (n && !slot)) return MM_ERR_INVALID_ARG;
         if (e->poisoned) return MM_ERR_STATE;
         ON_ENGINE_DEVICE(e);
@@ -2234,8 +1877,7 @@ extern "C" int mm_cancel(mm_engine* e, uint32_t n, const uint32_t* slot)
             }
         }
         if (live.empty()) return MM_OK;
-        int rc = ensure_staging(e, live.size());
-        if (rc) return rc;
+        MMTRY(ensure_staging(e, live.size()));
         const uint32_t k = (uint32_t)live.size();
         HIPCHK(e, hipMemcpyAsync(e->d_in_slot, live.data(), k * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
         hipLaunchKernelGGL(k_cancel, dim3((k + 255) / 256), dim3(256), 0, e->stream, k, e->d_in_slot, e->d_state);
@@ -2243,11 +1885,7 @@ extern "C" int mm_cancel(mm_engine* e, uint32_t n, const uint32_t* slot)
         HIPCHK(e, hipStreamSynchronize(e->stream));   // `live` must outlive the copy
         e->cancel_pending += k;
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 // ---- the match list on its way to the host while the walk runs --------------------------------------------------
@@ -2298,11 +1936,10 @@ static int results_send(mm_engine* e, const uint32_t* n_out, uint32_t L, uint32_
     for (uint32_t g = 0; g < e->cfg.n_groups; ++g) fresh += n_out[g] > e->r_sent[g] ? n_out[g] - e->r_sent[g] : 0u;
     if (on_main) *on_main = false;
     if (fresh < min_new) return MM_OK;
-    int rc = results_absorb(e, L);                       // one batch of copies in flight at a time
-    if (rc) return rc;
+    MMTRY(results_absorb(e, L));                       // one batch of copies in flight at a time
     // the end of a tick with little left to send (every tick of a stream): on the engine's own stream, behind the
     // walk — the caller synchronises that stream anyway, and a second stream's event would be one more round trip
-    if (on_main != nullptr && fresh <= MM_TAIL_MAX && e->results_tail_kernel) {
+    if (on_main != nullptr && fresh <= MM_TAIL_MAX && e->tn.results_tail) {
         TailArgs A;
         memset(&A, 0, sizeof(A));
         A.n_groups = e->cfg.n_groups; A.L = L; A.out_slot_stride = e->out_slot_stride; A.out_rec_stride = e->out_rec_stride;
@@ -2345,7 +1982,7 @@ static int results_send(mm_engine* e, const uint32_t* n_out, uint32_t L, uint32_
 // itself: a stream that has finished (or failed) without the sequence number having arrived ends it.
 static int look_launch(mm_engine* e, const void* d_src, void* h_dst, size_t bytes)
 {
-    if (!e->look_poll) {
+    if (!e->tn.look_poll) {
         HIPCHK(e, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, e->stream));
         return MM_OK;
     }
@@ -2357,7 +1994,7 @@ static int look_launch(mm_engine* e, const void* d_src, void* h_dst, size_t byte
 }
 static int look_wait(mm_engine* e)
 {
-    if (!e->look_poll) {
+    if (!e->tn.look_poll) {
         HIPCHK(e, hipStreamSynchronize(e->stream));
         return MM_OK;
     }
@@ -2378,6 +2015,9 @@ static int look_wait(mm_engine* e)
         __builtin_ia32_pause();
     }
 }
+
+// Several passes per launch (kp_rounds)?  The knob, until a PF_XCD stop switches it off for the rest of the engine's life.
+static bool kp_rounds_on(const mm_engine* e) { return e->tn.pair_persist != 0u && !e->kp_rounds_off; }
 
 // kp_round's workgroup map of a batch (PairParams.xseg): the tiles of a chain on as few XCDs as its tile count allows.
 // Up to eight chains: an XCD each, the XCDs that are left go one by one to the chain with the most tiles per XCD;
@@ -2434,6 +2074,30 @@ static uint32_t pair_xcd_map(PairParams& P, const uint32_t* tiles_of, uint32_t G
     return slots;
 }
 
+// What PairParams, TeamParams and WalkParams hold under the same names: the ticked mode, the queues, the ActiveUser mirror
+// and the emission logs.  Everything else of the record is zero.
+template <class Params>
+static void walk_params_common(Params& P, const mm_engine* e, uint32_t mode, bool purge)
+{
+    memset(&P, 0, sizeof(P));
+    P.mode = mode;
+    P.n_groups = e->cfg.n_groups;
+    P.capacity = e->cfg.capacity;
+    P.purge = purge ? 1u : 0u;
+    P.out_slot_stride = e->out_slot_stride;
+    P.out_rec_stride = e->out_rec_stride;
+    P.chains = e->d_chains;
+    P.q_rating = e->d_q_rating;
+    P.q_cons = e->d_q_cons;
+    P.q_slot = e->d_q_slot;
+    P.state = e->d_state;
+    P.released = e->d_released;
+    P.n_released = e->d_counters;
+    P.out_slots = e->d_out_slots;
+    P.out_score = e->d_out_score;
+    P.out_pass = e->d_out_pass;
+}
+
 // The pair path (mm_pair.inc) for every chain of `mode` it is eligible for; the others are
 // left to k_walk (PairChain.fast == 0).  All launches are asynchronous on the engine stream.
 static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
@@ -2441,26 +2105,21 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
     const mm_config& cfg = e->cfg;
     const uint32_t G = cfg.n_groups;
     PairParams P;
-    memset(&P, 0, sizeof(P));
-    P.mode = mode;
-    P.n_groups = G;
-    P.capacity = cfg.capacity;
+    walk_params_common(P, e, mode, purge);
+    // the knobs (mm_tuning -> PairParams)
+    P.tune = e->tn.pair_tune;
+    P.pinject = e->tn.pair_pinject;
+    // the first barrier of a launch is where a workgroup that found no CU is waited for (another engine's launch in the
+    // way ends within a millisecond or two); behind it everybody is on the chip and only slow, never absent
+    // — 5 ms, half a tick period of the stream (20 ms until round 5: two whole periods of spinning whenever somebody
+    // else held the CUs, and kp_round is a cheap way on); 40 x that behind it (200 ms), as before.  In 100 MHz ticks.
+    P.ptimeout0 = e->tn.pair_ptimeout_us * 100u;
+    P.ptimeout1 = P.ptimeout0 * 40u;
     P.window = M.window > 0xFFFFFu ? 0xFFFFFu : M.window;   // rating span of a fast chain < 2^20
     P.eqmask = M.eqmask;
-    P.out_slot_stride = e->out_slot_stride;
-    P.out_rec_stride = e->out_rec_stride;
     P.bits_stride = e->pk_bits_stride;
     P.pstride = e->pk_stride;
-    P.tune = e->pair_tune;
-    P.purge = purge ? 1u : 0u;
-    P.state = e->d_state;
-    P.released = e->d_released;
-    P.n_released = e->d_counters;
-    P.chains = e->d_chains;
     P.pchains = e->d_pchains;
-    P.q_rating = e->d_q_rating;
-    P.q_cons = e->d_q_cons;
-    P.q_slot = e->d_q_slot;
     for (int b = 0; b < 2; ++b) {
         P.key[b] = e->d_pk_key[b]; P.oidx[b] = e->d_pk_oidx[b];
         P.nx16[b] = e->d_pk_nx16[b]; P.bits[b] = e->d_pk_bits[b];
@@ -2478,16 +2137,10 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
     P.grp = 0;
     P.pbar = e->d_pk_pbar;
     P.pxmask = (uint32_t*)(e->d_pk_pbar + MM_MAX_GROUPS);
-    P.ptimeout0 = e->pair_ptimeout[0];
-    P.ptimeout1 = e->pair_ptimeout[1];
-    P.pinject = e->pair_pinject;
     P.pyield = (uint32_t*)(e->d_pk_pbar + MM_MAX_GROUPS) + MM_MAX_GROUPS;
-    P.out_slots = e->d_out_slots;
-    P.out_score = e->d_out_score;
-    P.out_pass = e->d_out_pass;
     const unsigned long long bound64 = e->live_upper < cfg.capacity ? e->live_upper : cfg.capacity;
     const uint32_t bound = (uint32_t)bound64;
-    if (e->pair_tune & 0x10000u) HIPCHK(e, hipMemsetAsync(e->d_pk_grec, 0, (size_t)G * e->pk_gstride * sizeof(uint4), e->stream));   // (diagnostics)
+    if (e->tn.pair_tune & 0x10000u) HIPCHK(e, hipMemsetAsync(e->d_pk_grec, 0, (size_t)G * e->pk_gstride * sizeof(uint4), e->stream));   // (diagnostics)
     hipLaunchKernelGGL(kp_init, dim3(G), dim3(1024), 0, e->stream, P, cfg.capacity);
     hipLaunchKernelGGL(kp_pack, dim3((bound + 32u + 1023u) / 1024u, G), dim3(1024), 0, e->stream, P);
     {
@@ -2500,8 +2153,8 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
         // lengths yet — and a quarter of a million workgroups that only find out they have nothing to do are not free)
         uint32_t seg = 256u, stage = NXI_STAGE;
         while (seg < NXI_SEG && (unsigned long long)bound > 8192ull * seg) seg <<= 1;
-        if (e->pair_nxseg) seg = e->pair_nxseg;               // MM_PAIR_NXSEG / MM_PAIR_NXSTAGE (experiments)
-        if (e->pair_nxstage) stage = e->pair_nxstage;
+        if (e->tn.pair_nxseg) seg = e->tn.pair_nxseg;               // MM_PAIR_NXSEG / MM_PAIR_NXSTAGE (experiments)
+        if (e->tn.pair_nxstage) stage = e->tn.pair_nxstage;
         if (stage < seg + 64u) stage = seg + 64u;
         if (stage > NXI_STAGE) stage = NXI_STAGE;
         const bool timing = (cfg.flags & MM_CFG_TIMING) != 0;
@@ -2529,11 +2182,11 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
             // counted in looks that bound was 3 x capacity round trips (tens of minutes at 2^24 before MM_ERR_INTERNAL,
             // and 3u * capacity wraps above 1.43e9).  Counted in PASSES it is tight: see idle_looks below.
             if (idle_looks > 64u) return MM_ERR_INTERNAL;
-            { int lrc = look_launch(e, e->d_pchains, e->h_pchains, G * sizeof(PairChain)); if (lrc) return lrc; }
-            { int lrc = look_wait(e); if (lrc) return lrc; }
+            MMTRY(look_launch(e, e->d_pchains, e->h_pchains, G * sizeof(PairChain)));
+            MMTRY(look_wait(e));
             ++e->ps.host_looks;
-            if (e->pair_debug && guard >= 200u && guard % 200u == 0u) {           // (a tick that looks at its chains hundreds of times)
-                fprintf(stderr, "[mm-pair] look %u: cool-down %u, persist %d, last tile length %u;", guard, e->pair_pcool, (int)e->pair_persist, last_tp);
+            if (e->tn.debug && guard >= 200u && guard % 200u == 0u) {           // (a tick that looks at its chains hundreds of times)
+                fprintf(stderr, "[mm-pair] look %u: cool-down %u, persist %d, last tile length %u;", guard, e->pair_pcool, (int)kp_rounds_on(e), last_tp);
                 for (uint32_t g = 0; g < G; ++g) {
                     const PairChain& pc = e->h_pchains[g];
                     if (pc.fast) fprintf(stderr, " g%u[stage %u m %u qlen %u passes %u compact %u pfail 0x%x]", g, pc.stage, pc.m, pc.qlen, pc.passes, pc.want_compact, pc.pfail);
@@ -2567,11 +2220,11 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
                     ++e->pair_pstops;
                     e->pair_pcool = 16u;
                     const uint32_t why = pc.pfail & 0xFFu;
-                    if (why == PF_XCD) { e->pair_persist = false; ++e->ps.pair_stops_xcd; }
+                    if (why == PF_XCD) { e->kp_rounds_off = true; ++e->ps.pair_stops_xcd; }
                     else if (why == PF_INJECT) ++e->ps.pair_stops_inject;
                     else ++e->ps.pair_stops_timeout;
                     e->ps.degraded = 1;
-                    if (e->pair_debug) fprintf(stderr, "[mm-pair] g%u: kp_rounds stopped (reason %u, iteration %u)\n", g, pc.pfail & 0xFFu, pc.pfail >> 8);
+                    if (e->tn.debug) fprintf(stderr, "[mm-pair] g%u: kp_rounds stopped (reason %u, iteration %u)\n", g, pc.pfail & 0xFFu, pc.pfail >> 8);
                 }
                 P.bm[g] = pc.m;                       // constant until the next compaction, i.e. for the whole batch
                 P.bbuf[g] = (uint8_t)pc.buf;
@@ -2612,21 +2265,21 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
             // compacted now rather than at 75 % alive.  Only the longest chain decides the tile length.
             bool want_fit = false;
             uint32_t yield_q = 0, yield_g = 0;
-            if (e->pair_persist && !e->pair_pcool && !compact && !e->pair_tile_fixed) {
+            if (kp_rounds_on(e) && !e->pair_pcool && !compact && !e->tn.pair_tile_fixed) {
                 uint32_t gl = 0;
                 for (uint32_t g = 1; g < G; ++g)
                     if (P.bm[g] > P.bm[gl]) gl = g;
                 const PairChain& pc = e->h_pchains[gl];
                 if (P.bm[gl]) {
                     // the capacity the chain's index space has to get under for the next shorter tile length (or for kp_rounds)
-                    uint32_t capq = e->pair_ptiles * PK_TMAX;
-                    for (uint32_t tlen = PK_TMAX; tlen >= PK_TMAX / 4u && pc.m <= e->pair_ptiles * tlen; tlen >>= 1) capq = e->pair_ptiles * (tlen >> 1);
-                    if (pc.m <= e->pair_ptiles * (PK_TMAX / 4u)) capq = PL_MAX - 1u;          // shortest tiles already: next is kp_late
+                    uint32_t capq = e->tn.pair_ptiles * PK_TMAX;
+                    for (uint32_t tlen = PK_TMAX; tlen >= PK_TMAX / 4u && pc.m <= e->tn.pair_ptiles * tlen; tlen >>= 1) capq = e->tn.pair_ptiles * (tlen >> 1);
+                    if (pc.m <= e->tn.pair_ptiles * (PK_TMAX / 4u)) capq = PL_MAX - 1u;          // shortest tiles already: next is kp_late
                     if (pc.qlen <= capq && pc.m > capq && capq >= PL_MAX) {
                         hipLaunchKernelGGL(kp_ask_compact, dim3(G), dim3(64), 0, e->stream, P, 1u << gl);
                         compact = true;
                     } else {
-                        if (pc.m > e->pair_ptiles * PK_TMAX) want_fit = true;          // not yet within kp_rounds' reach: a short batch
+                        if (pc.m > e->tn.pair_ptiles * PK_TMAX) want_fit = true;          // not yet within kp_rounds' reach: a short batch
                         yield_q = capq;                                                // compact (and, in kp_rounds, end the batch) at this length
                         yield_g = gl;
                     }
@@ -2636,10 +2289,10 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
             // walk costs one dependent load per tile, everything else is proportional to the tile)
             uint32_t tp = PK_TMAX;
             // several passes per launch (kp_rounds) when every chain's tiles fit the CUs of one XCD
-            bool persist = e->pair_persist && !compact && (longest + PK_TMAX - 1u) / PK_TMAX <= e->pair_ptiles;
+            bool persist = kp_rounds_on(e) && !compact && (longest + PK_TMAX - 1u) / PK_TMAX <= e->tn.pair_ptiles;
             if (persist && e->pair_pcool) { --e->pair_pcool; persist = false; e->ps.degraded = 1; }
             // (a batch that kp_rounds would have taken, walked launch by launch because it is off: a fall-back's timing)
-            if (!e->pair_persist && !compact && (longest + PK_TMAX - 1u) / PK_TMAX <= e->pair_ptiles) e->ps.degraded = 1;
+            if (!kp_rounds_on(e) && !compact && (longest + PK_TMAX - 1u) / PK_TMAX <= e->tn.pair_ptiles) e->ps.degraded = 1;
             // ONE cap for the tile count whether this batch is kp_rounds' or kp_round's (round 5): the tile length of a tick must
             // never GROW.  An entry next[i] = NX_FAR says "nobody fits inside the horizon", and the horizon is two tiles of the
             // length it was computed at; the walk resolves it by scanning from the end of the CURRENT horizon — right for an
@@ -2649,9 +2302,9 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
             // kp_rounds, or while ANOTHER chain was still too long for kp_rounds — came back to kp_rounds at 2 T.  Found by
             // tests/stress.py with MM_PAIR_PTILES=5 (seed 130203984: 46 lobbies of one chain missing), on the device and on
             // the shim; it needs a stop of kp_rounds (or the knob) to happen, which is why no default run ever met it.
-            const uint32_t cap_p = e->pair_ptiles < e->pair_tiles_max ? e->pair_ptiles : e->pair_tiles_max;
-            const uint32_t tiles_max = e->pair_persist ? cap_p : e->pair_tiles_max;
-            if (!e->pair_tile_fixed)
+            const uint32_t cap_p = e->tn.pair_ptiles < e->tn.pair_tiles_max ? e->tn.pair_ptiles : e->tn.pair_tiles_max;
+            const uint32_t tiles_max = kp_rounds_on(e) ? cap_p : e->tn.pair_tiles_max;
+            if (!e->tn.pair_tile_fixed)
                 for (uint32_t cand = PK_TMAX / 4u; cand < PK_TMAX; cand <<= 1)    // (an eighth was measured: slower, the fixed cost of a round takes over)
                     if ((longest + cand - 1u) / cand <= tiles_max) { tp = cand; break; }
             if (last_tp && tp > last_tp && !compact) {
@@ -2690,7 +2343,7 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
                 // one launch per pass; the first of a batch only prepares, the commit brings the
                 // latest parity back into the chains' committed state
                 // chains of many tiles: a second level of the route, rebuilt behind every round (kp_group)
-                P.grp = (e->pair_group_min && tiles >= e->pair_group_min && tp == PK_TMAX) ? PK_GS : 0u;
+                P.grp = (e->tn.pair_group_min && tiles >= e->tn.pair_group_min && tp == PK_TMAX) ? PK_GS : 0u;
                 const uint32_t ngr = P.grp ? (tiles + P.grp - 1u) / P.grp : 0u;
                 // the batch's workgroup map: a chain's tiles together on one XCD (mm_pair.inc, PairParams.xseg)
                 dim3 rgrid(tiles, G);
@@ -2704,20 +2357,20 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
                         P.grp = 0;
                         // (the arrival words are zero: kp_init at the start of the tick, kc_commit behind every batch)
                         // (the batch ends by itself when the longest chain can be compacted into shorter tiles: it may be long)
-                        const uint32_t K = e->pair_pbatch, slice = MM_PERSIST_SLICE ? MM_PERSIST_SLICE : K + 1u;
+                        const uint32_t K = e->tn.pair_pbatch, slice = MM_PERSIST_SLICE ? MM_PERSIST_SLICE : K + 1u;
                         for (uint32_t it = 0; it <= K; it += slice)
                             TILE_LAUNCH(kp_rounds, dim3(8u * slots), dim3(PT_THREADS), P, it, it + slice < K + 1u ? it + slice : K + 1u, K);
                         ++e->ps.pair_rounds_launches;
                         after_persist = true;
                         COMPACT_LAUNCH();
                         HIPCHK(e, hipGetLastError());
-                        { int arc = results_absorb(e, M.L); if (arc) return arc; }
-                        { int src = results_send(e, sent_no, M.L, e->results_early ? MM_RESULTS_MIN_PAIR : 0xFFFFFFFFu); if (src) return src; }
+                        MMTRY(results_absorb(e, M.L));
+                        MMTRY(results_send(e, sent_no, M.L, e->tn.results_early ? MM_RESULTS_MIN_PAIR : 0xFFFFFFFFu));
                         continue;
                     }
                     P.xslots = 0;
                 }
-                if (e->pair_xcd) {
+                if (e->tn.pair_xcd) {
                     const uint32_t slots = pair_xcd_map(P, tof, G);
                     if (slots) rgrid = dim3(8u * slots);
                 }
@@ -2725,7 +2378,7 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
                 TILE_LAUNCH(kp_round, rgrid, dim3(PT_THREADS), P, r, 1u);
                 ++r;
                 if (P.grp) TILE_LAUNCH(kp_group, dim3(ngr, G), dim3(1024), P, r);
-                for (uint32_t b = 0; b < (want_fit && e->pair_batch > 12u ? 12u : e->pair_batch); ++b) {
+                for (uint32_t b = 0; b < (want_fit && e->tn.pair_batch > 12u ? 12u : e->tn.pair_batch); ++b) {
                     TILE_LAUNCH(kp_round, rgrid, dim3(PT_THREADS), P, r, 0u);
                     ++e->ps.pair_round_launches;
                     ++r;
@@ -2741,18 +2394,74 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
             HIPCHK(e, hipGetLastError());
             // the device is busy with the batch: now the host takes what the last look's copies brought (slots released)
             // and sends this look's lobbies after them
-            { int arc = results_absorb(e, M.L); if (arc) return arc; }
-            { int src = results_send(e, sent_no, M.L, e->results_early ? MM_RESULTS_MIN_PAIR : 0xFFFFFFFFu); if (src) return src; }
+            MMTRY(results_absorb(e, M.L));
+            MMTRY(results_send(e, sent_no, M.L, e->tn.results_early ? MM_RESULTS_MIN_PAIR : 0xFFFFFFFFu));
         }
     }
     hipLaunchKernelGGL(kp_late, dim3(G), dim3(PL_THREADS), 0, e->stream, P);
     hipLaunchKernelGGL(kp_finish, dim3(G), dim3(1024), 0, e->stream, P);
     HIPCHK(e, hipGetLastError());
     if (tail_send) {
-        { int arc = results_absorb(e, M.L); if (arc) return arc; }
-        { int src = results_send(e, tail_no, M.L, e->results_early ? MM_RESULTS_MIN_PAIR : 0xFFFFFFFFu); if (src) return src; }
+        MMTRY(results_absorb(e, M.L));
+        MMTRY(results_send(e, tail_no, M.L, e->tn.results_early ? MM_RESULTS_MIN_PAIR : 0xFFFFFFFFu));
     }
     return MM_OK;
+}
+
+// MM_PAIR_DEBUG=1: what the team path's kernels counted and timed in this tick, per rating group (stderr).
+static void report_team(const mm_engine* e)
+{
+    const uint32_t G = e->cfg.n_groups;
+    for (uint32_t g = 0; g < G; ++g) {
+        const TeamChain& t = e->h_tchains[g];
+        const uint32_t np = t.passes + 1u;
+        fprintf(stderr, "[mm-team] g%u fast %u m %u passes %u out %u left %u | cancel tick: head sat out %u, seated %u, lobby filtered %u, anchor moved %u x | "
+                "kt_f, the middle chunk, cycles per pass: first loads %u, probes + lists %u, replacements %u, look-ups from scratch %u, barrier %u, step C %u; anchors at work per pass %u | "
+                "F values written %u, changed after the first pass %u | kt_chase: sub-queue entries looked at by the stored lobby's fills %u, by %u look-ups %u\n",
+                g, t.fast, t.m, t.passes, t.n_out, t.qlen,
+                t.dbg[6] & 1u, (t.dbg[6] >> 1) & 1u, (t.dbg[6] >> 2) & 1u, t.dbg[7],
+                t.tmk[0] / np, t.tmk[1] / np, t.tmk[2] / np, t.tmk[3] / np, t.tmk[4] / np, t.tmk[5] / np, t.dbg[2] / np, t.dbg[5], t.dbg[4],
+                t.dbg[0], t.dbg[3], t.dbg[1]);
+        if (t.lt[11])
+            fprintf(stderr, "[mm-team] g%u kt_fc's chaser: %u passes, %u lobbies by F; cycles per pass: all %u, the chase loop %u, its hops by F %u, of them on kt_f's flags %u; "
+                    "cycles per hop without the flags %u; %u look-ups, cycles each: starts %u, the roles' stretches %u, the members' records %u, seats + kills (the one a pass ends on) %u "
+                    "(with MM_TEAM_LATE=0: kt_late keeps its own timers in the same words)\n",
+                    g, t.lt[11], t.lt[12], 16u * (t.lt[9] / t.lt[11]), 16u * (t.lt[10] / t.lt[11]), 16u * (t.lt[13] / t.lt[11]), 16u * (t.lt[8] / t.lt[11]),
+                    t.lt[12] ? (uint32_t)(16ull * (t.lt[13] - t.lt[8]) / t.lt[12]) : 0u,
+                    t.lt[3], t.lt[3] ? 16u * (t.lt[4] / t.lt[3]) : 0u, t.lt[3] ? 16u * (t.lt[5] / t.lt[3]) : 0u, t.lt[3] ? 16u * (t.lt[6] / t.lt[3]) : 0u,
+                    16u * (t.lt[7] / t.lt[11]));
+    }
+}
+
+// ... per look while kt_late walks: the chains whose pass count moved since `p0`
+static void report_team_late(const mm_engine* e, const uint32_t* p0)
+{
+    const uint32_t G = e->cfg.n_groups;
+    for (uint32_t g = 0; g < G; ++g) {
+        const TeamChain& t = e->h_tchains[g];
+        if (t.fast && t.passes != p0[g])
+            fprintf(stderr, "[mm-team-late] g%u: kt_late walked passes %u..%u%s (m %u, sub-queues %u %u %u %u %u): "
+                    "%u lobbies by record, %u looked up, %u left open, %u stored fills; entries scanned per role %u %u %u %u %u; "
+                    "cycles/16: records %u look-ups %u fills %u ring waits %u all %u\n", g, p0[g], t.passes,
+                    t.done ? "" : " and handed the chain back", t.m, t.len[0], t.len[1], t.len[2], t.len[3], t.len[4],
+                    t.lt[1], t.lt[2], t.lt[3], t.lt[4], t.lt[5], t.lt[6], t.lt[7], t.lt[8], t.lt[9], t.lt[10], t.lt[11],
+                    t.lt[12], t.lt[14], t.lt[13]);
+    }
+}
+
+// ... with MM_TEAM_BATCH=1: one line per pass, the longest chain
+static void report_team_pass(mm_engine* e, uint32_t guard)
+{
+    const uint32_t G = e->cfg.n_groups;
+    uint32_t gl = 0;
+    for (uint32_t g = 1; g < G; ++g)
+        if (e->h_tchains[g].m > e->h_tchains[gl].m) gl = g;
+    const TeamChain& tc = e->h_tchains[gl];
+    if (guard == 0) { e->dbg_last_w = 0; e->dbg_last_c = 0; }
+    fprintf(stderr, "[mm-team-pass] g%u pass %u queued %u lobbies %u F written %u changed %u\n", gl, tc.passes,
+            tc.qlen, tc.n_vis, tc.dbg[5] - e->dbg_last_w, tc.dbg[4] - e->dbg_last_c);
+    e->dbg_last_w = tc.dbg[5];
+    e->dbg_last_c = tc.dbg[4];
 }
 
 // The team path (mm_team.inc).  *any is set when at least one chain was walked by it; the others
@@ -2763,40 +2472,26 @@ static int team_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge, 
     const uint32_t G = cfg.n_groups;
     *any = false;
     TeamParams P;
-    memset(&P, 0, sizeof(P));
-    P.mode = mode;
-    P.n_groups = G;
-    P.capacity = cfg.capacity;
+    walk_params_common(P, e, mode, purge);
+    // the knobs (mm_tuning -> TeamParams)
+    P.scan_cap = e->tn.team_cap;
+    P.late_bail = 4u * e->tn.team_late + 32u;
+    P.fwait = e->tn.team_fwait;
+    P.fix_max = e->tn.team_fix_max;
+    P.fix_t8 = e->tn.team_fix_t8;
+    P.fix_t4 = e->tn.team_fix_t4;
+    P.pull_xcd = e->tn.team_pull_xcd;
+    P.nowait = e->tn.team_nowait;
+    P.debug = e->tn.debug ? (e->tn.team_batch == 1u ? 3u : 1u) : 0u;   // bit 1 (with MM_TEAM_BATCH=1): kt_f counts every F it writes — an atomic per thread
     P.window = M.window > 0xFFFFFu ? 0xFFFFFu : M.window;
     P.eqmask = M.eqmask;
     P.out_cap = (cfg.capacity + MM_MAX_LOBBY) / M.L + 1u;
-    P.out_slot_stride = e->out_slot_stride;
-    P.out_rec_stride = e->out_rec_stride;
     P.bits_stride = e->pk_bits_stride;
     P.pstride = e->pk_stride;
     P.chunk_stride = e->tk_chunk_stride;
     P.blk_stride = e->pk_stride / 64u;
-    P.purge = purge ? 1u : 0u;
-    P.state = e->d_state;
-    P.released = e->d_released;
-    P.n_released = e->d_counters;
-    P.scan_cap = e->team_cap;
-    P.late_bail = 4u * e->team_late + 32u;
-    P.fwait = e->team_fwait;
-    P.fix_max = e->team_fix_max;
-    P.fix_t8 = e->team_fix_t8;
-    P.fix_t4 = e->team_fix_t4;
-    P.pull_xcd = e->team_pull_xcd;
-    P.nowait = e->team_nowait;
-    P.debug = e->pair_debug ? (e->team_batch == 1u ? 3u : 1u) : 0u;   // bit 1 (with MM_TEAM_BATCH=1): kt_f counts every F it writes — an atomic per thread
-    P.seq = 0;
-    P.n_emit = 0;
     P.M = M;
-    P.chains = e->d_chains;
     P.tchains = e->d_tchains;
-    P.q_rating = e->d_q_rating;
-    P.q_cons = e->d_q_cons;
-    P.q_slot = e->d_q_slot;
     P.tkey = e->d_pk_key[0];
     P.bits[0] = e->d_pk_bits[0];
     P.bits[1] = e->d_pk_bits[1];
@@ -2813,17 +2508,13 @@ static int team_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge, 
     P.chunkB = e->d_tk_chunkB;
     P.sqi = e->d_tk_sqi;
     P.fdone = e->d_tk_fdone;
-    P.use_f2 = 0;
-    P.out_slots = e->d_out_slots;
-    P.out_score = e->d_out_score;
-    P.out_pass = e->d_out_pass;
     hipLaunchKernelGGL(kt_init, dim3(G), dim3(1024), 0, e->stream, P);
     HIPCHK(e, hipGetLastError());
-    { int lrc = look_launch(e, e->d_tchains, e->h_tchains, G * sizeof(TeamChain)); if (lrc) return lrc; }
-    { int lrc = look_wait(e); if (lrc) return lrc; }
+    MMTRY(look_launch(e, e->d_tchains, e->h_tchains, G * sizeof(TeamChain)));
+    MMTRY(look_wait(e));
     uint32_t longest = 0;
     unsigned long long arrivals = 0;
-    bool late_ok = e->team_late != 0u;
+    bool late_ok = e->tn.team_late != 0u;
     for (uint32_t g = 0; g < G; ++g) {
         const TeamChain& t = e->h_tchains[g];
         if (!t.fast) continue;
@@ -2873,12 +2564,12 @@ static int team_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge, 
     // seen only a few arrivals since its last (quiescent) tick: the ticks of a stream.  kt_late hands a chain back
     // after a pass that seated many lobbies after all (`late_bail`); the sub-queues are rebuilt then (it leaves no
     // tombstones behind).
-    uint32_t pass = 0, batch = e->team_batch < 2u ? e->team_batch : 2u;
+    uint32_t pass = 0, batch = e->tn.team_batch < 2u ? e->tn.team_batch : 2u;
     uint32_t n_emit = longest / (M.L * TC_WAVES * 8u) + 1u;          // the first passes: a worker wave per lobby if an eighth of the chain is seated
-    if (n_emit > e->team_emit_max) n_emit = e->team_emit_max;
+    if (n_emit > e->tn.team_emit_max) n_emit = e->tn.team_emit_max;
     uint32_t team_no[MM_MAX_GROUPS];
     bool team_have = false, force_build = false;
-    bool late_now = late_ok && e->team_late0 != 0u && arrivals <= e->team_late0;
+    bool late_now = late_ok && e->tn.team_late0 != 0u && arrivals <= e->tn.team_late0;
     ++e->ps.host_looks;
     if (late_now) { hipLaunchKernelGGL(kt_build, dim3(nch, G), dim3(TT_CH), 0, e->stream, P); ++e->ps.team_build_launches; }
     for (uint32_t guard = 0;; ++guard) {
@@ -2891,10 +2582,10 @@ static int team_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge, 
         } else {
             for (uint32_t b = 0; b < batch; ++b, ++pass) {
                 // the first passes of a tick emit hundreds of lobbies each: the chase takes them two at a time (kt_f2)
-                P.use_f2 = pass < e->team_f2 ? 1u : 0u;
+                P.use_f2 = pass < e->tn.team_f2 ? 1u : 0u;
                 // the role sub-queues are rebuilt in the first two passes (a head that sat out the first one is back in
                 // the second) and every team_rebuild passes after; in between, players that leave are tombstones in them
-                if (pass < 2u || pass % e->team_rebuild == 0u || force_build) {
+                if (pass < 2u || pass % e->tn.team_rebuild == 0u || force_build) {
                     hipLaunchKernelGGL(kt_build, dim3(nch, G), dim3(TT_CH), 0, e->stream, P);
                     ++e->ps.team_build_launches;
                 }
@@ -2907,8 +2598,8 @@ static int team_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge, 
                 P.hf_x = 0xFFFFFFFFu;
                 if (P.use_f2) {
                     // (the stored lobbies' fill from the heads of the queues rides in kt_f's launch: MM_TEAM_SPLIT)
-                    if (e->team_split) P.hf_x = nch;
-                    hipLaunchKernelGGL(kt_f, dim3(nch + (e->team_split ? 1u : 0u), G), dim3(TT_CH), 0, e->stream, P);
+                    if (e->tn.team_split) P.hf_x = nch;
+                    hipLaunchKernelGGL(kt_f, dim3(nch + (e->tn.team_split ? 1u : 0u), G), dim3(TT_CH), 0, e->stream, P);
                     hipLaunchKernelGGL(kt_f2, dim3(nch, G), dim3(TT_CH), 0, e->stream, P);
                     hipLaunchKernelGGL(kt_chase, dim3(G * (1u + P.n_emit)), dim3(TC_THREADS), 0, e->stream, P);
                     ++e->ps.team_f_launches;
@@ -2922,11 +2613,11 @@ static int team_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge, 
         HIPCHK(e, hipGetLastError());
         uint32_t p0[MM_MAX_GROUPS];
         for (uint32_t g = 0; g < G; ++g) p0[g] = e->h_tchains[g].passes;
-        { int lrc = look_launch(e, e->d_tchains, e->h_tchains, G * sizeof(TeamChain)); if (lrc) return lrc; }
+        MMTRY(look_launch(e, e->d_tchains, e->h_tchains, G * sizeof(TeamChain)));
         // host work while the device runs the batch: what the last look's copies brought, then this look's lobbies
-        { int arc = results_absorb(e, M.L); if (arc) return arc; }
-        if (team_have) { int src = results_send(e, team_no, M.L, e->results_early ? MM_RESULTS_MIN_TEAM : 0xFFFFFFFFu); if (src) return src; }
-        { int lrc = look_wait(e); if (lrc) return lrc; }
+        MMTRY(results_absorb(e, M.L));
+        if (team_have) MMTRY(results_send(e, team_no, M.L, e->tn.results_early ? MM_RESULTS_MIN_TEAM : 0xFFFFFFFFu));
+        MMTRY(look_wait(e));
         ++e->ps.host_looks;
         {   // kt_fc's chasers count the anchors whose chunk flag did not come (they looked the lobby up themselves)
             uint32_t fl = 0;
@@ -2940,30 +2631,10 @@ static int team_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge, 
             if (!t.fast || t.done) continue;
             busy = true;
             most = t.n_vis > most ? t.n_vis : most;
-            if (t.n_vis > e->team_late) late = false;
+            if (t.n_vis > e->tn.team_late) late = false;
         }
-        if (e->pair_debug && late_now)
-            for (uint32_t g = 0; g < G; ++g) {
-                const TeamChain& t = e->h_tchains[g];
-                if (t.fast && t.passes != p0[g])
-                    fprintf(stderr, "[mm-team-late] g%u: kt_late walked passes %u..%u%s (m %u, sub-queues %u %u %u %u %u): "
-                            "%u lobbies by record, %u looked up, %u left open, %u stored fills; entries scanned per role %u %u %u %u %u; "
-                            "cycles/16: records %u look-ups %u fills %u ring waits %u all %u\n", g, p0[g], t.passes,
-                            t.done ? "" : " and handed the chain back", t.m, t.len[0], t.len[1], t.len[2], t.len[3], t.len[4],
-                            t.lt[1], t.lt[2], t.lt[3], t.lt[4], t.lt[5], t.lt[6], t.lt[7], t.lt[8], t.lt[9], t.lt[10], t.lt[11],
-                            t.lt[12], t.lt[14], t.lt[13]);
-            }
-        if (e->pair_debug && e->team_batch == 1u && !late_now) {   // MM_TEAM_BATCH=1: one line per pass, the longest chain
-            uint32_t gl = 0;
-            for (uint32_t g = 1; g < G; ++g)
-                if (e->h_tchains[g].m > e->h_tchains[gl].m) gl = g;
-            const TeamChain& tc = e->h_tchains[gl];
-            if (guard == 0) { e->dbg_last_w = 0; e->dbg_last_c = 0; }
-            fprintf(stderr, "[mm-team-pass] g%u pass %u queued %u lobbies %u F written %u changed %u\n", gl, tc.passes,
-                    tc.qlen, tc.n_vis, tc.dbg[5] - e->dbg_last_w, tc.dbg[4] - e->dbg_last_c);
-            e->dbg_last_w = tc.dbg[5];
-            e->dbg_last_c = tc.dbg[4];
-        }
+        if (e->tn.debug && late_now) report_team_late(e, p0);
+        if (e->tn.debug && e->tn.team_batch == 1u && !late_now) report_team_pass(e, guard);
         {   // the lobbies emitted so far leave for the host while the next passes run (sent behind the next batch's launches)
             uint32_t bf[MM_MAX_GROUPS];
             for (uint32_t g = 0; g < G; ++g) { bf[g] = e->h_tchains[g].before; team_no[g] = e->h_tchains[g].fast ? e->h_tchains[g].n_out : 0u; }
@@ -2977,41 +2648,160 @@ static int team_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge, 
             // from the chain's current pass on
             late_now = false;
             if (pass < 2u) pass = 2u;                 // (no doubled rebuild: the tick is past its opening)
-            batch = e->team_batch;
+            batch = e->tn.team_batch;
             continue;
         }
         late_now = late;
         n_emit = most / (TT_WAVES - 1u) + 1u;                         // (kt_fc's emitter workgroups have seven worker waves)
-        if (n_emit > e->team_emit_max) n_emit = e->team_emit_max;
+        if (n_emit > e->tn.team_emit_max) n_emit = e->tn.team_emit_max;
         // close to the switch: look again soon (a look costs a D2H round trip, an idle pass a launch)
-        batch = (e->team_late && most <= 3u * e->team_late) ? (e->team_batch < 4u ? e->team_batch : 4u) : e->team_batch;
+        batch = (e->tn.team_late && most <= 3u * e->tn.team_late) ? (e->tn.team_batch < 4u ? e->tn.team_batch : 4u) : e->tn.team_batch;
     }
     if (e->ps.team_flags_late) { e->ps.team_flags_late_total += e->ps.team_flags_late; e->ps.degraded = 1; }
     hipLaunchKernelGGL(kt_fin_scatter, dim3(nch, G), dim3(TT_CH), 0, e->stream, P);
     hipLaunchKernelGGL(kt_fin_copy, dim3(nch, G), dim3(TT_CH), 0, e->stream, P);
     HIPCHK(e, hipGetLastError());
-    if (e->pair_debug)
-        for (uint32_t g = 0; g < G; ++g)
-        {
-            const TeamChain& t = e->h_tchains[g];
-            const uint32_t np = t.passes + 1u;
-            fprintf(stderr, "[mm-team] g%u fast %u m %u passes %u out %u left %u | cancel tick: head sat out %u, seated %u, lobby filtered %u, anchor moved %u x | "
-                    "kt_f, the middle chunk, cycles per pass: first loads %u, probes + lists %u, replacements %u, look-ups from scratch %u, barrier %u, step C %u; anchors at work per pass %u | "
-                    "F values written %u, changed after the first pass %u | kt_chase: sub-queue entries looked at by the stored lobby's fills %u, by %u look-ups %u\n",
-                    g, t.fast, t.m, t.passes, t.n_out, t.qlen,
-                    t.dbg[6] & 1u, (t.dbg[6] >> 1) & 1u, (t.dbg[6] >> 2) & 1u, t.dbg[7],
-                    t.tmk[0] / np, t.tmk[1] / np, t.tmk[2] / np, t.tmk[3] / np, t.tmk[4] / np, t.tmk[5] / np, t.dbg[2] / np, t.dbg[5], t.dbg[4],
-                    t.dbg[0], t.dbg[3], t.dbg[1]);
-            if (t.lt[11])
-                fprintf(stderr, "[mm-team] g%u kt_fc's chaser: %u passes, %u lobbies by F; cycles per pass: all %u, the chase loop %u, its hops by F %u, of them on kt_f's flags %u; "
-                        "cycles per hop without the flags %u; %u look-ups, cycles each: starts %u, the roles' stretches %u, the members' records %u, seats + kills (the one a pass ends on) %u "
-                        "(with MM_TEAM_LATE=0: kt_late keeps its own timers in the same words)\n",
-                        g, t.lt[11], t.lt[12], 16u * (t.lt[9] / t.lt[11]), 16u * (t.lt[10] / t.lt[11]), 16u * (t.lt[13] / t.lt[11]), 16u * (t.lt[8] / t.lt[11]),
-                        t.lt[12] ? (uint32_t)(16ull * (t.lt[13] - t.lt[8]) / t.lt[12]) : 0u,
-                        t.lt[3], t.lt[3] ? 16u * (t.lt[4] / t.lt[3]) : 0u, t.lt[3] ? 16u * (t.lt[5] / t.lt[3]) : 0u, t.lt[3] ? 16u * (t.lt[6] / t.lt[3]) : 0u,
-                        16u * (t.lt[7] / t.lt[11]));
-        }
+    if (e->tn.debug) report_team(e);
     return MM_OK;
+}
+
+// MM_PAIR_DEBUG=1: what the pair path's kernels counted and timed in this tick, per rating group (stderr).
+static int report_pair(mm_engine* e)
+{
+    const uint32_t G = e->cfg.n_groups;
+    std::vector<PairChain> hp(G);
+    HIPCHK(e, hipMemcpy(hp.data(), e->d_pchains, G * sizeof(PairChain), hipMemcpyDeviceToHost));
+    for (uint32_t g = 0; g < G; ++g)
+        fprintf(stderr, "[mm-pair] g%u fast %u m %u qlen %u passes %u out %u rounds %u (group hops of tile 0: %u of %u entries looked at, %u not of the round) | stale %u inv %u slowsucc %u compact %u fixed(w1) %u | chase clk %u wall(100MHz) %u wrapscan clk %u\n",
+                g, hp[g].fast, hp[g].m, hp[g].qlen, hp[g].passes, hp[g].n_out, hp[g].rounds, hp[g].ghops, hp[g].gtry, hp[g].gstale, hp[g].dbg[0], hp[g].dbg[1],
+                hp[g].dbg[2], hp[g].dbg[3], hp[g].dbg[4], hp[g].dbg[5], hp[g].dbg[6], hp[g].dbg[7]);
+    for (uint32_t g = 0; g < G; ++g)
+        if (hp[g].rounds) {
+            const uint32_t nr = hp[g].tm[5] ? hp[g].tm[5] : 1u;
+            fprintf(stderr, "[mm-pair] g%u tile1 cycles/round over %u rounds (load %u walk+stage+sweepA %u apply %u | detect %u items %u long %u (%.1f long items) | graph %u resolve %u publish %u | cand+head %u)\n",
+                    g, nr, hp[g].tm[0] / nr, hp[g].tm[6] / nr, hp[g].tm[9] / nr, hp[g].tm[1] / nr, hp[g].tm[12] / nr, hp[g].tm[2] / nr,
+                    (double)hp[g].tm[11] / nr, hp[g].tm[7] / nr, hp[g].tm[8] / nr, hp[g].tm[10] / nr, hp[g].tm[4] / nr);
+        }
+    for (uint32_t g = 0; g < G; ++g)
+        if (hp[g].ppass) {
+            const uint32_t nr = hp[g].ptm[5] ? hp[g].ptm[5] : 1u;
+            fprintf(stderr, "[mm-pair] g%u kp_rounds: %u passes inside persistent launches (%u launches gave up so far); tile1 cycles/pass over %u passes (barrier %u fast hops %u walk+sweepA %u apply %u | detect %u items %u long %u | graph %u resolve %u publish %u | head+arrive %u) walk loop %.0f cycles, %.1f hops\n",
+                    g, hp[g].ppass, e->pair_pstops, nr, hp[g].ptm[0] / nr, hp[g].ptm[3] / nr, hp[g].ptm[6] / nr, hp[g].ptm[9] / nr, hp[g].ptm[1] / nr,
+                    hp[g].ptm[12] / nr, hp[g].ptm[2] / nr, hp[g].ptm[7] / nr, hp[g].ptm[8] / nr, hp[g].ptm[10] / nr, hp[g].ptm[4] / nr,
+                    16.0 * hp[g].ptm[13] / nr, (double)hp[g].ptm[15] / nr);
+            fprintf(stderr, "[mm-pair] g%u kp_rounds, tile 1's walker off the fast path: %u hops whose partner had left, %.0f cycles each; %u hops without a partner inside the horizon, %.0f cycles each\n",
+                    g, hp[g].pslow[0], hp[g].pslow[0] ? 16.0 * hp[g].pslow[1] / hp[g].pslow[0] : 0.0, hp[g].pslow[2],
+                    hp[g].pslow[2] ? 16.0 * hp[g].pslow[3] / hp[g].pslow[2] : 0.0);
+        }
+    {   // where the last kp_rounds launch ran and where the tables live (run-to-run spread: two modes of the walk, 9.4 / 9.7 ms)
+        fprintf(stderr, "[mm-pair] physical XCD mask of each chain's workgroups in its last kp_rounds launch:");
+        for (uint32_t g = 0; g < G; ++g) fprintf(stderr, " g%u=0x%x", g, hp[g].pxm);
+        fprintf(stderr, " | key %p rec %p %p bitsp %p %p pbar %p stream %p\n", (void*)e->d_pk_key[0], (void*)e->d_pk_scratch, (void*)e->d_pk_rec1,
+                (void*)e->d_pk_bitsp[0], (void*)e->d_pk_bitsp[1], (void*)e->d_pk_pbar, (void*)e->stream);
+    }
+    if (e->tn.pair_tune & 0x10000u) {   // every tile's own work per pass inside kp_rounds: who does the chain's barrier wait for?
+        const uint32_t nt = 40u;
+        std::vector<uint4> dg(nt);
+        for (uint32_t g = 0; g < G; ++g) {
+            if (!hp[g].ppass) continue;
+            HIPCHK(e, hipMemcpy(dg.data(), e->d_pk_grec + (size_t)g * e->pk_gstride, nt * sizeof(uint4), hipMemcpyDeviceToHost));
+            fprintf(stderr, "[mm-pair] g%u kp_rounds, cycles from barrier to arrival per tile (passes):", g);
+            for (uint32_t t = 0; t < nt; ++t) if (dg[t].y && dg[t].y != 0xFFFFFFFFu) fprintf(stderr, " t%u=%u(%u)", t, dg[t].x / dg[t].y, dg[t].y);
+            fprintf(stderr, "\n");
+        }
+    }
+    if (e->tn.pair_tune & 0x2000u) {
+        unsigned long long tested = 0, algo = 0;
+        for (uint32_t g = 0; g < G; ++g) { tested += hp[g].tested; algo += hp[g].pairs; }
+        fprintf(stderr, "[mm-pair] predicate tests the kernels physically performed (next[] build, repairs, head scans, LDS-resident walk): %llu = %.2f x the %llu pair evaluations of the reference algorithm\n",
+                tested, algo ? (double)tested / (double)algo : 0.0, algo);
+        std::vector<uint32_t> xc(e->pk_max_tiles);
+        HIPCHK(e, hipMemcpy(xc.data(), e->d_pk_tilectl + ((size_t)TC_DISP * G + 0) * e->pk_max_tiles,
+                            e->pk_max_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        fprintf(stderr, "[mm-pair] g0 XCD of tile 0..47's workgroup at its last round:");
+        for (uint32_t t = 0; t < 48 && t < e->pk_max_tiles; ++t) fprintf(stderr, " %u", xc[t] & 0xFu);
+        fprintf(stderr, "\n");
+    }
+    if (e->tn.pair_tune & 0x2000u)
+        for (uint32_t g = 0; g < G; ++g)
+            if (hp[g].rounds)
+                fprintf(stderr, "[mm-pair] g%u walk loop of tile 1's workgroup: %u iterations, %.0f cycles each (%.0f cycles per timed round)\n",
+                        g, hp[g].tm[15], hp[g].tm[15] ? 16.0 * hp[g].tm[13] / hp[g].tm[15] : 0.0,
+                        16.0 * hp[g].tm[13] / (hp[g].tm[5] ? hp[g].tm[5] : 1u));
+    if (e->tn.pair_tune & 0x2000u)
+        fprintf(stderr, "[mm-pair] g0 walk: cycles in iterations 1-4 per round %.0f, in the later ones %.0f\n",
+                16.0 * hp[0].tm[12] / (hp[0].tm[5] ? hp[0].tm[5] : 1u), 16.0 * hp[0].tm[14] / (hp[0].tm[5] ? hp[0].tm[5] : 1u));
+    return MM_OK;
+}
+
+// mm_path_stats_get after a tick of the pair path: the chain with the most passes, by launch shape
+static void path_stats_pair(mm_engine* e, uint32_t mode)
+{
+    const uint32_t G = e->cfg.n_groups;
+    // ... among the chains the pair path walked: one k_walk took (PairChain.fast == 0: a rating span beyond the packed key)
+    // has no launch shapes to report, and its passes counted as kp_late's would price them as LDS steps
+    uint32_t gc = 0xFFFFFFFFu;
+    for (uint32_t g = 0; g < G; ++g)
+        if (e->h_pchains[g].fast && (gc == 0xFFFFFFFFu || e->h_chains[mode * G + g].passes > e->h_chains[mode * G + gc].passes)) gc = g;
+    e->ps.crit_group = gc;
+    if (gc == 0xFFFFFFFFu) gc = 0;            // (none: the zeros of ps_hand say so)
+    const ChainDev& cd = e->h_chains[mode * G + gc];
+    e->ps.crit_passes = e->ps.crit_group == 0xFFFFFFFFu ? 0u : cd.passes;
+    e->ps.crit_rounds_passes = e->ps_hand[2][gc];
+    e->ps.crit_rounds_hops = e->ps_hand[3][gc];
+    e->ps.crit_round_passes = e->ps_hand[0][gc] >= e->ps_hand[2][gc] ? e->ps_hand[0][gc] - e->ps_hand[2][gc] : 0u;
+    e->ps.crit_late_passes = cd.passes >= e->ps_hand[0][gc] ? cd.passes - e->ps_hand[0][gc] : 0u;
+    e->ps.crit_late_lobbies = cd.n_out >= e->ps_hand[1][gc] ? cd.n_out - e->ps_hand[1][gc] : 0u;
+    // the primitives of its serial chain as tile 1's walker timed them (PairChain.ptm), the clock (kp_late's chase in
+    // shader-clock cycles and in 100 MHz ticks), kp_nx_init by HIP events, the physical predicate tests (pair_tune bit 13)
+    const PairChain& pc = e->h_pchains[gc];
+    if (e->ps.crit_group != 0xFFFFFFFFu) {
+        e->ps.crit_timed_passes = pc.ptm[5];
+        e->ps.crit_timed_hops = pc.ptm[15];
+        e->ps.crit_barrier_cycles = pc.ptm[0];
+        e->ps.crit_hop_cycles = pc.ptm[3];
+        e->ps.clk_cycles = pc.dbg[5];
+        e->ps.clk_wall_ticks = pc.dbg[6];
+    }
+    if (e->ev_nx_set) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, e->ev_nx[0], e->ev_nx[1]) == hipSuccess) e->ps.pair_nx_init_ns = (uint32_t)(ms * 1e6f);
+        e->ev_nx_set = false;
+    }
+    if (e->tn.pair_tune & 0x2000u) {
+        unsigned long long t = 0, tn = 0;
+        for (uint32_t g = 0; g < G; ++g) if (e->h_pchains[g].fast) { t += e->h_pchains[g].tested; tn += e->h_pchains[g].tested_nx; }
+        e->ps.pair_tested_lo = (uint32_t)t; e->ps.pair_tested_hi = (uint32_t)(t >> 32);
+        e->ps.pair_tested_nx_lo = (uint32_t)tn; e->ps.pair_tested_nx_hi = (uint32_t)(tn >> 32);
+    }
+}
+
+// ... and of the team path: what its chaser did, by launch shape (TeamChain.cp)
+static void path_stats_team(mm_engine* e)
+{
+    const uint32_t G = e->cfg.n_groups;
+    uint32_t gc = 0xFFFFFFFFu;
+    for (uint32_t g = 0; g < G; ++g)
+        if (e->h_tchains[g].fast && (gc == 0xFFFFFFFFu || e->h_tchains[g].passes > e->h_tchains[gc].passes)) gc = g;
+    if (gc != 0xFFFFFFFFu) {
+        const TeamChain& t = e->h_tchains[gc];
+        e->ps.crit_team_group = gc;
+        e->ps.crit_team_passes = t.passes;
+        e->ps.crit_team_f_passes = t.cp[0]; e->ps.crit_team_fc_passes = t.cp[1]; e->ps.crit_team_late_passes = t.cp[2];
+        e->ps.crit_team_f_lobbies = t.cp[3]; e->ps.crit_team_fc_lobbies = t.cp[4]; e->ps.crit_team_late_lobbies = t.cp[5];
+        e->ps.crit_team_lookups = t.cp[6]; e->ps.crit_team_late_lookups = t.cp[7];
+    }
+}
+
+// The tick's lobbies as k_pack_results and k_wait_matched address them: group g's at its prefix (h_chains holds the tick's counts).
+static PackArgs pack_args(const mm_engine* e, uint32_t mode, uint32_t L, uint32_t total)
+{
+    const uint32_t G = e->cfg.n_groups;
+    PackArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_groups = G; A.L = L; A.total = total; A.out_slot_stride = e->out_slot_stride; A.out_rec_stride = e->out_rec_stride;
+    for (uint32_t g = 0; g < G; ++g) A.pre[g + 1u] = A.pre[g] + e->h_chains[mode * G + g].n_out;
+    return A;
 }
 
 static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats* stats);
@@ -3023,14 +2813,7 @@ extern "C" int mm_tick(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stat
     if (!e || mode >= e->cfg.n_modes) return MM_ERR_INVALID_ARG;
     if (e->poisoned) return MM_ERR_STATE;
     ON_ENGINE_DEVICE(e);
-    int rc;
-    try {
-        rc = tick_impl(e, mode, n_matches, stats);
-    } catch (const std::bad_alloc&) {
-        rc = MM_ERR_OOM;
-    } catch (...) {
-        rc = MM_ERR_INTERNAL;
-    }
+    const int rc = guarded([&]() -> int { return tick_impl(e, mode, n_matches, stats); });
     if (rc != MM_OK) {
         // whatever was enqueued on the stream finishes before the caller sees the error; the queues
         // and lobbies are then in an unspecified (mid-tick) state: mm_reset or mm_restore before
@@ -3072,43 +2855,25 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
         HIPCHK(e, hipGetLastError());
     }
     if (timing) HIPCHK(e, hipEventRecord(e->ev[1], e->stream));
-    const bool use_pair = M.team_size == 1u && M.teams == 2u && !e->force_generic;
+    const bool use_pair = M.team_size == 1u && M.teams == 2u && !e->tn.force_generic;
     if (use_pair) {
         RoctxRange rr("mm_tick/pair walk");
         e->ps.paths |= MM_PATH_PAIR;
-        int prc = pair_walk(e, mode, M, purge);
-        if (prc) return prc;
+        MMTRY(pair_walk(e, mode, M, purge));
     }
     // team modes: long chains take the team path
     bool team_any = false;
-    if (!use_pair && !e->force_generic && e->live_upper >= TT_MIN) {
+    if (!use_pair && !e->tn.force_generic && e->live_upper >= TT_MIN) {
         RoctxRange rr("mm_tick/team walk");
-        int trc = team_walk(e, mode, M, purge, &team_any);
-        if (trc) return trc;
+        MMTRY(team_walk(e, mode, M, purge, &team_any));
         if (team_any) e->ps.paths |= MM_PATH_TEAM;
     }
     if (!e->ps.paths) e->ps.paths = MM_PATH_GENERIC;        // (k_walk also takes the short chains the other two leave: not recorded)
     WalkParams P;
-    memset(&P, 0, sizeof(P));
-    P.mode = mode;
-    P.n_groups = G;
-    P.capacity = cfg.capacity;
-    P.purge = purge ? 1u : 0u;
+    walk_params_common(P, e, mode, purge);
     P.out_cap = (cfg.capacity + MM_MAX_LOBBY) / M.L + 1u;   // lobbies a group can emit at most
-    P.out_slot_stride = e->out_slot_stride;
-    P.out_rec_stride = e->out_rec_stride;
     P.max_passes = 0x7FFFFFFFu;
     P.M = M;
-    P.chains = e->d_chains;
-    P.q_rating = e->d_q_rating;
-    P.q_cons = e->d_q_cons;
-    P.q_slot = e->d_q_slot;
-    P.state = e->d_state;
-    P.released = e->d_released;
-    P.n_released = e->d_counters;
-    P.out_slots = e->d_out_slots;
-    P.out_score = e->d_out_score;
-    P.out_pass = e->d_out_pass;
     P.pskip = use_pair ? e->d_pchains : NULL;
     P.tskip = team_any ? e->d_tchains : NULL;
     hipLaunchKernelGGL(k_walk, dim3(G), dim3(WK_THREADS), 0, e->stream, P);
@@ -3120,70 +2885,7 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
     if (use_pair) HIPCHK(e, hipMemcpyAsync(e->h_pchains, e->d_pchains, G * sizeof(PairChain), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     const double t_copy0 = host_now_ms();
-    if (use_pair && e->pair_debug) {
-        std::vector<PairChain> hp(G);
-        HIPCHK(e, hipMemcpy(hp.data(), e->d_pchains, G * sizeof(PairChain), hipMemcpyDeviceToHost));
-        for (uint32_t g = 0; g < G; ++g)
-            fprintf(stderr, "[mm-pair] g%u fast %u m %u qlen %u passes %u out %u rounds %u (group hops of tile 0: %u of %u entries looked at, %u not of the round) | stale %u inv %u slowsucc %u compact %u fixed(w1) %u | chase clk %u wall(100MHz) %u wrapscan clk %u\n",
-                    g, hp[g].fast, hp[g].m, hp[g].qlen, hp[g].passes, hp[g].n_out, hp[g].rounds, hp[g].ghops, hp[g].gtry, hp[g].gstale, hp[g].dbg[0], hp[g].dbg[1],
-                    hp[g].dbg[2], hp[g].dbg[3], hp[g].dbg[4], hp[g].dbg[5], hp[g].dbg[6], hp[g].dbg[7]);
-        for (uint32_t g = 0; g < G; ++g)
-            if (hp[g].rounds) {
-                const uint32_t nr = hp[g].tm[5] ? hp[g].tm[5] : 1u;
-                fprintf(stderr, "[mm-pair] g%u tile1 cycles/round over %u rounds (load %u walk+stage+sweepA %u apply %u | detect %u items %u long %u (%.1f long items) | graph %u resolve %u publish %u | cand+head %u)\n",
-                        g, nr, hp[g].tm[0] / nr, hp[g].tm[6] / nr, hp[g].tm[9] / nr, hp[g].tm[1] / nr, hp[g].tm[12] / nr, hp[g].tm[2] / nr,
-                        (double)hp[g].tm[11] / nr, hp[g].tm[7] / nr, hp[g].tm[8] / nr, hp[g].tm[10] / nr, hp[g].tm[4] / nr);
-            }
-        for (uint32_t g = 0; g < G; ++g)
-            if (hp[g].ppass) {
-                const uint32_t nr = hp[g].ptm[5] ? hp[g].ptm[5] : 1u;
-                fprintf(stderr, "[mm-pair] g%u kp_rounds: %u passes inside persistent launches (%u launches gave up so far); tile1 cycles/pass over %u passes (barrier %u fast hops %u walk+sweepA %u apply %u | detect %u items %u long %u | graph %u resolve %u publish %u | head+arrive %u) walk loop %.0f cycles, %.1f hops\n",
-                        g, hp[g].ppass, e->pair_pstops, nr, hp[g].ptm[0] / nr, hp[g].ptm[3] / nr, hp[g].ptm[6] / nr, hp[g].ptm[9] / nr, hp[g].ptm[1] / nr,
-                        hp[g].ptm[12] / nr, hp[g].ptm[2] / nr, hp[g].ptm[7] / nr, hp[g].ptm[8] / nr, hp[g].ptm[10] / nr, hp[g].ptm[4] / nr,
-                        16.0 * hp[g].ptm[13] / nr, (double)hp[g].ptm[15] / nr);
-                fprintf(stderr, "[mm-pair] g%u kp_rounds, tile 1's walker off the fast path: %u hops whose partner had left, %.0f cycles each; %u hops without a partner inside the horizon, %.0f cycles each\n",
-                        g, hp[g].pslow[0], hp[g].pslow[0] ? 16.0 * hp[g].pslow[1] / hp[g].pslow[0] : 0.0, hp[g].pslow[2],
-                        hp[g].pslow[2] ? 16.0 * hp[g].pslow[3] / hp[g].pslow[2] : 0.0);
-            }
-        {   // where the last kp_rounds launch ran and where the tables live (run-to-run spread: two modes of the walk, 9.4 / 9.7 ms)
-            fprintf(stderr, "[mm-pair] physical XCD mask of each chain's workgroups in its last kp_rounds launch:");
-            for (uint32_t g = 0; g < G; ++g) fprintf(stderr, " g%u=0x%x", g, hp[g].pxm);
-            fprintf(stderr, " | key %p rec %p %p bitsp %p %p pbar %p stream %p\n", (void*)e->d_pk_key[0], (void*)e->d_pk_scratch, (void*)e->d_pk_rec1,
-                    (void*)e->d_pk_bitsp[0], (void*)e->d_pk_bitsp[1], (void*)e->d_pk_pbar, (void*)e->stream);
-        }
-        if (e->pair_tune & 0x10000u) {   // every tile's own work per pass inside kp_rounds: who does the chain's barrier wait for?
-            const uint32_t nt = 40u;
-            std::vector<uint4> dg(nt);
-            for (uint32_t g = 0; g < G; ++g) {
-                if (!hp[g].ppass) continue;
-                HIPCHK(e, hipMemcpy(dg.data(), e->d_pk_grec + (size_t)g * e->pk_gstride, nt * sizeof(uint4), hipMemcpyDeviceToHost));
-                fprintf(stderr, "[mm-pair] g%u kp_rounds, cycles from barrier to arrival per tile (passes):", g);
-                for (uint32_t t = 0; t < nt; ++t) if (dg[t].y && dg[t].y != 0xFFFFFFFFu) fprintf(stderr, " t%u=%u(%u)", t, dg[t].x / dg[t].y, dg[t].y);
-                fprintf(stderr, "\n");
-            }
-        }
-        if (e->pair_tune & 0x2000u) {
-            unsigned long long tested = 0, algo = 0;
-            for (uint32_t g = 0; g < G; ++g) { tested += hp[g].tested; algo += hp[g].pairs; }
-            fprintf(stderr, "[mm-pair] predicate tests the kernels physically performed (next[] build, repairs, head scans, LDS-resident walk): %llu = %.2f x the %llu pair evaluations of the reference algorithm\n",
-                    tested, algo ? (double)tested / (double)algo : 0.0, algo);
-            std::vector<uint32_t> xc(e->pk_max_tiles);
-            HIPCHK(e, hipMemcpy(xc.data(), e->d_pk_tilectl + ((size_t)TC_DISP * G + 0) * e->pk_max_tiles,
-                                e->pk_max_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[mm-pair] g0 XCD of tile 0..47's workgroup at its last round:");
-            for (uint32_t t = 0; t < 48 && t < e->pk_max_tiles; ++t) fprintf(stderr, " %u", xc[t] & 0xFu);
-            fprintf(stderr, "\n");
-        }
-        if (e->pair_tune & 0x2000u)
-            for (uint32_t g = 0; g < G; ++g)
-                if (hp[g].rounds)
-                    fprintf(stderr, "[mm-pair] g%u walk loop of tile 1's workgroup: %u iterations, %.0f cycles each (%.0f cycles per timed round)\n",
-                            g, hp[g].tm[15], hp[g].tm[15] ? 16.0 * hp[g].tm[13] / hp[g].tm[15] : 0.0,
-                            16.0 * hp[g].tm[13] / (hp[g].tm[5] ? hp[g].tm[5] : 1u));
-        if (e->pair_tune & 0x2000u)
-            fprintf(stderr, "[mm-pair] g0 walk: cycles in iterations 1-4 per round %.0f, in the later ones %.0f\n",
-                    16.0 * hp[0].tm[12] / (hp[0].tm[5] ? hp[0].tm[5] : 1u), 16.0 * hp[0].tm[14] / (hp[0].tm[5] ? hp[0].tm[5] : 1u));
-    }
+    if (use_pair && e->tn.debug) MMTRY(report_pair(e));
 
     uint32_t total = 0, after = 0, before = 0, pmax = 0, errf = 0;
     unsigned long long pairs = 0, scanned = 0;
@@ -3198,7 +2900,7 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
         if (c.passes > pmax) pmax = c.passes;
     }
     if (errf) return MM_ERR_INTERNAL;
-    if (e->fault_tick && ++e->ticks_seen == e->fault_tick) return MM_ERR_INTERNAL;   // test hook: a tick that dies after its walk
+    if (e->tn.fail_tick && ++e->ticks_seen == e->tn.fail_tick) return MM_ERR_INTERNAL;   // test hook: a tick that dies after its walk
     if ((size_t)total * M.L > (size_t)cfg.capacity + (size_t)MM_MAX_LOBBY * G) return MM_ERR_INTERNAL;
     RoctxRange rr_res("mm_tick/match list");
     bool tail_on_main = false;
@@ -3216,10 +2918,8 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
         }
         if (!e->r_based && total > 0u && total <= MM_PACK_MAX) {
             // nothing has left yet and the tick is small: one packed piece, tight layout (group g at its prefix)
-            PackArgs A;
-            memset(&A, 0, sizeof(A));
-            A.n_groups = G; A.L = M.L; A.total = total; A.out_slot_stride = e->out_slot_stride; A.out_rec_stride = e->out_rec_stride;
-            for (uint32_t g = 0; g < G; ++g) { A.pre[g + 1u] = A.pre[g] + no[g]; e->r_base[g] = A.pre[g]; e->r_sent[g] = no[g]; }
+            const PackArgs A = pack_args(e, mode, M.L, total);
+            for (uint32_t g = 0; g < G; ++g) { e->r_base[g] = A.pre[g]; e->r_sent[g] = no[g]; }
             e->r_based = true;
             hipLaunchKernelGGL(k_pack_results, dim3((total + 255u) / 256u), dim3(256), 0, e->stream, A, e->d_out_slots, e->d_out_score,
                                e->d_out_pass, e->d_pack);
@@ -3230,8 +2930,7 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
             tail_on_main = true;
         } else {
             if (!e->r_based) results_set_bases(e, bf, M.L);
-            int src = results_send(e, no, M.L, 1u, &tail_on_main);
-            if (src) return src;
+            MMTRY(results_send(e, no, M.L, 1u, &tail_on_main));
         }
     }
     const uint32_t nrel = e->h_counters[0];
@@ -3242,10 +2941,7 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
         // mm_matches_wait: the waits of the matched, while their stamps are still theirs (the emission logs are final:
         // the stream was synchronised above).  Queued BEHIND the match list's tail, so the list reaches the host as early
         // as without the clock; the copy goes into pinned memory and is covered by this tick's last synchronisation
-        PackArgs A;
-        memset(&A, 0, sizeof(A));
-        A.n_groups = G; A.L = M.L; A.total = total; A.out_slot_stride = e->out_slot_stride; A.out_rec_stride = e->out_rec_stride;
-        for (uint32_t g = 0; g < G; ++g) A.pre[g + 1u] = A.pre[g] + e->h_chains[mode * G + g].n_out;
+        const PackArgs A = pack_args(e, mode, M.L, total);
         const uint32_t words = total * M.L;
         hipLaunchKernelGGL(k_wait_matched, dim3((words + 255u) / 256u), dim3(256), 0, e->stream, A, e->d_out_slots, e->d_stamp,
                            cfg.capacity, e->clock_now, e->d_wt_matched);
@@ -3253,8 +2949,7 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
         HIPCHK(e, hipMemcpyAsync(e->h_mwait, e->d_wt_matched, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     }
     {
-        int src = results_absorb(e, M.L);
-        if (src) return src;
+        MMTRY(results_absorb(e, M.L));
     }
     e->r_pre[0] = 0;
     for (uint32_t g = 0; g < G; ++g) {
@@ -3275,58 +2970,9 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
     e->r_n = total;
     e->mw_n = e->clock_on ? total : 0u;
     if (n_matches) *n_matches = total;
-    if (e->ps.paths & MM_PATH_PAIR) {            // mm_path_stats_get: the chain with the most passes, by launch shape
-        // ... among the chains the pair path walked: one k_walk took (PairChain.fast == 0: a rating span beyond the packed key)
-        // has no launch shapes to report, and its passes counted as kp_late's would price them as LDS steps
-        uint32_t gc = 0xFFFFFFFFu;
-        for (uint32_t g = 0; g < G; ++g)
-            if (e->h_pchains[g].fast && (gc == 0xFFFFFFFFu || e->h_chains[mode * G + g].passes > e->h_chains[mode * G + gc].passes)) gc = g;
-        e->ps.crit_group = gc;
-        if (gc == 0xFFFFFFFFu) gc = 0;            // (none: the zeros of ps_hand say so)
-        const ChainDev& cd = e->h_chains[mode * G + gc];
-        e->ps.crit_passes = e->ps.crit_group == 0xFFFFFFFFu ? 0u : cd.passes;
-        e->ps.crit_rounds_passes = e->ps_hand[2][gc];
-        e->ps.crit_rounds_hops = e->ps_hand[3][gc];
-        e->ps.crit_round_passes = e->ps_hand[0][gc] >= e->ps_hand[2][gc] ? e->ps_hand[0][gc] - e->ps_hand[2][gc] : 0u;
-        e->ps.crit_late_passes = cd.passes >= e->ps_hand[0][gc] ? cd.passes - e->ps_hand[0][gc] : 0u;
-        e->ps.crit_late_lobbies = cd.n_out >= e->ps_hand[1][gc] ? cd.n_out - e->ps_hand[1][gc] : 0u;
-        // the primitives of its serial chain as tile 1's walker timed them (PairChain.ptm), the clock (kp_late's chase in
-        // shader-clock cycles and in 100 MHz ticks), kp_nx_init by HIP events, the physical predicate tests (pair_tune bit 13)
-        const PairChain& pc = e->h_pchains[gc];
-        if (e->ps.crit_group != 0xFFFFFFFFu) {
-            e->ps.crit_timed_passes = pc.ptm[5];
-            e->ps.crit_timed_hops = pc.ptm[15];
-            e->ps.crit_barrier_cycles = pc.ptm[0];
-            e->ps.crit_hop_cycles = pc.ptm[3];
-            e->ps.clk_cycles = pc.dbg[5];
-            e->ps.clk_wall_ticks = pc.dbg[6];
-        }
-        if (e->ev_nx_set) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, e->ev_nx[0], e->ev_nx[1]) == hipSuccess) e->ps.pair_nx_init_ns = (uint32_t)(ms * 1e6f);
-            e->ev_nx_set = false;
-        }
-        if (e->pair_tune & 0x2000u) {
-            unsigned long long t = 0, tn = 0;
-            for (uint32_t g = 0; g < G; ++g) if (e->h_pchains[g].fast) { t += e->h_pchains[g].tested; tn += e->h_pchains[g].tested_nx; }
-            e->ps.pair_tested_lo = (uint32_t)t; e->ps.pair_tested_hi = (uint32_t)(t >> 32);
-            e->ps.pair_tested_nx_lo = (uint32_t)tn; e->ps.pair_tested_nx_hi = (uint32_t)(tn >> 32);
-        }
-    }
+    if (e->ps.paths & MM_PATH_PAIR) path_stats_pair(e, mode);
     e->ps.crit_team_group = 0xFFFFFFFFu;
-    if (e->ps.paths & MM_PATH_TEAM) {            // ... and the team path's: what its chaser did, by launch shape (TeamChain.cp)
-        uint32_t gc = 0xFFFFFFFFu;
-        for (uint32_t g = 0; g < G; ++g)
-            if (e->h_tchains[g].fast && (gc == 0xFFFFFFFFu || e->h_tchains[g].passes > e->h_tchains[gc].passes)) gc = g;
-        if (gc != 0xFFFFFFFFu) {
-            const TeamChain& t = e->h_tchains[gc];
-            e->ps.crit_team_group = gc;
-            e->ps.crit_team_passes = t.passes;
-            e->ps.crit_team_f_passes = t.cp[0]; e->ps.crit_team_fc_passes = t.cp[1]; e->ps.crit_team_late_passes = t.cp[2];
-            e->ps.crit_team_f_lobbies = t.cp[3]; e->ps.crit_team_fc_lobbies = t.cp[4]; e->ps.crit_team_late_lobbies = t.cp[5];
-            e->ps.crit_team_lookups = t.cp[6]; e->ps.crit_team_late_lookups = t.cp[7];
-        }
-    }
+    if (e->ps.paths & MM_PATH_TEAM) path_stats_team(e);
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         stats->pool_before = before;
@@ -3351,7 +2997,7 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
 extern "C" int mm_matches(mm_engine* e, uint32_t first, uint32_t count, uint32_t* slots, float* score,
                           uint32_t* group, uint32_t* pass)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e) return MM_ERR_INVALID_ARG;
         if (first > e->r_n || count > e->r_n - first) return MM_ERR_RANGE;
         if (count == 0) return MM_OK;
@@ -3370,11 +3016,7 @@ extern "C" int mm_matches(mm_engine* e, uint32_t first, uint32_t count, uint32_t
             if (group) std::fill_n(group + dst, n, g);
         }
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 static int fetch_chains(mm_engine* e)
@@ -3386,27 +3028,21 @@ static int fetch_chains(mm_engine* e)
 
 extern "C" int mm_queue_depth(mm_engine* e, uint32_t mode, uint32_t* per_group)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e || !per_group || mode >= e->cfg.n_modes) return MM_ERR_INVALID_ARG;
         ON_ENGINE_DEVICE(e);
-        int rc = fetch_chains(e);
-        if (rc) return rc;
+        MMTRY(fetch_chains(e));
         for (uint32_t g = 0; g < e->cfg.n_groups; ++g) per_group[g] = e->h_chains[mode * e->cfg.n_groups + g].len;
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int mm_queue_slots(mm_engine* e, uint32_t mode, uint32_t group, uint32_t* n, uint32_t* slots)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e || !n || mode >= e->cfg.n_modes || group >= e->cfg.n_groups) return MM_ERR_INVALID_ARG;
         ON_ENGINE_DEVICE(e);
-        int rc = fetch_chains(e);
-        if (rc) return rc;
+        MMTRY(fetch_chains(e));
         const uint32_t c = mode * e->cfg.n_groups + group;
         const uint32_t len = e->h_chains[c].len;
         const uint32_t k = len < *n ? len : *n;
@@ -3418,21 +3054,16 @@ extern "C" int mm_queue_slots(mm_engine* e, uint32_t mode, uint32_t group, uint3
             HIPCHK(e, hipStreamSynchronize(e->stream));
         }
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int mm_lobby_state(mm_engine* e, uint32_t mode, uint32_t group, uint32_t* n, uint32_t* slots,
                               uint8_t* teams)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e || !n || mode >= e->cfg.n_modes || group >= e->cfg.n_groups) return MM_ERR_INVALID_ARG;
         ON_ENGINE_DEVICE(e);
-        int rc = fetch_chains(e);
-        if (rc) return rc;
+        MMTRY(fetch_chains(e));
         const LobbyDev& lb = e->h_chains[mode * e->cfg.n_groups + group].lobby;
         uint32_t k = 0;
         for (uint32_t t = 0; t < e->cfg.modes[mode].teams; ++t)
@@ -3443,11 +3074,7 @@ extern "C" int mm_lobby_state(mm_engine* e, uint32_t mode, uint32_t group, uint3
             }
         *n = k;
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------
@@ -3491,32 +3118,26 @@ static unsigned long long snap_cfg_hash(const mm_config& c)
 
 extern "C" int mm_snapshot_size(mm_engine* e, uint64_t* bytes)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e || !bytes) return MM_ERR_INVALID_ARG;
         ON_ENGINE_DEVICE(e);
-        int rc = fetch_chains(e);
-        if (rc) return rc;
+        MMTRY(fetch_chains(e));
         uint64_t n = sizeof(SnapHeader) + e->cfg.capacity + (uint64_t)e->n_chains * sizeof(ChainDev);
         for (uint32_t c = 0; c < e->n_chains; ++c) n += (uint64_t)e->h_chains[c].len * 12u;
         if (e->clock_on) n += 4u + (uint64_t)e->cfg.capacity * 4u;   // version 2: the clock and the stamps behind the v1 payload
         *bytes = n;
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int mm_snapshot(mm_engine* e, void* buf, uint64_t cap, uint64_t* written)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e || !buf || !written) return MM_ERR_INVALID_ARG;
         if (e->poisoned) return MM_ERR_STATE;                 // a mid-tick pool is not a pool worth keeping
         ON_ENGINE_DEVICE(e);
         uint64_t need = 0;
-        int rc = mm_snapshot_size(e, &need);                  // also refreshes h_chains
-        if (rc) return rc;
+        MMTRY(mm_snapshot_size(e, &need));                  // also refreshes h_chains
         if (cap < need) return MM_ERR_RANGE;
         unsigned char* out = (unsigned char*)buf;
         SnapHeader h;
@@ -3559,16 +3180,12 @@ extern "C" int mm_snapshot(mm_engine* e, void* buf, uint64_t cap, uint64_t* writ
         memcpy(out, &h, sizeof(h));
         *written = need;
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int mm_restore(mm_engine* e, const void* buf, uint64_t bytes)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e || !buf || bytes < sizeof(SnapHeader)) return MM_ERR_INVALID_ARG;
         ON_ENGINE_DEVICE(e);
         const unsigned char* in = (const unsigned char*)buf;
@@ -3593,12 +3210,10 @@ extern "C" int mm_restore(mm_engine* e, const void* buf, uint64_t bytes)
         }
         if (h.version == 2u) need += 4u + (uint64_t)h.capacity * 4u;
         if (need != bytes) return MM_ERR_INVALID_ARG;
-        int rc = mm_reset(e);
-        if (rc) return rc;
+        MMTRY(mm_reset(e));
         e->clock_on = false;                                 // a version-1 snapshot has no clock: the feature is off again
         if (h.version == 2u) {
-            rc = wait_alloc(e);
-            if (rc) return rc;
+            MMTRY(wait_alloc(e));
         }
         memcpy(e->h_state.data(), in + sizeof(SnapHeader), h.capacity);
         HIPCHK(e, hipMemcpyAsync(e->d_state, e->h_state.data(), h.capacity, hipMemcpyHostToDevice, e->stream));
@@ -3630,11 +3245,7 @@ extern "C" int mm_restore(mm_engine* e, const void* buf, uint64_t bytes)
         e->cancel_pending = h.cancel_pending;
         e->live_upper = h.live_upper;
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------
@@ -3643,23 +3254,26 @@ extern "C" int mm_restore(mm_engine* e, const void* buf, uint64_t bytes)
 static_assert(sizeof(WaitGroupDev) == sizeof(mm_wait_group) && offsetof(WaitGroupDev, age_sum) == offsetof(mm_wait_group, age_sum) &&
               offsetof(WaitGroupDev, hist) == offsetof(mm_wait_group, hist) && MM_WAIT_HIST == 33u, "WaitGroupDev is mm_wait_group");
 
-// The device arrays of the feature, at the first mm_clock_set (or a version-2 mm_restore).
+// The device arrays of the feature, at the first mm_clock_set (or a version-2 mm_restore): all six, or none.
 static int wait_alloc(mm_engine* e)
 {
     if (e->d_stamp) return MM_OK;
-    (void)hipFree(e->d_wt_rows); (void)hipFree(e->d_wt_out); (void)hipFree(e->d_wt_stats); (void)hipFree(e->d_wt_matched);   // (an earlier attempt that ran out of memory)
-    if (e->h_mwait) (void)hipHostFree(e->h_mwait);
-    e->d_wt_rows = NULL; e->d_wt_out = NULL; e->d_wt_stats = NULL; e->d_wt_matched = NULL; e->h_mwait = NULL;
     const size_t cap = e->cfg.capacity;
     // the queues of one mode hold at most `capacity` players between them: sum of ceil(len / WT_CHUNK) <= capacity / WT_CHUNK + groups
     e->wt_max_chunks = (uint32_t)(cap / WT_CHUNK + e->cfg.n_groups + 1u);
-    HIPCHK(e, hipMalloc((void**)&e->d_wt_rows, ((size_t)e->wt_max_chunks * WT_ROWS + 1u) * sizeof(uint32_t)));
-    HIPCHK(e, hipMalloc((void**)&e->d_wt_out, 3u * cap * sizeof(uint32_t)));
-    HIPCHK(e, hipMalloc((void**)&e->d_wt_stats, MM_MAX_GROUPS * sizeof(WaitGroupDev)));
-    HIPCHK(e, hipMalloc((void**)&e->d_wt_matched, (cap + (size_t)MM_MAX_LOBBY * MM_MAX_GROUPS + 64u) * sizeof(uint32_t)));
-    HIPCHK(e, hipHostMalloc((void**)&e->h_mwait, (cap + (size_t)MM_MAX_LOBBY * MM_MAX_GROUPS + 64u) * sizeof(uint32_t), hipHostMallocDefault));
-    HIPCHK(e, hipMalloc((void**)&e->d_stamp, cap * sizeof(uint32_t)));   // last: its presence says all of them are there
-    return MM_OK;
+    const int rc = guarded([&]() -> int {          // (also a bad_alloc of the registry ends in the clean-up below)
+        MMTRY(dev_alloc(e, e->d_wt_rows, ((size_t)e->wt_max_chunks * WT_ROWS + 1u) * sizeof(uint32_t)));
+        MMTRY(dev_alloc(e, e->d_wt_out, 3u * cap * sizeof(uint32_t)));
+        MMTRY(dev_alloc(e, e->d_wt_stats, MM_MAX_GROUPS * sizeof(WaitGroupDev)));
+        MMTRY(dev_alloc(e, e->d_wt_matched, (cap + (size_t)MM_MAX_LOBBY * MM_MAX_GROUPS + 64u) * sizeof(uint32_t)));
+        MMTRY(pin_alloc(e, e->h_mwait, (cap + (size_t)MM_MAX_LOBBY * MM_MAX_GROUPS + 64u) * sizeof(uint32_t)));
+        return dev_alloc(e, e->d_stamp, cap * sizeof(uint32_t));   // last: its presence says all of them are there
+    });
+    if (rc) {                                      // (out of memory half way: the next attempt starts from nothing)
+        mem_release(e, e->d_wt_rows); mem_release(e, e->d_wt_out); mem_release(e, e->d_wt_stats);
+        mem_release(e, e->d_wt_matched); mem_release(e, e->h_mwait); mem_release(e, e->d_stamp);
+    }
+    return rc;
 }
 
 static WaitParams wait_params(const mm_engine* e, uint32_t mode, uint32_t max_age)
@@ -3695,7 +3309,7 @@ static uint32_t wait_grid(const mm_engine* e)
 
 extern "C" int mm_clock_set(mm_engine* e, uint32_t now)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e) return MM_ERR_INVALID_ARG;
         if (e->poisoned) return MM_ERR_STATE;
         if (e->clock_on) {
@@ -3704,8 +3318,7 @@ extern "C" int mm_clock_set(mm_engine* e, uint32_t now)
             return MM_OK;
         }
         ON_ENGINE_DEVICE(e);
-        int rc = wait_alloc(e);
-        if (rc) return rc;
+        MMTRY(wait_alloc(e));
         // whoever waits already has waited since now (a slot nobody holds gets its stamp when it is handed out)
         const uint32_t cap = e->cfg.capacity;
         hipLaunchKernelGGL(k_wait_fill, dim3((cap + WT_THREADS - 1u) / WT_THREADS), dim3(WT_THREADS), 0, e->stream, cap, e->d_stamp, now);
@@ -3714,11 +3327,7 @@ extern "C" int mm_clock_set(mm_engine* e, uint32_t now)
         e->clock_now = now;
         e->clock_on = true;
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int mm_clock_get(const mm_engine* e, uint32_t* now, uint32_t* enabled)
@@ -3774,14 +3383,7 @@ extern "C" int mm_expire(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t
     e->x_slot.clear(); e->x_group.clear(); e->x_age.clear();
     if (n_expired) *n_expired = 0;
     bool marked_on_device = false;
-    int rc;
-    try {
-        rc = expire_impl(e, mode, max_age, n_expired, &marked_on_device);
-    } catch (const std::bad_alloc&) {
-        rc = MM_ERR_OOM;
-    } catch (...) {
-        rc = MM_ERR_INTERNAL;
-    }
+    const int rc = guarded([&]() -> int { return expire_impl(e, mode, max_age, n_expired, &marked_on_device); });
     if (rc != MM_OK) {
         // no half-filled list for mm_expired; and once the marks may be on the device while h_state and cancel_pending do
         // not have them, the pool is as undefined as after a tick that failed half way: mm_reset or mm_restore (mm_engine.h)
@@ -3810,7 +3412,7 @@ extern "C" int mm_expired(mm_engine* e, uint32_t first, uint32_t count, uint32_t
 
 extern "C" int mm_wait_stats(mm_engine* e, uint32_t mode, mm_wait_group* per_group)
 {
-    try {
+    return guarded([&]() -> int {
         if (!e || !per_group || mode >= e->cfg.n_modes) return MM_ERR_INVALID_ARG;
         if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
         ON_ENGINE_DEVICE(e);
@@ -3823,11 +3425,7 @@ extern "C" int mm_wait_stats(mm_engine* e, uint32_t mode, mm_wait_group* per_gro
         HIPCHK(e, hipMemcpyAsync(per_group, e->d_wt_stats, G * sizeof(mm_wait_group), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(e, hipStreamSynchronize(e->stream));
         return MM_OK;
-    } catch (const std::bad_alloc&) {
-        return MM_ERR_OOM;
-    } catch (...) {
-        return MM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int mm_matches_wait(mm_engine* e, uint32_t first, uint32_t count, uint32_t* wait)
@@ -3847,7 +3445,7 @@ extern "C" int mm_path_stats_get(mm_engine* e, mm_path_stats* out)
 {
     if (!e || !out || out->size < 2u * sizeof(uint32_t)) return MM_ERR_INVALID_ARG;
     mm_path_stats ps = e->ps;
-    ps.pair_persist_off = e->pair_persist ? 0u : 1u;
+    ps.pair_persist_off = kp_rounds_on(e) ? 0u : 1u;
     ps.pair_cooldown = e->pair_pcool;
     ps.pair_stops_total = e->pair_pstops;
     const uint32_t n = out->size < (uint32_t)sizeof(ps) ? out->size : (uint32_t)sizeof(ps);

@@ -1,0 +1,269 @@
+// mm_wait.inc — the clock of include/mm_wait.h on the device: expiry selection as a stable stream compaction over a
+// mode's queues, wait statistics.  Included by mm_engine.hip (ChainDev, LobbyDev, dev_min_u32, wave_incl_scan, the WT_* chunk geometry); the host
+// functions that launch these kernels (wait_alloc .. mm_wait_stats) are there, like the pair and team host loops.
+// k_wait_matched sits beside k_pack_results in mm_engine.hip, whose PackArgs it shares.  DESIGN.md §4.6.
+//
+// The waiting players of a mode are walked in ONE order by every kernel here — rating group ascending; within a group
+// the stored lobby's seats as mm_lobby_state lists them, then the queue from head to tail — cut into chunks of WT_CHUNK
+// queue entries, one workgroup per chunk (a chain of 300 000 players is 147 workgroups, not k_purge's one).  A group
+// has at least one chunk: an empty queue may still have a stored lobby, and the group's first chunk carries its seats.
+// mm_expire is count / scan / scatter over that order, the shape of k_bucket_*: per-wave counts, one exclusive scan
+// down the (chunk, wave) rows, then every wave writes its selected entries at base + wave-ballot rank — a stable
+// compaction, so the list is in queue order.  Per entry: q_slot streamed, stamp[slot] and state[slot] gathered.
+// This file is not self-contained: it needs six macros defined BEFORE its #include, which mm_engine.hip does right in front
+// of it — WT_THREADS, WT_WAVES, WT_PER_WAVE, WT_CHUNK, WT_ROWS, WT_SEATS, the chunk geometry of every kernel below.  They
+// live there because the host code sizes its buffers and grids by them (wait_alloc, wait_grid) and because the tests read
+// WT_CHUNK out of mm_engine.hip (tests/geometry.py's SOURCES, tests/wait_scenarios.py: chains of WT_CHUNK - 1 / + 1
+// players); a test suite that predates this file must find it where it always was.
+#if !defined(WT_THREADS) || !defined(WT_WAVES) || !defined(WT_PER_WAVE) || !defined(WT_CHUNK) || !defined(WT_ROWS) || !defined(WT_SEATS)
+#error "mm_wait.inc: define the WT_* chunk geometry before including this file (mm_engine.hip does)"
+#endif
+
+struct WaitGroupDev {                         // mm_wait_group (include/mm_wait.h) with a type atomicAdd takes
+    uint32_t waiting, oldest_age;
+    unsigned long long age_sum;
+    uint32_t hist[33];
+    uint32_t pad;
+};
+
+struct WaitParams {
+    uint32_t mode, n_groups, capacity, teams;
+    uint32_t now, max_age;
+    uint32_t max_chunks;                      // chunks `rows` has room for
+    const ChainDev* chains;
+    const uint32_t* q_slot;
+    const uint32_t* stamp;
+    uint8_t* state;
+    uint32_t* rows;                           // [chunk][WT_ROWS]; behind them the total ([max_chunks * WT_ROWS])
+    uint32_t* out_slot;                       // the expired, in order: slot | rating group | age
+    uint32_t* out_group;
+    uint32_t* out_age;
+    WaitGroupDev* stats;                      // [n_groups], zeroed by the host
+};
+
+static __device__ __forceinline__ uint32_t wait_chunks_of(uint32_t len) { return len ? (len + WT_CHUNK - 1u) / WT_CHUNK : 1u; }
+
+// Chunk b of the mode -> its rating group, the chunk's number inside the group and the queue's length.  false: past the
+// last chunk.  The same for every thread of a workgroup.
+static __device__ __forceinline__ bool wait_chunk(const WaitParams& P, uint32_t b, uint32_t& g, uint32_t& k, uint32_t& len)
+{
+    if (b >= P.max_chunks) return false;
+    uint32_t base = 0;
+    for (g = 0; g < P.n_groups; ++g) {
+        len = dev_min_u32(P.chains[P.mode * P.n_groups + g].len, P.capacity);
+        const uint32_t nb = wait_chunks_of(len);
+        if (b < base + nb) { k = b - base; return true; }
+        base += nb;
+    }
+    return false;
+}
+
+// The idx-th seated player of a stored lobby in mm_lobby_state's order (team by team), MM_NO_SLOT past the last.
+static __device__ __forceinline__ uint32_t wait_seat(const LobbyDev& lb, uint32_t teams, uint32_t idx)
+{
+    for (uint32_t t = 0; t < teams && t < MM_MAX_TEAMS; ++t) {
+        const uint32_t c = dev_min_u32(lb.cnt[t], 8u);
+        if (idx < c) return lb.slot[t][idx];
+        idx -= c;
+    }
+    return MM_NO_SLOT;
+}
+
+// Is the player in `sl` waiting (LIVE: not cancelled, not expired before), and for how long?
+static __device__ __forceinline__ bool wait_age(const WaitParams& P, uint32_t sl, uint32_t& age)
+{
+    if (sl >= P.capacity || P.state[sl] != MM_ST_LIVE) return false;
+    age = P.now - P.stamp[sl];
+    return true;
+}
+
+// A wave's WT_PER_WAVE queue entries from w0 on: the slots, then their ages — every load of a level issued before the
+// first one is used (the gathers are latency, not bandwidth).  Bit r of the result: this lane's entry r is waiting.
+#define WT_ITERS (WT_PER_WAVE / 64)
+static __device__ __forceinline__ uint32_t wait_load(const WaitParams& P, size_t qo, uint32_t w0, uint32_t len, int lane,
+                                                     uint32_t (&sl)[WT_ITERS], uint32_t (&age)[WT_ITERS])
+{
+    uint32_t live = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < WT_ITERS; ++r) {
+        const uint32_t i = w0 + r * 64 + lane;
+        sl[r] = i < len ? P.q_slot[qo + i] : MM_NO_SLOT;
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < WT_ITERS; ++r) {
+        age[r] = 0;
+        if (wait_age(P, sl[r], age[r])) live |= 1u << r;
+    }
+    return live;
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_wait_fill(uint32_t n, uint32_t* __restrict__ stamp, uint32_t now)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) stamp[i] = now;
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_wait_count(WaitParams P)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        uint32_t cnt = 0;
+        if (w0 < len) {
+            uint32_t sl[WT_ITERS], age[WT_ITERS];
+            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r)
+                cnt += (uint32_t)__popcll(__ballot(((live >> r) & 1u) && age[r] > P.max_age));
+        }
+        if (lane == 0) P.rows[(size_t)b * WT_ROWS + 1u + wave] = cnt;
+        if (wave == 0) {
+            uint32_t age = 0;
+            const bool sel = k == 0u && (uint32_t)lane < WT_SEATS &&
+                             wait_age(P, wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane), age) && age > P.max_age;
+            const unsigned long long m = __ballot(sel);
+            if (lane == 0) P.rows[(size_t)b * WT_ROWS] = (uint32_t)__popcll(m);
+        }
+    }
+}
+
+// Exclusive scan down the rows of k_wait_count, in place; the total behind them.  One workgroup.
+__global__ __launch_bounds__(WT_THREADS) void k_wait_scan(WaitParams P)
+{
+    __shared__ uint32_t wtot[WT_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t chunks = 0;
+    for (uint32_t g = 0; g < P.n_groups; ++g) chunks += wait_chunks_of(dev_min_u32(P.chains[P.mode * P.n_groups + g].len, P.capacity));
+    chunks = dev_min_u32(chunks, P.max_chunks);
+    const uint32_t n_rows = chunks * WT_ROWS;
+    const uint32_t per = (n_rows + WT_THREADS - 1) / WT_THREADS;
+    const uint32_t r0 = dev_min_u32(tid * per, n_rows), r1 = dev_min_u32(r0 + per, n_rows);
+    uint32_t s = 0;
+    for (uint32_t r = r0; r < r1; ++r) s += P.rows[r];
+    const uint32_t incl = wave_incl_scan(s, lane);
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    uint32_t run = incl - s;
+    for (int w = 0; w < wave; ++w) run += wtot[w];
+    for (uint32_t r = r0; r < r1; ++r) {
+        const uint32_t h = P.rows[r];
+        P.rows[r] = run;
+        run += h;
+    }
+    if (tid == 0) {
+        uint32_t total = 0;
+        for (int w = 0; w < WT_WAVES; ++w) total += wtot[w];
+        P.rows[(size_t)P.max_chunks * WT_ROWS] = total;
+    }
+}
+
+// Every selected player at its rank, and marked as k_cancel marks a slot.  A slot is in one queue or one lobby, once:
+// the mark a thread sets is read by nobody else, so the selection is the one k_wait_count counted.
+__global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        uint32_t base = P.rows[(size_t)b * WT_ROWS + 1u + wave];
+        if (w0 < len) {
+            uint32_t sl[WT_ITERS], age[WT_ITERS];
+            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) {
+                const bool sel = ((live >> r) & 1u) && age[r] > P.max_age;
+                const unsigned long long m = __ballot(sel);
+                const uint32_t at = base + (uint32_t)__popcll(m & lt);
+                if (sel && at < P.capacity) {
+                    P.out_slot[at] = sl[r];
+                    P.out_group[at] = g;
+                    P.out_age[at] = age[r];
+                    P.state[sl[r]] = MM_ST_CANCELLED;
+                }
+                base += (uint32_t)__popcll(m);
+            }
+        }
+        if (wave == 0) {
+            uint32_t age = 0, sl = MM_NO_SLOT;
+            if (k == 0u && (uint32_t)lane < WT_SEATS) sl = wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane);
+            const bool sel = wait_age(P, sl, age) && age > P.max_age;
+            const unsigned long long m = __ballot(sel);
+            const uint32_t at = P.rows[(size_t)b * WT_ROWS] + (uint32_t)__popcll(m & lt);
+            if (sel && at < P.capacity) {
+                P.out_slot[at] = sl;
+                P.out_group[at] = g;
+                P.out_age[at] = age;
+                P.state[sl] = MM_ST_CANCELLED;
+            }
+        }
+    }
+}
+
+static __device__ __forceinline__ uint32_t wait_bucket(uint32_t age) { return age ? 64u - (uint32_t)__clzll((long long)age) : 0u; }
+
+// mm_wait_stats: one streaming pass over the same chunks.  Counts, sums and maxima in registers, reduced per wave; the
+// histogram in LDS; a workgroup merges its chunk into the group's record with one atomic per non-empty field.
+__global__ __launch_bounds__(WT_THREADS) void k_wait_stats(WaitParams P)
+{
+    __shared__ uint32_t s_hist[33];
+    __shared__ uint32_t s_cnt, s_max;
+    __shared__ unsigned long long s_sum;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        if (tid < 33) s_hist[tid] = 0;
+        if (tid == 0) { s_cnt = 0; s_max = 0; s_sum = 0; }
+        __syncthreads();
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        uint32_t cnt = 0, mx = 0;
+        unsigned long long sum = 0;
+        if (wave == 0 && k == 0u && (uint32_t)lane < WT_SEATS) {
+            uint32_t age = 0;
+            if (wait_age(P, wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane), age)) {
+                cnt = 1; mx = age; sum = age;
+                atomicAdd(&s_hist[wait_bucket(age)], 1u);
+            }
+        }
+        if (w0 < len) {
+            uint32_t sl[WT_ITERS], age[WT_ITERS];
+            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r)
+                if ((live >> r) & 1u) {
+                    ++cnt;
+                    mx = age[r] > mx ? age[r] : mx;
+                    sum += age[r];
+                    atomicAdd(&s_hist[wait_bucket(age[r])], 1u);
+                }
+        }
+        for (int d = 32; d >= 1; d >>= 1) {
+            const uint32_t c2 = (uint32_t)__shfl((int)cnt, lane ^ d), m2 = (uint32_t)__shfl((int)mx, lane ^ d);
+            const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)sum, lane ^ d), hi = (uint32_t)__shfl((int)(uint32_t)(sum >> 32), lane ^ d);
+            cnt += c2;
+            mx = m2 > mx ? m2 : mx;
+            sum += ((unsigned long long)hi << 32) | lo;
+        }
+        if (lane == 0 && cnt) {
+            atomicAdd(&s_cnt, cnt);
+            atomicMax(&s_max, mx);
+            atomicAdd(&s_sum, sum);
+        }
+        __syncthreads();
+        WaitGroupDev* const out = P.stats + g;
+        if (tid < 33 && s_hist[tid]) atomicAdd(&out->hist[tid], s_hist[tid]);
+        if (tid == 64 && s_cnt) {
+            atomicAdd(&out->waiting, s_cnt);
+            atomicMax(&out->oldest_age, s_max);
+            atomicAdd(&out->age_sum, s_sum);
+        }
+        __syncthreads();
+    }
+}

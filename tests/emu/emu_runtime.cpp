@@ -204,17 +204,35 @@ hipError_t hipGetDevice(int* d) { *d = t_device; return hipSuccess; }
 extern "C" int emu_current_device(void) { return t_device; }
 extern "C" void emu_set_current_device(int d) { t_device = d; }
 extern "C" int emu_set_device_calls(void) { return g_set_device_calls; }
+/* tests/test_engine_memory.py: the blocks hipMalloc / hipHostMalloc have handed out and not got back, and a host-heap
+   failure on request — the k-th allocation from now answers hipErrorOutOfMemory (0: off) */
+static long g_live_blocks = 0;
+static long g_fail_in = 0;
+extern "C" long emu_live_blocks(void) { return g_live_blocks; }
+extern "C" void emu_fail_alloc_in(long k) { g_fail_in = k; }
+static void* emu_block(size_t n)
+{
+    if (g_fail_in > 0 && --g_fail_in == 0) return NULL;
+    void* p = malloc(n ? n : 1);
+    if (p) __atomic_add_fetch(&g_live_blocks, 1, __ATOMIC_RELAXED);   /* (engines are created from several threads) */
+    return p;
+}
+static void emu_unblock(void* p)
+{
+    if (p) __atomic_sub_fetch(&g_live_blocks, 1, __ATOMIC_RELAXED);
+    free(p);
+}
 hipError_t hipMalloc(void** p, size_t n)
 {
     /* poison so that reads of never-written device memory show up */
-    *p = malloc(n ? n : 1);
+    *p = emu_block(n);
     if (!*p) return hipErrorOutOfMemory;
     memset(*p, 0xA5, n);
     return hipSuccess;
 }
-hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+hipError_t hipFree(void* p) { emu_unblock(p); return hipSuccess; }
+hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = emu_block(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipHostFree(void* p) { emu_unblock(p); return hipSuccess; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memmove(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memmove(d, s, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
