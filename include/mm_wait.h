@@ -1,5 +1,6 @@
 /*
- * mm_wait.h — the engine's clock: arrival stamps, expiry of long-waiting players, wait times.
+ * mm_wait.h — the engine's clock: arrival stamps, expiry of long-waiting players, their move to a
+ * fallback mode, wait times.
  *
  * An extension of include/mm_engine.h (same rules: plain C types, status codes and never an
  * abort, every entry point selects the engine's HIP device itself, MM_ERR_STATE on an engine
@@ -21,8 +22,15 @@
  * calls mm_clock_set allocates nothing for this, launches nothing for this and writes the same
  * snapshot as before.
  *
- * Not here: the NIF binding (native/mm_nif.c; INTEGRATION.md names the calls to add), widening
- * of a waiting player's window, moving an expired player to another mode.
+ * Widening a search is mm_move: after some seconds the owner gives up on the strict queue and the
+ * device puts the player into a looser mode (a wider window, no region filter, "any role"), with
+ * the stamp it had — so ages go on, tiers chain and the wait statistics tell the true wait.
+ *
+ * Not here: the NIF binding (native/mm_nif.c; INTEGRATION.md section 7 names the calls to add);
+ * mm_move across the ranks of a ShardedSearch (chain (A, g) and chain (B, g) may have different
+ * owners: the owner of such a pool moves through mm_expire on one rank and mm_enqueue on the
+ * other, and loses the stamp); matching a waiting player against a wider window INSIDE its own
+ * queue (a new predicate, with no witness in the reference or the oracle).
  */
 #ifndef MM_WAIT_H
 #define MM_WAIT_H
@@ -71,14 +79,45 @@ int mm_clock_get(const mm_engine* e, uint32_t* now, uint32_t* enabled);
  * (lib/models/active_user.ex:57-66) is what each expiry amounts to. */
 int mm_expire(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t* n_expired);
 
-/* Entries [first, first + count) of the last mm_expire's list: the slot, its rating group and
- * the age it had reached.  Order: rating group ascending; within a group the stored lobby's
+/* Entries [first, first + count) of the last mm_expire's or mm_move's list: the slot, its rating
+ * group and the age it had reached.  Order: rating group ascending; within a group the stored lobby's
  * seats in the order mm_lobby_state lists them, then the queue from head to tail — the same on
  * every run, so an owner can publish its "no match found" replies from it.  Readable until the
- * next mm_expire, mm_reset or mm_restore.  Any output pointer may be NULL.
+ * next mm_expire, mm_move, mm_reset or mm_restore.  Any output pointer may be NULL.
  * MM_ERR_RANGE: the range is not inside the list.  Reference: none. */
 int mm_expired(mm_engine* e, uint32_t first, uint32_t count, uint32_t* slots, uint32_t* group,
                uint32_t* age);
+
+/* Moves every waiting player of `from_mode` whose age is greater than max_age into `to_mode`:
+ * exactly the players mm_expire(from_mode, max_age) selects, in exactly its order (mm_expired
+ * reads the list's slot, group and age columns afterwards, as after mm_expire).
+ *   the old slot   is marked as mm_expire marks it: from_mode's next tick drops it, and until then
+ *                  it is held — a move of k players needs k FREE slots beside them;
+ *   the new entry  goes to the tail of chain (to_mode, the same rating group), in list order,
+ *                  behind whoever is queued there, with the old rating and the constraint word
+ *                  ((cons & ~cons_clear) & MM_CONS_USER_MASK & ~0xF) | to_mode, in a new slot taken
+ *                  from the ring exactly as mm_enqueue takes them for a batch of *n_selected;
+ *   the stamp      of the new slot is the old slot's: the player's age goes on.
+ * A player to_mode cannot seat (role >= n_roles or a quota of 0 after cons_clear: mm_enqueue's
+ * rule) is expired only: its new slot is MM_NO_SLOT, it uses up its ring position as a refused row
+ * of mm_enqueue does, and it is counted in *n_refused.  *n_selected, *n_refused may be NULL.
+ * MM_ERR_INVALID_ARG: no such mode, from_mode == to_mode, cons_clear with a bit outside
+ * MM_CONS_USER_MASK or inside the mode nibble.  MM_ERR_STATE: the clock was never set.
+ * MM_ERR_FULL: fewer FREE slots than selected players — all or nothing: nothing is marked, queues,
+ * stamps, the ring position and the list of mm_expired (empty) are as if nobody had been selected.
+ * Any other failure once the first mark may be on the device leaves the engine MM_ERR_STATE until
+ * mm_reset / mm_restore, as for mm_expire.  Nothing of a move is in a snapshot that a pool of
+ * queues, states and stamps does not already hold (versions 1 and 2 are unchanged).
+ * Reference: none (a requeued player goes back to the queue it came from, requeue_player/5,
+ * lib/search/worker.ex:239-248); to the oracle a move is mo_cancel of the old slots plus
+ * mo_enqueue of the same rows. */
+int mm_move(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age,
+            uint32_t cons_clear, uint32_t* n_selected, uint32_t* n_refused);
+
+/* Entries [first, first + count) of the last mm_move's list, fourth column: the new slot, or
+ * MM_NO_SLOT for a refused player.  Range rule and lifetime as mm_expired (after an mm_expire the
+ * column is empty).  Reference: none. */
+int mm_moved(mm_engine* e, uint32_t first, uint32_t count, uint32_t* new_slot);
 
 /* per_group[cfg.n_groups]: who waits in `mode`, per rating group, and for how long.
  * MM_ERR_STATE: the clock was never set.

@@ -235,6 +235,11 @@ def bind(lib, prefix):
         f("wait_stats").restype = C.c_int
         f("matches_wait").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         f("matches_wait").restype = C.c_int
+    if hasattr(lib, prefix + "move"):                     # include/mm_wait.h: the move to a fallback mode
+        f("move").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]
+        f("move").restype = C.c_int
+        f("moved").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        f("moved").restype = C.c_int
     return lib
 
 
@@ -475,6 +480,21 @@ class EngineBase:
         slots, group, age = (np.empty(k, dtype=np.uint32) for _ in range(3))
         self._check(self._fn("expired")(self._h, 0, k, _ptr(slots), _ptr(group), _ptr(age)), "expired")
         return slots, group, age
+
+    def move(self, from_mode, to_mode, max_age, cons_clear=0):
+        """mm_move + mm_expired + mm_moved: every waiting player of `from_mode` older than max_age leaves it as if
+        expired and joins the tail of (to_mode, its rating group) with its stamp, its rating and its constraint word
+        less the `cons_clear` bits.  -> (slots, group, age, new_slots) in mm_expire's order; new_slots is NO_SLOT where
+        to_mode cannot seat the player (it is expired only).  self.last_move = {"selected", "refused"}."""
+        n, r = C.c_uint32(), C.c_uint32()
+        self._check(self._fn("move")(self._h, from_mode, to_mode, int(max_age) & 0xFFFFFFFF, int(cons_clear) & 0xFFFFFFFF,
+                                     C.byref(n), C.byref(r)), "move")
+        k = int(n.value)
+        self.last_move = {"selected": k, "refused": int(r.value)}
+        slots, group, age, new = (np.empty(k, dtype=np.uint32) for _ in range(4))
+        self._check(self._fn("expired")(self._h, 0, k, _ptr(slots), _ptr(group), _ptr(age)), "expired")
+        self._check(self._fn("moved")(self._h, 0, k, _ptr(new)), "moved")
+        return slots, group, age, new
 
     def wait_stats(self, mode=0):
         """mm_wait_stats: one dict per rating group (waiting, oldest_age, age_sum, hist[33])."""

@@ -1098,7 +1098,10 @@ struct mm_engine {
     uint32_t* d_wt_out;        // [3][capacity] the last mm_expire's list on the device: slot | rating group | age
     WaitGroupDev* d_wt_stats;  // [MM_MAX_GROUPS]
     uint32_t* d_wt_matched;    // waits of the last tick's matched players (k_wait_matched)
-    std::vector<uint32_t> x_slot, x_group, x_age;   // the last mm_expire's list (mm_expired)
+    std::vector<uint32_t> x_slot, x_group, x_age;   // the last mm_expire's or mm_move's list (mm_expired)
+    std::vector<uint32_t> x_new;                    // ... its fourth column after an mm_move: the new slots (mm_moved)
+    uint32_t* d_mv_cols;       // [4][capacity] mm_move's rows: rating | constraint word | stamp | new slot (allocated at the first mm_move)
+    uint8_t* d_mv_group;       // [capacity] ... and their rating groups, the column k_bucket_* take
     uint32_t* h_mwait;         // pinned, as large as d_wt_matched: mm_matches_wait, emission order, r_L words a lobby
     uint32_t mw_n;             // lobbies of the last tick h_mwait covers (0: the clock was off at that tick)
 };
@@ -1673,7 +1676,7 @@ extern "C" int mm_reset(mm_engine* e)
         e->cancel_pending = 0;
         e->r_n = 0;
         e->mw_n = 0;
-        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear();   // (the clock itself goes on: include/mm_wait.h)
+        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();   // (the clock itself goes on: include/mm_wait.h)
         e->live_upper = 0;
         std::fill(e->tk_last_len.begin(), e->tk_last_len.end(), 0u);
         const int rc = engine_reset_device(e);
@@ -1702,10 +1705,11 @@ static int ensure_staging(mm_engine* e, size_t n)
     return MM_OK;
 }
 
-// Shared by both enqueue entry points; all pointers are device pointers.
-static int enqueue_device_impl(mm_engine* e, uint32_t n, const int32_t* d_rating, const uint32_t* d_cons,
-                               const uint8_t* d_group, const uint32_t* d_slot_sel, uint32_t* d_out_slot,
-                               uint32_t* rejected, float* bucket_ms, uint32_t* h_out_slot = nullptr)
+// The bucketing of a batch, queued on the engine's stream with the copy of its refusal counter behind it; all pointers
+// are device pointers.  Nothing is waited for: enqueue_device_impl does that for the two enqueue entry points, mm_move
+// puts its own kernel and copies behind this first (one wait for all of it).
+static int enqueue_device_launch(mm_engine* e, uint32_t n, const int32_t* d_rating, const uint32_t* d_cons,
+                                 const uint8_t* d_group, const uint32_t* d_slot_sel, uint32_t* d_out_slot)
 {
     const uint32_t blocks = (n + BK_CHUNK - 1) / BK_CHUNK;
     const size_t rows = (size_t)blocks * BK_WAVES;
@@ -1729,6 +1733,16 @@ static int enqueue_device_impl(mm_engine* e, uint32_t n, const int32_t* d_rating
     HIPCHK(e, hipGetLastError());
     if (timing) HIPCHK(e, hipEventRecord(e->ev[1], e->stream));
     HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, e->d_counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    return MM_OK;
+}
+
+// Shared by both enqueue entry points; all pointers are device pointers.
+static int enqueue_device_impl(mm_engine* e, uint32_t n, const int32_t* d_rating, const uint32_t* d_cons,
+                               const uint8_t* d_group, const uint32_t* d_slot_sel, uint32_t* d_out_slot,
+                               uint32_t* rejected, float* bucket_ms, uint32_t* h_out_slot = nullptr)
+{
+    const bool timing = (e->cfg.flags & MM_CFG_TIMING) != 0;
+    MMTRY(enqueue_device_launch(e, n, d_rating, d_cons, d_group, d_slot_sel, d_out_slot));
     // the handles travel with the counter: one round trip to the device per enqueue, not two (a stream enqueues every tick)
     if (h_out_slot) HIPCHK(e, hipMemcpyAsync(h_out_slot, d_out_slot, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -3380,7 +3394,7 @@ extern "C" int mm_expire(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t
     if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
     ON_ENGINE_DEVICE(e);
     RoctxRange rr("mm_expire");
-    e->x_slot.clear(); e->x_group.clear(); e->x_age.clear();
+    e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
     if (n_expired) *n_expired = 0;
     bool marked_on_device = false;
     const int rc = guarded([&]() -> int { return expire_impl(e, mode, max_age, n_expired, &marked_on_device); });
@@ -3407,6 +3421,131 @@ extern "C" int mm_expired(mm_engine* e, uint32_t first, uint32_t count, uint32_t
     if (slots) memcpy(slots, &e->x_slot[first], (size_t)count * sizeof(uint32_t));
     if (group) memcpy(group, &e->x_group[first], (size_t)count * sizeof(uint32_t));
     if (age) memcpy(age, &e->x_age[first], (size_t)count * sizeof(uint32_t));
+    return MM_OK;
+}
+
+// The columns of a move, at the first mm_move: both, or neither.
+static int move_alloc(mm_engine* e)
+{
+    if (e->d_mv_group) return MM_OK;
+    const size_t cap = e->cfg.capacity;
+    const int rc = guarded([&]() -> int {
+        MMTRY(dev_alloc(e, e->d_mv_cols, 4u * cap * sizeof(uint32_t)));
+        return dev_alloc(e, e->d_mv_group, cap);   // last: its presence says both are there
+    });
+    if (rc) { mem_release(e, e->d_mv_cols); mem_release(e, e->d_mv_group); }
+    return rc;
+}
+
+// mm_move = the selection of mm_expire, then an enqueue of the selected rows into the other mode without leaving the
+// device.  The count comes back BEFORE anything is marked: the slots are picked on the host (pick_free_slots, as for any
+// mm_enqueue), and a pool without room for them refuses the call with nothing changed.  From k_move_scatter on the
+// rule is expire_impl's: a failure leaves marks the host does not know, so the caller poisons the engine.
+static int move_impl(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
+                     uint32_t* n_selected, uint32_t* n_refused, bool* marked_on_device)
+{
+    MMTRY(move_alloc(e));
+    const WaitParams P = wait_params(e, from_mode, max_age);
+    const uint32_t grid = wait_grid(e), cap = e->cfg.capacity;
+    uint32_t* const d_total = e->d_wt_rows + (size_t)e->wt_max_chunks * WT_ROWS;
+    hipLaunchKernelGGL(k_wait_count, dim3(grid), dim3(WT_THREADS), 0, e->stream, P);
+    hipLaunchKernelGGL(k_wait_scan, dim3(1), dim3(WT_THREADS), 0, e->stream, P);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const uint32_t k = e->h_counters[1];
+    if (k > cap) return MM_ERR_INTERNAL;
+    if (k == 0u) return MM_OK;
+    // the old slots stay held until from_mode's next purge: the pool needs k FREE slots beside them
+    std::vector<uint32_t> sel;
+    bool contiguous = false;
+    if (!pick_free_slots(e, k, sel, &contiguous)) return MM_ERR_FULL;
+    if (!contiguous) {
+        MMTRY(ensure_staging(e, k));
+        HIPCHK(e, hipMemcpyAsync(e->d_in_sel, sel.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    }
+    MoveCols M;
+    M.q_rating = e->d_q_rating;
+    M.q_cons = e->d_q_cons;
+    M.rating = (int32_t*)e->d_mv_cols;
+    M.cons = e->d_mv_cols + cap;
+    M.stamp = e->d_mv_cols + 2u * (size_t)cap;
+    M.group = e->d_mv_group;
+    M.keep = ~cons_clear & MM_CONS_USER_MASK & ~0xFu;
+    M.to_mode = to_mode;
+    uint32_t* const d_new = e->d_mv_cols + 3u * (size_t)cap;
+    *marked_on_device = true;
+    hipLaunchKernelGGL(k_move_scatter, dim3(grid), dim3(WT_THREADS), 0, e->stream, P, M);
+    HIPCHK(e, hipGetLastError());
+    MMTRY(enqueue_device_launch(e, k, M.rating, M.cons, M.group, contiguous ? NULL : e->d_in_sel, d_new));
+    hipLaunchKernelGGL(k_move_stamp, dim3((k + WT_THREADS - 1u) / WT_THREADS), dim3(WT_THREADS), 0, e->stream, k, cap, d_new,
+                       M.stamp, e->d_stamp);
+    HIPCHK(e, hipGetLastError());
+    e->x_slot.resize(k); e->x_group.resize(k); e->x_age.resize(k); e->x_new.resize(k);
+    HIPCHK(e, hipMemcpyAsync(e->x_slot.data(), P.out_slot, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->x_group.data(), P.out_group, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->x_age.data(), P.out_age, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->x_new.data(), d_new, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));           // `sel` must outlive its copy, too
+    const uint32_t rejected = e->h_counters[1];
+    // the host mirrors: the old slots as mm_cancel leaves them, the new ones as mm_enqueue does
+    uint32_t marked = 0, seated = 0;
+    for (uint32_t i = 0; i < k; ++i) {
+        const uint32_t sl = e->x_slot[i];
+        if (sl < cap && e->h_state[sl] == MM_ST_LIVE) { e->h_state[sl] = MM_ST_CANCELLED; ++marked; }
+    }
+    for (uint32_t i = 0; i < k; ++i) {
+        const uint32_t sl = e->x_new[i];
+        if (sl == MM_NO_SLOT) continue;
+        if (sl < cap && e->h_state[sl] == MM_ST_FREE) { e->h_state[sl] = MM_ST_LIVE; ++seated; }
+        else return MM_ERR_INTERNAL;
+    }
+    e->cancel_pending += k;
+    e->next_slot = contiguous ? (uint32_t)(((unsigned long long)e->next_slot + k) % cap) : (sel[k - 1] + 1u) % cap;
+    if (rejected > k || seated != k - rejected) return MM_ERR_INTERNAL;
+    e->live_upper += seated;
+    if (n_selected) *n_selected = k;
+    if (n_refused) *n_refused = rejected;
+    return marked == k ? MM_OK : MM_ERR_INTERNAL;             // (the device's ActiveUser mirror and the host's disagree)
+}
+
+extern "C" int mm_move(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
+                       uint32_t* n_selected, uint32_t* n_refused)
+{
+    if (!e || from_mode >= e->cfg.n_modes || to_mode >= e->cfg.n_modes || from_mode == to_mode ||
+        (cons_clear & (~MM_CONS_USER_MASK | 0xFu)))
+        return MM_ERR_INVALID_ARG;
+    if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
+    ON_ENGINE_DEVICE(e);
+    RoctxRange rr("mm_move");
+    e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
+    if (n_selected) *n_selected = 0;
+    if (n_refused) *n_refused = 0;
+    bool marked_on_device = false;
+    const int rc = guarded([&]() -> int {
+        return move_impl(e, from_mode, to_mode, max_age, cons_clear, n_selected, n_refused, &marked_on_device);
+    });
+    if (rc != MM_OK) {
+        // as mm_expire: no half-filled list, and an engine whose device may hold marks the host does not is poisoned
+        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
+        if (n_selected) *n_selected = 0;
+        if (n_refused) *n_refused = 0;
+        if (marked_on_device) {
+            (void)hipStreamSynchronize(e->stream);
+            e->poisoned = true;
+        }
+    }
+    return rc;
+}
+
+extern "C" int mm_moved(mm_engine* e, uint32_t first, uint32_t count, uint32_t* new_slot)
+{
+    if (!e) return MM_ERR_INVALID_ARG;
+    if (e->poisoned) return MM_ERR_STATE;
+    const size_t n = e->x_new.size();
+    if (first > n || count > n - first) return MM_ERR_RANGE;
+    if (count == 0 || !new_slot) return MM_OK;
+    memcpy(new_slot, &e->x_new[first], (size_t)count * sizeof(uint32_t));
     return MM_OK;
 }
 

@@ -1,5 +1,5 @@
 // mm_wait.inc — the clock of include/mm_wait.h on the device: expiry selection as a stable stream compaction over a
-// mode's queues, wait statistics.  Included by mm_engine.hip (ChainDev, LobbyDev, dev_min_u32, wave_incl_scan, the WT_* chunk geometry); the host
+// mode's queues, the same selection gathering the rows of a move into another mode (mm_move), wait statistics.  Included by mm_engine.hip (ChainDev, LobbyDev, dev_min_u32, wave_incl_scan, the WT_* chunk geometry); the host
 // functions that launch these kernels (wait_alloc .. mm_wait_stats) are there, like the pair and team host loops.
 // k_wait_matched sits beside k_pack_results in mm_engine.hip, whose PackArgs it shares.  DESIGN.md §4.6.
 //
@@ -160,9 +160,37 @@ __global__ __launch_bounds__(WT_THREADS) void k_wait_scan(WaitParams P)
     }
 }
 
+// What mm_move's scatter gathers beside the list (include/mm_wait.h): the rows of an enqueue into the other mode, on the
+// device, at the ranks of the list — rating, rewritten constraint word, rating group as a byte (k_bucket_* take that
+// column), and the stamp the player keeps.  cons' = (cons & keep) | to_mode, keep = ~cons_clear & MM_CONS_USER_MASK & ~0xF.
+struct MoveCols {
+    const int32_t* q_rating;
+    const uint32_t* q_cons;
+    int32_t* rating;
+    uint32_t* cons;
+    uint32_t* stamp;
+    uint8_t* group;
+    uint32_t keep, to_mode;
+};
+
+// The (team, seat) of the idx-th seated player of a stored lobby, in wait_seat's order; false past the last.
+static __device__ __forceinline__ bool wait_seat_at(const LobbyDev& lb, uint32_t teams, uint32_t idx, uint32_t& t, uint32_t& i)
+{
+    for (t = 0; t < teams && t < MM_MAX_TEAMS; ++t) {
+        const uint32_t c = dev_min_u32(lb.cnt[t], 8u);
+        if (idx < c) { i = idx; return true; }
+        idx -= c;
+    }
+    return false;
+}
+
 // Every selected player at its rank, and marked as k_cancel marks a slot.  A slot is in one queue or one lobby, once:
 // the mark a thread sets is read by nobody else, so the selection is the one k_wait_count counted.
-__global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P)
+// GATHER (mm_move): the selected player's row goes along — a queue entry's rating and constraint word from the position
+// the wave streams anyway (loaded with the slots, before the gathers of wait_load are waited for), a lobby seat's from
+// the LobbyDev record; the stamp is the clock minus the age the selection computed.
+template <bool GATHER>
+static __device__ __forceinline__ void wait_scatter_body(const WaitParams& P, const MoveCols& M)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -174,6 +202,16 @@ __global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P)
         uint32_t base = P.rows[(size_t)b * WT_ROWS + 1u + wave];
         if (w0 < len) {
             uint32_t sl[WT_ITERS], age[WT_ITERS];
+            int32_t rt[WT_ITERS];
+            uint32_t cn[WT_ITERS];
+            if (GATHER) {
+#pragma unroll
+                for (uint32_t r = 0; r < WT_ITERS; ++r) {
+                    const uint32_t i = w0 + r * 64 + lane;
+                    rt[r] = i < len ? M.q_rating[qo + i] : 0;
+                    cn[r] = i < len ? M.q_cons[qo + i] : 0u;
+                }
+            }
             const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
 #pragma unroll
             for (uint32_t r = 0; r < WT_ITERS; ++r) {
@@ -184,14 +222,24 @@ __global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P)
                     P.out_slot[at] = sl[r];
                     P.out_group[at] = g;
                     P.out_age[at] = age[r];
+                    if (GATHER) {
+                        M.rating[at] = rt[r];
+                        M.cons[at] = (cn[r] & M.keep) | M.to_mode;
+                        M.group[at] = (uint8_t)g;
+                        M.stamp[at] = P.now - age[r];
+                    }
                     P.state[sl[r]] = MM_ST_CANCELLED;
                 }
                 base += (uint32_t)__popcll(m);
             }
         }
         if (wave == 0) {
-            uint32_t age = 0, sl = MM_NO_SLOT;
-            if (k == 0u && (uint32_t)lane < WT_SEATS) sl = wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane);
+            const LobbyDev& lb = P.chains[P.mode * P.n_groups + g].lobby;
+            uint32_t age = 0, sl = MM_NO_SLOT, t = 0, i = 0;
+            if (k == 0u && (uint32_t)lane < WT_SEATS) {
+                if (!GATHER) sl = wait_seat(lb, P.teams, (uint32_t)lane);
+                else if (wait_seat_at(lb, P.teams, (uint32_t)lane, t, i)) sl = lb.slot[t][i];
+            }
             const bool sel = wait_age(P, sl, age) && age > P.max_age;
             const unsigned long long m = __ballot(sel);
             const uint32_t at = P.rows[(size_t)b * WT_ROWS] + (uint32_t)__popcll(m & lt);
@@ -199,10 +247,38 @@ __global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P)
                 P.out_slot[at] = sl;
                 P.out_group[at] = g;
                 P.out_age[at] = age;
+                if (GATHER) {
+                    M.rating[at] = lb.rating[t][i];
+                    M.cons[at] = (lb.cons[t][i] & M.keep) | M.to_mode;
+                    M.group[at] = (uint8_t)g;
+                    M.stamp[at] = P.now - age;
+                }
                 P.state[sl] = MM_ST_CANCELLED;
             }
         }
     }
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P)
+{
+    MoveCols none;
+    none.q_rating = nullptr; none.q_cons = nullptr; none.rating = nullptr; none.cons = nullptr;
+    none.stamp = nullptr; none.group = nullptr; none.keep = 0u; none.to_mode = 0u;
+    wait_scatter_body<false>(P, none);
+}
+
+// mm_move's scatter: the list as k_wait_scatter writes it, plus the rows for k_bucket_*.
+__global__ __launch_bounds__(WT_THREADS) void k_move_scatter(WaitParams P, MoveCols M) { wait_scatter_body<true>(P, M); }
+
+// After the bucketing of a move: an accepted row's new slot carries the stamp of the slot the player left
+// (k_bucket_scatter stamped it with the clock, as for any enqueue; new_slot is its out_slot column, MM_NO_SLOT = refused).
+__global__ __launch_bounds__(WT_THREADS) void k_move_stamp(uint32_t n, uint32_t capacity, const uint32_t* __restrict__ new_slot,
+                                                           const uint32_t* __restrict__ old_stamp, uint32_t* __restrict__ stamp)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t s = new_slot[i];
+    if (s < capacity) stamp[s] = old_stamp[i];
 }
 
 static __device__ __forceinline__ uint32_t wait_bucket(uint32_t age) { return age ? 64u - (uint32_t)__clzll((long long)age) : 0u; }

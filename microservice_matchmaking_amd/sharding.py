@@ -172,6 +172,17 @@ class ShardedSearch:
         self.local_to_global[slots[ok].astype(np.int64)] = first_global_index + idx[ok]
         return idx, slots
 
+    def move(self, from_mode, to_mode, max_age, cons_clear=0):
+        """mm_move (include/mm_wait.h) on a search that is ONE rank: chain (from_mode, g) and chain (to_mode, g) may have
+        different owners, and nothing here carries a player from one engine to another.  The moved players keep their
+        global arrival index under their new slot."""
+        if self.world_size != 1:
+            raise NotImplementedError("mm_move across ranks: chains (from_mode, g) and (to_mode, g) may have different owners")
+        got = self.engine.move(from_mode, to_mode, max_age, cons_clear)
+        ok = got[3] != NO_SLOT
+        self.local_to_global[got[3][ok].astype(np.int64)] = self.local_to_global[got[0][ok].astype(np.int64)]
+        return got
+
     def tick(self, mode=0):
         return self.engine.tick(mode)
 

@@ -45,7 +45,8 @@ def stream_schedule(qps, seconds, tick_ms, seed):
     return out
 
 
-def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=True, batches=None, ttl_ms=None):
+def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=True, batches=None, ttl_ms=None,
+               fallback=None):
     """Drive `search` (a sharding.ShardedSearch: one engine + the chains this rank owns) through
     the schedule.  Returns a dict with per-mode latency arrays (real, floor), matched players,
     per-tick cost and a digest per chain of everything it emitted, in order.
@@ -56,8 +57,14 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
     period's end in milliseconds, every mode expires whoever has waited longer than ttl_ms, then the modes tick.  The result
     then also holds `expired` (players per mode), `wait_ms` (per mode, the engine's own figure for every matched player:
     clock at its tick minus clock at its enqueue — whole periods, beside `real` and `floor`) and `depth_max` (per mode,
-    the deepest the queues were after a tick).  None: no clock, nothing of this runs."""
+    the deepest the queues were after a tick).  None: no clock, nothing of this runs.
+    `fallback`: rules [(from_mode, to_mode, after_ms, cons_clear)] of mm_move (include/mm_wait.h): every period, after the
+    clock is set and the arrivals are in and before the expiry, whoever has waited in from_mode for longer than after_ms
+    moves to to_mode with its stamp, the rules in list order (so tiers chain within a period).  The clock runs as for
+    ttl_ms; the result also holds `moved` and `refused` (players per rule), `wait_ms` and `depth_max`.  One rank only."""
     assert batches is None or len(batches) == len(schedule)
+    fallback = list(fallback or ())
+    clocked = ttl_ms is not None or bool(fallback)
     cfg = search.cfg
     n_modes, n_groups = int(cfg.n_modes), int(cfg.n_groups)
     total = sum(s[2] for s in schedule)
@@ -73,6 +80,7 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
     expired = [0] * n_modes
     wait_ms = [[] for _ in range(n_modes)]
     depth_max = [0] * n_modes
+    moved, refused = [0] * len(fallback), [0] * len(fallback)
     # (a generation-2 collection of the interpreter's heap is a pause of tens of milliseconds in one tick of a real-time
     # run: nothing here makes reference cycles, so the collector rests until the stream is over)
     import gc
@@ -94,7 +102,7 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
                     if left > 0.0006:
                         time.sleep(left - 0.0004)
             t0 = time.perf_counter()
-            if ttl_ms is not None:
+            if clocked:
                 search.engine.clock_set(int(round(t_close * 1e3)))  # this period's arrivals are stamped with its end
             try:
                 search.enqueue(rating, cons, first_global_index=first)
@@ -107,13 +115,17 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
                 full_at_s = t_open
                 break
             first += n
+            for i, (src, dst, after_ms, cons_clear) in enumerate(fallback):
+                got = search.move(src, dst, int(after_ms), int(cons_clear))
+                moved[i] += int(got[0].size)
+                refused[i] += int(search.engine.last_move["refused"])
             if ttl_ms is not None:
                 for md in range(n_modes):
                     expired[md] += int(search.engine.expire(md, int(ttl_ms))[0].size)
             for md in range(n_modes):
                 m = search.tick(md)
                 t1 = time.perf_counter()
-                if ttl_ms is not None:
+                if clocked:
                     if len(m):
                         wait_ms[md].append(search.engine.matches_wait().ravel().astype(np.float64))
                     depth_max[md] = max(depth_max[md], int(search.engine.queue_depth(md).sum()))
@@ -141,8 +153,12 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
         "depth": depth, "digests": {k: h.hexdigest() for k, h in hashers.items()}, "lobbies": emitted,
         "arrivals": total, "ingested": first, "full_at_s": full_at_s,
     }
+    if clocked:
+        out.update({"wait_ms": [cat(x) for x in wait_ms], "depth_max": depth_max})
     if ttl_ms is not None:
-        out.update({"expired": expired, "wait_ms": [cat(x) for x in wait_ms], "depth_max": depth_max})
+        out["expired"] = expired
+    if fallback:
+        out.update({"moved": moved, "refused": refused})
     return out
 
 

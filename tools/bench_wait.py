@@ -9,7 +9,14 @@ mm_expire and mm_wait_stats are timed on the host around the call (what the owne
 synchronisation, and for mm_expire the copy of the list and the host mirror's update); the kernels' own durations come
 from a kernel trace of this script (rocprofv3 --kernel-trace --stats -- python tools/bench_wait.py --steps 20).
 
-Usage (GPU box, repo root):  python tools/bench_wait.py [--steps 30] [--players 1000000] > profiles/wait_1m.json"""
+--move adds mm_move at 0 %, 1 % and 50 % selected (cfg-2's pool as mode 0, the same game with a window of +-100 and no
+region filter as mode 1, its fallback; twice the capacity, since the old slots are held until the next tick) beside the
+route an owner had before it, timed in the same process in turns: mm_expire, mm_expired, a numpy gather of rating and
+constraint word from a host table, mm_enqueue of the same rows.  The enqueue and tick figures above are restated in the
+same output (they must not have moved: k_bucket_scatter is untouched).
+
+Usage (GPU box, repo root):  python tools/bench_wait.py [--steps 30] [--players 1000000] > profiles/wait_1m.json
+                             python tools/bench_wait.py --move > profiles/wait_move_1m.json"""
 import argparse
 import json
 import os
@@ -30,6 +37,61 @@ def spread(xs):
     return {"median": float(np.median(a)), "p10": float(np.percentile(a, 10)), "p90": float(np.percentile(a, 90)), "n": int(a.size)}
 
 
+def measure_move(args, rating, cons, d_rating, d_cons, now):
+    """mm_move and the host route, in turns on one engine: the same pool, the same split into an old and a young batch, the
+    same players selected; both leave the same queues behind (checked once per share)."""
+    from microservice_matchmaking_amd import Engine, make_config, mode_1v1
+    n = args.players
+    cap = 2 << (n - 1).bit_length()
+    cfg = make_config([mode_1v1(window=25, region_filter=True), mode_1v1(window=100)], capacity=cap, timing=True)
+    out = {}
+    with Engine(cfg) as eng:
+        eng.clock_set(now)
+        for label, frac in (("0pct", 0.0), ("1pct", 0.01), ("50pct", 0.5)):
+            old = int(n * frac)
+            t_move, t_host, parts, depth = [], [], {"expire_ms": [], "gather_ms": [], "enqueue_ms": []}, {}
+            for k in range(args.warmup + args.steps):
+                for route in ("move", "host") if k % 2 == 0 else ("host", "move"):
+                    eng.reset()
+                    now += 10
+                    eng.clock_set(now)
+                    if old:
+                        eng.enqueue_device(d_rating[:old], d_cons[:old])
+                    now += 100
+                    eng.clock_set(now)
+                    eng.enqueue_device(d_rating[old:], d_cons[old:])        # slot i holds player i: the owner's table is (rating, cons)
+                    t0 = time.perf_counter()
+                    if route == "move":
+                        got = eng.move(0, 1, 50)
+                        t1 = time.perf_counter()
+                        assert got[0].size == old and (got[3] != 0xFFFFFFFF).all()
+                        if k >= args.warmup:
+                            t_move.append((t1 - t0) * 1e3)
+                    else:
+                        slots, group, _ = eng.expire(0, 50)
+                        ta = time.perf_counter()
+                        r2 = rating[slots]
+                        c2 = (cons[slots] & np.uint32(0x000FFFF0)) | np.uint32(1)
+                        g2 = group.astype(np.uint8)
+                        tb = time.perf_counter()
+                        new = eng.enqueue(r2, c2, g2) if old else np.zeros(0, np.uint32)
+                        t1 = time.perf_counter()
+                        assert slots.size == old and new.size == old
+                        if k >= args.warmup:
+                            t_host.append((t1 - t0) * 1e3)
+                            parts["expire_ms"].append((ta - t0) * 1e3)
+                            parts["gather_ms"].append((tb - ta) * 1e3)
+                            parts["enqueue_ms"].append((t1 - tb) * 1e3)
+                    depth[route] = (eng.queue_depth(0).tolist(), eng.queue_depth(1).tolist())
+            assert depth["move"] == depth["host"], depth
+            out[label] = {"selected": old, "move_call_ms": spread(t_move), "host_route_ms": spread(t_host),
+                          "host_route_parts_ms": {k: med(v) for k, v in parts.items()},
+                          "move_over_host": med(t_move) / med(t_host)}
+    out["note"] = ("host time around the calls; the host route's stamp is the time of the re-enqueue, mm_move's the original one. "
+                   "capacity %d: a moved player's old slot is held until from_mode's next tick on either route" % cap)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
@@ -38,6 +100,7 @@ def main():
     ap.add_argument("--clock-first", action="store_true",
                     help="create the engine with the clock before the one without (two engines are two sets of allocations: "
                          "does a difference between their ticks follow the clock or the engine's place in memory?)")
+    ap.add_argument("--move", action="store_true", help="also measure mm_move beside the host route it replaces")
     args = ap.parse_args()
     assert args.steps >= 20, "medians of at least 20 steps"
     import torch
@@ -117,6 +180,8 @@ def main():
                 call.append((t1 - t0) * 1e3)
         expire[label] = {"expired": old, "call_ms": spread(call)}
 
+    move = measure_move(args, rating, cons, d_rating, d_cons, now) if args.move else None
+
     bucket = med(rows["off"]["bucket_ms"])
     out = {
         "workload": "cfg-2: %d players, 1v1, +-25 rating + region filter, uniform ratings, capacity %d" % (n, cap),
@@ -137,6 +202,8 @@ def main():
                       "note": "call_ms is host time around the call (launches + synchronisation + copies), bucket_ms the HIP-event "
                               "time of three kernels: the kernels' own durations are in the kernel trace of this script"},
     }
+    if move is not None:
+        out["move"] = move
     print(json.dumps(out, indent=1))
     off.close()
     on.close()
