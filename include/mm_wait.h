@@ -1,6 +1,6 @@
 /*
  * mm_wait.h — the engine's clock: arrival stamps, expiry of long-waiting players, their move to a
- * fallback mode, wait times.
+ * fallback mode — inside one engine or carried to another one with their rows and stamps — wait times.
  *
  * An extension of include/mm_engine.h (same rules: plain C types, status codes and never an
  * abort, every entry point selects the engine's HIP device itself, MM_ERR_STATE on an engine
@@ -26,11 +26,23 @@
  * device puts the player into a looser mode (a wider window, no region filter, "any role"), with
  * the stamp it had — so ages go on, tiers chain and the wait statistics tell the true wait.
  *
+ * Carrying a player between engines is mm_move cut in two: mm_move_out selects and marks as mm_move
+ * does and hands the rows out (mm_expired: slot, group, age; mm_moved_rows: rating, rewritten
+ * constraint word, stamp), mm_enqueue_stamped takes rows in WITH their stamps.  The same two calls
+ * re-queue the rest of a lobby whose ready check failed (stamp = clock at the tick - its
+ * mm_matches_wait word) and refill an engine from redelivered messages that carry their own times.
+ * On ONE engine mm_move_out + mm_enqueue_stamped of the same rows with their groups is mm_move word
+ * for word — the same new slots (out_slot == mm_moved's column), the same queue order, the same
+ * stamps: slot allocation steps over LIVE and CANCELLED slots alike, so marking the old slots before
+ * or after the new ones are picked makes no difference.
+ *
  * Not here: the NIF binding (native/mm_nif.c; INTEGRATION.md section 7 names the calls to add);
- * mm_move across the ranks of a ShardedSearch (chain (A, g) and chain (B, g) may have different
- * owners: the owner of such a pool moves through mm_expire on one rank and mm_enqueue on the
- * other, and loses the stamp); matching a waiting player against a wider window INSIDE its own
- * queue (a new predicate, with no witness in the reference or the oracle).
+ * an ALL-OR-NOTHING move across engines (chain (A, g) and chain (B, g) of a ShardedSearch may have
+ * different owners: mm_move_out has expired the players on their source before the destination's
+ * mm_enqueue_stamped can answer MM_ERR_FULL, so a full destination loses them — sharding.py raises
+ * on every rank); a device-pointer variant of mm_enqueue_stamped; mm_move itself on the stamped
+ * scatter (it still stamps in a kernel of its own); matching a waiting player against a wider window
+ * INSIDE its own queue (a new predicate, with no witness in the reference or the oracle).
  */
 #ifndef MM_WAIT_H
 #define MM_WAIT_H
@@ -79,11 +91,11 @@ int mm_clock_get(const mm_engine* e, uint32_t* now, uint32_t* enabled);
  * (lib/models/active_user.ex:57-66) is what each expiry amounts to. */
 int mm_expire(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t* n_expired);
 
-/* Entries [first, first + count) of the last mm_expire's or mm_move's list: the slot, its rating
+/* Entries [first, first + count) of the last mm_expire's, mm_move's or mm_move_out's list: the slot, its rating
  * group and the age it had reached.  Order: rating group ascending; within a group the stored lobby's
  * seats in the order mm_lobby_state lists them, then the queue from head to tail — the same on
  * every run, so an owner can publish its "no match found" replies from it.  Readable until the
- * next mm_expire, mm_move, mm_reset or mm_restore.  Any output pointer may be NULL.
+ * next mm_expire, mm_move, mm_move_out, mm_reset or mm_restore.  Any output pointer may be NULL.
  * MM_ERR_RANGE: the range is not inside the list.  Reference: none. */
 int mm_expired(mm_engine* e, uint32_t first, uint32_t count, uint32_t* slots, uint32_t* group,
                uint32_t* age);
@@ -118,6 +130,39 @@ int mm_move(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age
  * MM_NO_SLOT for a refused player.  Range rule and lifetime as mm_expired (after an mm_expire the
  * column is empty).  Reference: none. */
 int mm_moved(mm_engine* e, uint32_t first, uint32_t count, uint32_t* new_slot);
+
+/* The first half of mm_move: selects exactly the players mm_expire(from_mode, max_age) selects, in
+ * exactly its order, and marks them exactly as mm_expire does (from_mode's next tick drops them);
+ * the list stays readable through mm_expired, and mm_moved_rows reads what an enqueue elsewhere
+ * needs.  It takes no new slot and touches no other queue: never MM_ERR_FULL.  to_mode only goes
+ * into the rewritten constraint word and may be a mode THIS engine does not have (the destination
+ * may be another engine); mm_moved reads an empty column afterwards, as after mm_expire.
+ * MM_ERR_INVALID_ARG: no such from_mode, to_mode >= MM_MAX_MODES, from_mode == to_mode, cons_clear
+ * with a bit outside MM_CONS_USER_MASK or inside the mode nibble.  MM_ERR_STATE: the clock was never
+ * set.  A failure once the first mark may be on the device leaves the engine MM_ERR_STATE until
+ * mm_reset / mm_restore, as for mm_expire.  *n_selected may be NULL.
+ * Reference: none (as mm_move); to the oracle it is mo_cancel of the listed slots. */
+int mm_move_out(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age,
+                uint32_t cons_clear, uint32_t* n_selected);
+
+/* Entries [first, first + count) of the last mm_move_out's list, the rows: the rating, the
+ * constraint word already rewritten to ((cons & ~cons_clear) & MM_CONS_USER_MASK & ~0xF) | to_mode,
+ * and the stamp (the clock at the call minus the age mm_expired reports).  Range rule and lifetime
+ * as mm_expired; the columns are empty after mm_expire, mm_move, mm_reset and mm_restore.  Any
+ * output pointer may be NULL.  Reference: none. */
+int mm_moved_rows(mm_engine* e, uint32_t first, uint32_t count, int32_t* rating, uint32_t* cons,
+                  uint32_t* stamp);
+
+/* mm_enqueue (include/mm_engine.h) in every respect — slot choice, MM_ERR_FULL, the `group`
+ * override, refused rows, out_slot, st — except that accepted player i is stamped stamp[i] instead
+ * of the clock: its age is clock - stamp[i] from the start.  Nothing is written for a refused row.
+ * MM_ERR_STATE: the clock was never set.  MM_ERR_INVALID_ARG: stamp == NULL with n > 0 (and
+ * mm_enqueue's).  MM_ERR_RANGE, and nothing has changed: some (int32_t)(clock - stamp[i]) < 0 — a
+ * stamp ahead of the clock would read as an age near 2^32 and expire at once.
+ * Reference: none (the deliveries of lib/search/worker.ex:352-358 carry no arrival time). */
+int mm_enqueue_stamped(mm_engine* e, uint32_t n, const int32_t* rating, const uint32_t* cons,
+                       const uint8_t* group, const uint32_t* stamp, uint32_t* out_slot,
+                       mm_enqueue_stats* st);
 
 /* per_group[cfg.n_groups]: who waits in `mode`, per rating group, and for how long.
  * MM_ERR_STATE: the clock was never set.

@@ -240,6 +240,14 @@ def bind(lib, prefix):
         f("move").restype = C.c_int
         f("moved").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         f("moved").restype = C.c_int
+    if hasattr(lib, prefix + "move_out"):                 # include/mm_wait.h: carrying waiting players between engines
+        f("move_out").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
+        f("move_out").restype = C.c_int
+        f("moved_rows").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        f("moved_rows").restype = C.c_int
+        f("enqueue_stamped").argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.POINTER(MMEnqueueStats)]
+        f("enqueue_stamped").restype = C.c_int
     return lib
 
 
@@ -495,6 +503,38 @@ class EngineBase:
         self._check(self._fn("expired")(self._h, 0, k, _ptr(slots), _ptr(group), _ptr(age)), "expired")
         self._check(self._fn("moved")(self._h, 0, k, _ptr(new)), "moved")
         return slots, group, age, new
+
+    def move_out(self, from_mode, to_mode, max_age, cons_clear=0):
+        """mm_move_out + mm_expired + mm_moved_rows: the first half of `move` — the same players leave `from_mode` as if
+        expired, and their rows come back instead of being enqueued: -> (slots, group, age, rating, cons, stamp) in
+        mm_expire's order, `cons` already rewritten for `to_mode` (which may be a mode of ANOTHER engine), `stamp` the
+        arrival time to hand to enqueue_stamped there."""
+        n = C.c_uint32()
+        self._check(self._fn("move_out")(self._h, from_mode, to_mode, int(max_age) & 0xFFFFFFFF,
+                                         int(cons_clear) & 0xFFFFFFFF, C.byref(n)), "move_out")
+        k = int(n.value)
+        slots, group, age, cons, stamp = (np.empty(k, dtype=np.uint32) for _ in range(5))
+        rating = np.empty(k, dtype=np.int32)
+        self._check(self._fn("expired")(self._h, 0, k, _ptr(slots), _ptr(group), _ptr(age)), "expired")
+        self._check(self._fn("moved_rows")(self._h, 0, k, _ptr(rating), _ptr(cons), _ptr(stamp)), "moved_rows")
+        return slots, group, age, rating, cons, stamp
+
+    def enqueue_stamped(self, rating, cons, stamp, group=None):
+        """mm_enqueue_stamped: `enqueue`, every accepted player stamped stamp[i] instead of the clock.  -> slots."""
+        rating = np.ascontiguousarray(rating, dtype=np.int32)
+        cons = np.ascontiguousarray(cons, dtype=np.uint32)
+        stamp = np.ascontiguousarray(stamp, dtype=np.uint32)
+        assert rating.shape == cons.shape == stamp.shape and rating.ndim == 1
+        if group is not None:
+            group = np.ascontiguousarray(group, dtype=np.uint8)
+            assert group.shape == rating.shape
+        n = rating.shape[0]
+        slots = np.empty(n, dtype=np.uint32)
+        st = MMEnqueueStats()
+        self._check(self._fn("enqueue_stamped")(self._h, n, _ptr(rating), _ptr(cons), _ptr(group), _ptr(stamp),
+                                                _ptr(slots), C.byref(st)), "enqueue_stamped")
+        self.last_enqueue_stats = st.as_dict()
+        return slots
 
     def wait_stats(self, mode=0):
         """mm_wait_stats: one dict per rating group (waiting, oldest_age, age_sum, hist[33])."""

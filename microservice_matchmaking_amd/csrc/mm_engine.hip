@@ -259,6 +259,11 @@ __global__ __launch_bounds__(BK_THREADS) void k_bucket_scan(uint32_t n_rows, uin
 }
 
 // Stable scatter into the chain tails.  wave_base = scanned wave_hist.
+// STAMPED (mm_enqueue_stamped, include/mm_wait.h): row i brings its own arrival stamp in in_stamp[i], loaded with its
+// rating and constraint word and written with the queue entry — to the SLOT the row got, for accepted rows only; `now` is
+// not used.  k_bucket_scatter<false> is the scatter of every other enqueue (in_stamp NULL and never read): no load, no
+// register and no store of the stamped instance is in it.
+template <bool STAMPED>
 __global__ __launch_bounds__(BK_THREADS) void k_bucket_scatter(uint32_t n, const int32_t* __restrict__ rating,
                                                                const uint32_t* __restrict__ cons,
                                                                const uint8_t* __restrict__ group, BucketCfg B,
@@ -271,7 +276,8 @@ __global__ __launch_bounds__(BK_THREADS) void k_bucket_scatter(uint32_t n, const
                                                                uint32_t* __restrict__ q_slot,
                                                                uint8_t* __restrict__ state,
                                                                uint32_t* __restrict__ out_slot,
-                                                               uint32_t* __restrict__ stamp, uint32_t now)
+                                                               uint32_t* __restrict__ stamp, uint32_t now,
+                                                               const uint32_t* __restrict__ in_stamp)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t row = (blockIdx.x * BK_WAVES + wave) * n_chains;
@@ -287,9 +293,11 @@ __global__ __launch_bounds__(BK_THREADS) void k_bucket_scatter(uint32_t n, const
         const bool valid = i < n;
         uint32_t ch = BK_INVALID, cn = 0;
         int32_t rt = 0;
+        uint32_t st = 0;
         if (valid) {
             rt = rating[i];
             cn = cons[i] & MM_CONS_USER_MASK;
+            if (STAMPED) st = in_stamp[i];
             ch = dev_chain_of(B, rt, cn, group, i);
         }
         // slot_sel: the host picked the free slots itself (the ring range held a waiting player)
@@ -310,7 +318,8 @@ __global__ __launch_bounds__(BK_THREADS) void k_bucket_scatter(uint32_t n, const
                     q_cons[o] = cn;
                     q_slot[o] = slot;
                     state[slot] = MM_ST_LIVE;
-                    if (stamp) stamp[slot] = now;   // the clock (include/mm_wait.h); NULL until the owner sets it
+                    if (STAMPED) stamp[slot] = st;  // the player's own arrival time (the clock is on: mm_enqueue_stamped)
+                    else if (stamp) stamp[slot] = now;   // the clock (include/mm_wait.h); NULL until the owner sets it
                 }
             }
             lc_add(cur, c0, (uint32_t)__popcll(m), lane);
@@ -1014,6 +1023,8 @@ struct mm_engine {
     uint32_t* d_in_slot;       // also cancel staging
     uint32_t* d_in_sel;        // slots the host picked (mm_enqueue stepping over waiting players)
     size_t in_cap;
+    uint32_t* d_in_stamp;      // the stamp column of mm_enqueue_stamped (include/mm_wait.h): allocated at its first call
+    size_t in_stamp_cap;
     uint32_t* d_out_slots;
     float* d_out_score;
     uint32_t* d_out_pass;
@@ -1100,6 +1111,8 @@ struct mm_engine {
     uint32_t* d_wt_matched;    // waits of the last tick's matched players (k_wait_matched)
     std::vector<uint32_t> x_slot, x_group, x_age;   // the last mm_expire's or mm_move's list (mm_expired)
     std::vector<uint32_t> x_new;                    // ... its fourth column after an mm_move: the new slots (mm_moved)
+    std::vector<int32_t> x_rating;                  // ... and after an mm_move_out the rows themselves (mm_moved_rows):
+    std::vector<uint32_t> x_cons, x_stamp;          //     rating | rewritten constraint word | stamp
     uint32_t* d_mv_cols;       // [4][capacity] mm_move's rows: rating | constraint word | stamp | new slot (allocated at the first mm_move)
     uint8_t* d_mv_group;       // [capacity] ... and their rating groups, the column k_bucket_* take
     uint32_t* h_mwait;         // pinned, as large as d_wt_matched: mm_matches_wait, emission order, r_L words a lobby
@@ -1677,6 +1690,7 @@ extern "C" int mm_reset(mm_engine* e)
         e->r_n = 0;
         e->mw_n = 0;
         e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();   // (the clock itself goes on: include/mm_wait.h)
+        e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
         e->live_upper = 0;
         std::fill(e->tk_last_len.begin(), e->tk_last_len.end(), 0u);
         const int rc = engine_reset_device(e);
@@ -1708,8 +1722,10 @@ static int ensure_staging(mm_engine* e, size_t n)
 // The bucketing of a batch, queued on the engine's stream with the copy of its refusal counter behind it; all pointers
 // are device pointers.  Nothing is waited for: enqueue_device_impl does that for the two enqueue entry points, mm_move
 // puts its own kernel and copies behind this first (one wait for all of it).
+// d_in_stamp (mm_enqueue_stamped only): the batch's own stamps, scattered with the rows instead of the clock.
 static int enqueue_device_launch(mm_engine* e, uint32_t n, const int32_t* d_rating, const uint32_t* d_cons,
-                                 const uint8_t* d_group, const uint32_t* d_slot_sel, uint32_t* d_out_slot)
+                                 const uint8_t* d_group, const uint32_t* d_slot_sel, uint32_t* d_out_slot,
+                                 const uint32_t* d_in_stamp = nullptr)
 {
     const uint32_t blocks = (n + BK_CHUNK - 1) / BK_CHUNK;
     const size_t rows = (size_t)blocks * BK_WAVES;
@@ -1727,9 +1743,15 @@ static int enqueue_device_launch(mm_engine* e, uint32_t n, const int32_t* d_rati
                        e->n_chains, e->d_wave_hist, e->d_counters + 1);
     hipLaunchKernelGGL(k_bucket_scan, dim3(e->n_chains), dim3(BK_THREADS), 0, e->stream, (uint32_t)rows, e->n_chains,
                        e->d_wave_hist, e->d_chains, e->cfg.capacity);
-    hipLaunchKernelGGL(k_bucket_scatter, dim3(blocks), dim3(BK_THREADS), 0, e->stream, n, d_rating, d_cons, d_group, B,
-                       e->n_chains, e->d_wave_hist, e->next_slot, d_slot_sel, e->d_q_rating, e->d_q_cons, e->d_q_slot,
-                       e->d_state, d_out_slot, e->clock_on ? e->d_stamp : (uint32_t*)NULL, e->clock_now);
+    if (d_in_stamp)
+        hipLaunchKernelGGL(k_bucket_scatter<true>, dim3(blocks), dim3(BK_THREADS), 0, e->stream, n, d_rating, d_cons, d_group, B,
+                           e->n_chains, e->d_wave_hist, e->next_slot, d_slot_sel, e->d_q_rating, e->d_q_cons, e->d_q_slot,
+                           e->d_state, d_out_slot, e->d_stamp, e->clock_now, d_in_stamp);
+    else
+        hipLaunchKernelGGL(k_bucket_scatter<false>, dim3(blocks), dim3(BK_THREADS), 0, e->stream, n, d_rating, d_cons, d_group, B,
+                           e->n_chains, e->d_wave_hist, e->next_slot, d_slot_sel, e->d_q_rating, e->d_q_cons, e->d_q_slot,
+                           e->d_state, d_out_slot, e->clock_on ? e->d_stamp : (uint32_t*)NULL, e->clock_now,
+                           (const uint32_t*)NULL);
     HIPCHK(e, hipGetLastError());
     if (timing) HIPCHK(e, hipEventRecord(e->ev[1], e->stream));
     HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, e->d_counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
@@ -1739,10 +1761,11 @@ static int enqueue_device_launch(mm_engine* e, uint32_t n, const int32_t* d_rati
 // Shared by both enqueue entry points; all pointers are device pointers.
 static int enqueue_device_impl(mm_engine* e, uint32_t n, const int32_t* d_rating, const uint32_t* d_cons,
                                const uint8_t* d_group, const uint32_t* d_slot_sel, uint32_t* d_out_slot,
-                               uint32_t* rejected, float* bucket_ms, uint32_t* h_out_slot = nullptr)
+                               uint32_t* rejected, float* bucket_ms, uint32_t* h_out_slot = nullptr,
+                               const uint32_t* d_in_stamp = nullptr)
 {
     const bool timing = (e->cfg.flags & MM_CFG_TIMING) != 0;
-    MMTRY(enqueue_device_launch(e, n, d_rating, d_cons, d_group, d_slot_sel, d_out_slot));
+    MMTRY(enqueue_device_launch(e, n, d_rating, d_cons, d_group, d_slot_sel, d_out_slot, d_in_stamp));
     // the handles travel with the counter: one round trip to the device per enqueue, not two (a stream enqueues every tick)
     if (h_out_slot) HIPCHK(e, hipMemcpyAsync(h_out_slot, d_out_slot, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -1788,14 +1811,15 @@ static int pick_free_slots(const mm_engine* e, uint32_t n, std::vector<uint32_t>
     return sel.size() == n;
 }
 
-extern "C" int mm_enqueue(mm_engine* e, uint32_t n, const int32_t* rating, const uint32_t* cons,
-                          const uint8_t* group, uint32_t* out_slot, mm_enqueue_stats* st)
+// mm_enqueue, and with `stamp` mm_enqueue_stamped (include/mm_wait.h): the same call in every respect but the stamps.
+static int enqueue_host(mm_engine* e, uint32_t n, const int32_t* rating, const uint32_t* cons, const uint8_t* group,
+                        const uint32_t* stamp, bool stamped, uint32_t* out_slot, mm_enqueue_stats* st)
 {
     return guarded([&]() -> int {
-        if (!e || (n && (!rating || !cons))) return MM_ERR_INVALID_ARG;
-        if (e->poisoned) return MM_ERR_STATE;
+        if (!e || (n && (!rating || !cons || (stamped && !stamp)))) return MM_ERR_INVALID_ARG;
+        if (e->poisoned || (stamped && !e->clock_on)) return MM_ERR_STATE;
         ON_ENGINE_DEVICE(e);
-        RoctxRange rr("mm_enqueue");
+        RoctxRange rr(stamped ? "mm_enqueue_stamped" : "mm_enqueue");
         const double t0 = host_now_ms();
         if (st) memset(st, 0, sizeof(*st));
         if (n == 0) return MM_OK;
@@ -1805,7 +1829,19 @@ extern "C" int mm_enqueue(mm_engine* e, uint32_t n, const int32_t* rating, const
         if (group)
             for (uint32_t i = 0; i < n; ++i)
                 if (group[i] >= e->cfg.n_groups) return MM_ERR_INVALID_ARG;
+        if (stamped)                                          // a stamp ahead of the clock would read as an age near 2^32
+            for (uint32_t i = 0; i < n; ++i)
+                if ((int32_t)(e->clock_now - stamp[i]) < 0) return MM_ERR_RANGE;
         MMTRY(ensure_staging(e, n));
+        if (stamped) {
+            if (e->in_stamp_cap < n) {                         // beside d_in_*, and as large: an engine that never calls this has none
+                mem_release(e, e->d_in_stamp);
+                e->in_stamp_cap = 0;
+                MMTRY(dev_alloc(e, e->d_in_stamp, e->in_cap * sizeof(uint32_t)));
+                e->in_stamp_cap = e->in_cap;
+            }
+            HIPCHK(e, hipMemcpyAsync(e->d_in_stamp, stamp, n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+        }
         if (!contiguous)
             HIPCHK(e, hipMemcpyAsync(e->d_in_sel, sel.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
         HIPCHK(e, hipMemcpyAsync(e->d_in_rating, rating, n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
@@ -1817,7 +1853,8 @@ extern "C" int mm_enqueue(mm_engine* e, uint32_t n, const int32_t* rating, const
         uint32_t* slots = out_slot;
         if (!slots) { tmp.resize(n); slots = tmp.data(); }
         MMTRY(enqueue_device_impl(e, n, e->d_in_rating, e->d_in_cons, group ? e->d_in_group : NULL,
-                                  contiguous ? NULL : e->d_in_sel, e->d_in_slot, &rejected, &bms, slots));   // syncs: `sel` outlives the copy
+                                  contiguous ? NULL : e->d_in_sel, e->d_in_slot, &rejected, &bms, slots,
+                                  stamped ? e->d_in_stamp : NULL));   // syncs: `sel` outlives the copy
         for (uint32_t i = 0; i < n; ++i)
             if (slots[i] != MM_NO_SLOT) e->h_state[slots[i]] = MM_ST_LIVE;
         e->next_slot = contiguous ? (uint32_t)(((unsigned long long)e->next_slot + n) % e->cfg.capacity)
@@ -1831,6 +1868,18 @@ extern "C" int mm_enqueue(mm_engine* e, uint32_t n, const int32_t* rating, const
         }
         return MM_OK;
     });
+}
+
+extern "C" int mm_enqueue(mm_engine* e, uint32_t n, const int32_t* rating, const uint32_t* cons,
+                          const uint8_t* group, uint32_t* out_slot, mm_enqueue_stats* st)
+{
+    return enqueue_host(e, n, rating, cons, group, NULL, false, out_slot, st);
+}
+
+extern "C" int mm_enqueue_stamped(mm_engine* e, uint32_t n, const int32_t* rating, const uint32_t* cons,
+                                  const uint8_t* group, const uint32_t* stamp, uint32_t* out_slot, mm_enqueue_stats* st)
+{
+    return enqueue_host(e, n, rating, cons, group, stamp, true, out_slot, st);
 }
 
 extern "C" int mm_enqueue_device(mm_engine* e, uint32_t n, const int32_t* d_rating, const uint32_t* d_cons,
@@ -3395,6 +3444,7 @@ extern "C" int mm_expire(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t
     ON_ENGINE_DEVICE(e);
     RoctxRange rr("mm_expire");
     e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
+    e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
     if (n_expired) *n_expired = 0;
     bool marked_on_device = false;
     const int rc = guarded([&]() -> int { return expire_impl(e, mode, max_age, n_expired, &marked_on_device); });
@@ -3519,6 +3569,7 @@ extern "C" int mm_move(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint3
     ON_ENGINE_DEVICE(e);
     RoctxRange rr("mm_move");
     e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
+    e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
     if (n_selected) *n_selected = 0;
     if (n_refused) *n_refused = 0;
     bool marked_on_device = false;
@@ -3546,6 +3597,98 @@ extern "C" int mm_moved(mm_engine* e, uint32_t first, uint32_t count, uint32_t* 
     if (first > n || count > n - first) return MM_ERR_RANGE;
     if (count == 0 || !new_slot) return MM_OK;
     memcpy(new_slot, &e->x_new[first], (size_t)count * sizeof(uint32_t));
+    return MM_OK;
+}
+
+// mm_move_out = the first half of mm_move: the selection and marks of mm_expire with k_move_scatter's rows beside the
+// list, and no enqueue — no slot is picked, no other queue touched.  One round trip for the count (nothing selected:
+// nothing more is launched), then the six columns come back together.  Failures as expire_impl's.
+static int move_out_impl(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
+                         uint32_t* n_selected, bool* marked_on_device)
+{
+    MMTRY(move_alloc(e));
+    const WaitParams P = wait_params(e, from_mode, max_age);
+    const uint32_t grid = wait_grid(e), cap = e->cfg.capacity;
+    uint32_t* const d_total = e->d_wt_rows + (size_t)e->wt_max_chunks * WT_ROWS;
+    hipLaunchKernelGGL(k_wait_count, dim3(grid), dim3(WT_THREADS), 0, e->stream, P);
+    hipLaunchKernelGGL(k_wait_scan, dim3(1), dim3(WT_THREADS), 0, e->stream, P);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const uint32_t k = e->h_counters[1];
+    if (k > cap) return MM_ERR_INTERNAL;
+    if (k == 0u) return MM_OK;
+    MoveCols M;
+    M.q_rating = e->d_q_rating;
+    M.q_cons = e->d_q_cons;
+    M.rating = (int32_t*)e->d_mv_cols;
+    M.cons = e->d_mv_cols + cap;
+    M.stamp = e->d_mv_cols + 2u * (size_t)cap;
+    M.group = e->d_mv_group;
+    M.keep = ~cons_clear & MM_CONS_USER_MASK & ~0xFu;
+    M.to_mode = to_mode;
+    *marked_on_device = true;
+    hipLaunchKernelGGL(k_move_scatter, dim3(grid), dim3(WT_THREADS), 0, e->stream, P, M);
+    HIPCHK(e, hipGetLastError());
+    e->x_slot.resize(k); e->x_group.resize(k); e->x_age.resize(k);
+    e->x_rating.resize(k); e->x_cons.resize(k); e->x_stamp.resize(k);
+    HIPCHK(e, hipMemcpyAsync(e->x_slot.data(), P.out_slot, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->x_group.data(), P.out_group, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->x_age.data(), P.out_age, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->x_rating.data(), M.rating, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->x_cons.data(), M.cons, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->x_stamp.data(), M.stamp, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    // the host mirrors, as mm_cancel leaves them for these slots
+    uint32_t marked = 0;
+    for (uint32_t i = 0; i < k; ++i) {
+        const uint32_t sl = e->x_slot[i];
+        if (sl < cap && e->h_state[sl] == MM_ST_LIVE) { e->h_state[sl] = MM_ST_CANCELLED; ++marked; }
+    }
+    e->cancel_pending += k;
+    if (n_selected) *n_selected = k;
+    return marked == k ? MM_OK : MM_ERR_INTERNAL;             // (the device's ActiveUser mirror and the host's disagree)
+}
+
+extern "C" int mm_move_out(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
+                           uint32_t* n_selected)
+{
+    if (!e || from_mode >= e->cfg.n_modes || to_mode >= MM_MAX_MODES || from_mode == to_mode ||
+        (cons_clear & (~MM_CONS_USER_MASK | 0xFu)))
+        return MM_ERR_INVALID_ARG;
+    if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
+    ON_ENGINE_DEVICE(e);
+    RoctxRange rr("mm_move_out");
+    e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
+    e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
+    if (n_selected) *n_selected = 0;
+    bool marked_on_device = false;
+    const int rc = guarded([&]() -> int {
+        return move_out_impl(e, from_mode, to_mode, max_age, cons_clear, n_selected, &marked_on_device);
+    });
+    if (rc != MM_OK) {
+        // as mm_expire: no half-filled list, and an engine whose device may hold marks the host does not is poisoned
+        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear();
+        e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
+        if (n_selected) *n_selected = 0;
+        if (marked_on_device) {
+            (void)hipStreamSynchronize(e->stream);
+            e->poisoned = true;
+        }
+    }
+    return rc;
+}
+
+extern "C" int mm_moved_rows(mm_engine* e, uint32_t first, uint32_t count, int32_t* rating, uint32_t* cons, uint32_t* stamp)
+{
+    if (!e) return MM_ERR_INVALID_ARG;
+    if (e->poisoned) return MM_ERR_STATE;
+    const size_t n = e->x_stamp.size();
+    if (first > n || count > n - first) return MM_ERR_RANGE;
+    if (count == 0) return MM_OK;
+    if (rating) memcpy(rating, &e->x_rating[first], (size_t)count * sizeof(int32_t));
+    if (cons) memcpy(cons, &e->x_cons[first], (size_t)count * sizeof(uint32_t));
+    if (stamp) memcpy(stamp, &e->x_stamp[first], (size_t)count * sizeof(uint32_t));
     return MM_OK;
 }
 

@@ -267,7 +267,8 @@ __global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P)
     wait_scatter_body<false>(P, none);
 }
 
-// mm_move's scatter: the list as k_wait_scatter writes it, plus the rows for k_bucket_*.
+// mm_move's and mm_move_out's scatter: the list as k_wait_scatter writes it, plus the rows — for k_bucket_* on this engine
+// (mm_move), or for the host to hand to another engine's mm_enqueue_stamped (mm_move_out reads rating, word and stamp back).
 __global__ __launch_bounds__(WT_THREADS) void k_move_scatter(WaitParams P, MoveCols M) { wait_scatter_body<true>(P, M); }
 
 // After the bucketing of a move: an accepted row's new slot carries the stamp of the slot the player left

@@ -10,7 +10,12 @@ rank owns one engine and the chains assigned to it, players are routed by
 `find_rating_group_by_rating/1` (lib/generic/worker.ex:46-53) and their `"game-mode"`
 (lib/search/worker.ex:294) exactly as the Generic worker routes them to per-group AMQP
 queues.  torch.distributed (RCCL on GPUs, gloo in the CPU tests) is only used to sum
-counters / gather results.
+counters / gather results — and, off the matching path, to carry the players of an mm_move
+(include/mm_wait.h) from the rank that owns chain (from_mode, g) to the one that owns chain
+(to_mode, g): `ShardedSearch.move` is mm_move_out on every rank, one all-gather of the selected
+rows with their stamps, mm_enqueue_stamped on the new owners.  Unlike mm_move on one engine it is
+not all-or-nothing: a destination without room raises on every rank after the sources have expired
+their players.
 
 What this does NOT do, and why: split ONE chain across ranks with a
 rating-bucket halo all-gather.  A chain has one open lobby (lobby_state.ex:90-91) and one
@@ -25,7 +30,7 @@ import hashlib
 
 import numpy as np
 
-from ._abi import MMConfig, NO_SLOT
+from ._abi import MMConfig, MMError, NO_SLOT
 
 
 def rating_groups(cfg: MMConfig, rating) -> np.ndarray:
@@ -173,15 +178,53 @@ class ShardedSearch:
         return idx, slots
 
     def move(self, from_mode, to_mode, max_age, cons_clear=0):
-        """mm_move (include/mm_wait.h) on a search that is ONE rank: chain (from_mode, g) and chain (to_mode, g) may have
-        different owners, and nothing here carries a player from one engine to another.  The moved players keep their
-        global arrival index under their new slot."""
+        """mm_move (include/mm_wait.h).  The moved players keep their global arrival index under their new slot.
+        On ONE rank it is the engine's mm_move.  On several, chain (from_mode, g) and chain (to_mode, g) may have different
+        owners, and EVERY rank calls this collectively: mm_move_out here, an all-gather of the selected rows (rating group,
+        rating, rewritten constraint word, stamp, global index), concatenated in rank order and sorted stably by rating group
+        — every chain (from_mode, g) has one owner, so that is the single engine's mm_expired order — and each rank takes the
+        rows whose chain (to_mode, group) it owns through mm_enqueue_stamped, stamps and all.
+        -> (slots, group, age, new_slots) over the rows THIS rank selected; new_slots is NO_SLOT where the row was refused or
+        went to another rank.  self.last_move = {"selected", "taken", "refused"}: this rank's selected rows, the rows it took in
+        and the rows it refused as a destination — each sums over the ranks to the one-engine figure.
+        Across ranks the move is NOT all-or-nothing: a destination without room raises MMError(MM_ERR_FULL) on every rank,
+        after the sources have expired their players and the destinations WITH room have taken theirs in (those players
+        wait there under their global index)."""
         if self.world_size != 1:
-            raise NotImplementedError("mm_move across ranks: chains (from_mode, g) and (to_mode, g) may have different owners")
+            return self._move_across_ranks(from_mode, to_mode, max_age, cons_clear)
         got = self.engine.move(from_mode, to_mode, max_age, cons_clear)
         ok = got[3] != NO_SLOT
         self.local_to_global[got[3][ok].astype(np.int64)] = self.local_to_global[got[0][ok].astype(np.int64)]
         return got
+
+    def _move_across_ranks(self, from_mode, to_mode, max_age, cons_clear):
+        if not 0 <= int(to_mode) < self.cfg.n_modes:
+            raise MMError(-1, "move across ranks (to_mode)")
+        old, group, age, rating, cons, stamp = self.engine.move_out(from_mode, to_mode, max_age, cons_clear)
+        gid = self.local_to_global[old.astype(np.int64)]
+        rows = np.stack([group.astype(np.int64), rating.astype(np.int64), cons.astype(np.int64), stamp.astype(np.int64),
+                         gid, np.full(old.size, self.rank, np.int64), np.arange(old.size, dtype=np.int64)], axis=1)
+        rows = np.concatenate(self.gather_rows(rows.reshape(-1, 7)))
+        rows = rows[np.argsort(rows[:, 0], kind="stable")]
+        rows = rows[self.sharding.chain_owner[to_mode, rows[:, 0]] == self.rank]
+        new = np.full(old.size, NO_SLOT, dtype=np.uint32)
+        status, got = 0, np.zeros(0, np.uint32)
+        try:
+            if rows.shape[0]:
+                got = self.engine.enqueue_stamped(rows[:, 1].astype(np.int32), rows[:, 2].astype(np.uint32),
+                                                  rows[:, 3].astype(np.uint32), rows[:, 0].astype(np.uint8))
+        except MMError as ex:
+            status = ex.status
+        ok = got != NO_SLOT
+        self.local_to_global[got[ok].astype(np.int64)] = rows[ok, 4]   # (before the raise below: a rank with room has taken its rows)
+        # one status for all: a rank that raised alone would leave the others waiting in their next collective
+        status = int(-max(self.max_over_ranks([-status])))
+        if status:
+            raise MMError(status, "move across ranks")
+        here = ok & (rows[:, 5] == self.rank)
+        new[rows[here, 6]] = got[here]
+        self.last_move = {"selected": int(old.size), "taken": int(ok.sum()), "refused": int((~ok).sum())}
+        return old, group, age, new
 
     def tick(self, mode=0):
         return self.engine.tick(mode)
@@ -193,13 +236,37 @@ class ShardedSearch:
         return self.local_to_global[matches.slots.astype(np.int64)]
 
     @staticmethod
-    def sum_over_ranks(values):
-        """Counters summed over the ranks (the only collective of the path)."""
+    def sum_over_ranks(values, op="SUM"):
+        """Counters summed over the ranks (the only collective of the matching path)."""
         import torch
         import torch.distributed as dist
         t = torch.tensor([float(v) for v in values], dtype=torch.float64)
         if dist.is_available() and dist.is_initialized():
             if dist.get_backend() == "nccl":
                 t = t.cuda()
-            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            dist.all_reduce(t, op=getattr(dist.ReduceOp, op))
         return t.cpu().tolist()
+
+    @staticmethod
+    def max_over_ranks(values):
+        return ShardedSearch.sum_over_ranks(values, "MAX")
+
+    @staticmethod
+    def gather_rows(rows):
+        """An (n, c) int64 array of every rank, in rank order (n differs between ranks: the counts go first, the rows
+        padded to the longest).  No process group: this rank's alone."""
+        import torch
+        import torch.distributed as dist
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if not (dist.is_available() and dist.is_initialized()):
+            return [rows]
+        dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
+        world = dist.get_world_size()
+        counts = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
+        dist.all_gather(counts, torch.tensor([rows.shape[0]], dtype=torch.int64, device=dev))
+        counts = [int(c.item()) for c in counts]
+        pad = np.zeros((max(counts + [1]), rows.shape[1]), np.int64)
+        pad[:rows.shape[0]] = rows
+        parts = [torch.zeros(pad.shape, dtype=torch.int64, device=dev) for _ in range(world)]
+        dist.all_gather(parts, torch.from_numpy(pad).to(dev))
+        return [p.cpu().numpy()[:k] for p, k in zip(parts, counts)]

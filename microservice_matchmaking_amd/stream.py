@@ -61,7 +61,11 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
     `fallback`: rules [(from_mode, to_mode, after_ms, cons_clear)] of mm_move (include/mm_wait.h): every period, after the
     clock is set and the arrivals are in and before the expiry, whoever has waited in from_mode for longer than after_ms
     moves to to_mode with its stamp, the rules in list order (so tiers chain within a period).  The clock runs as for
-    ttl_ms; the result also holds `moved` and `refused` (players per rule), `wait_ms` and `depth_max`.  One rank only."""
+    ttl_ms; the result also holds `moved` and `refused` (players per rule: the ones THIS rank selected, and the ones it
+    refused — on several ranks every rank calls the move collectively, sharding.ShardedSearch.move, and the sums over the
+    ranks are the one-engine figures), `wait_ms` and `depth_max`.  A move that finds a destination without room
+    (MM_ERR_FULL, on every rank) ends the stream like a refused batch: `full_at_s`.  With a fallback on several ranks a batch
+    refused on ONE rank ends the stream on all of them (one all-reduced flag a period): the moves are collectives."""
     assert batches is None or len(batches) == len(schedule)
     fallback = list(fallback or ())
     clocked = ttl_ms is not None or bool(fallback)
@@ -104,21 +108,34 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
             t0 = time.perf_counter()
             if clocked:
                 search.engine.clock_set(int(round(t_close * 1e3)))  # this period's arrivals are stamped with its end
+            refused_here = False
             try:
                 search.enqueue(rating, cons, first_global_index=first)
             except MMError as ex:
                 if ex.status != -4:                                 # MM_ERR_FULL: fewer than n free slots in the pool
                     raise
+                refused_here = True
+            if fallback and search.world_size != 1:
+                # the moves below are collectives: a rank that left the loop alone would leave the others waiting in them,
+                # so with a fallback on several ranks a batch refused on ONE rank ends the stream on all
+                refused_here = max(search.max_over_ranks([1.0 if refused_here else 0.0])) > 0
+            if refused_here:
                 # The batch is refused as a whole and nothing of it was queued (include/mm_engine.h): for the
                 # service these deliveries stay unacked in the broker (prefetch back-pressure,
                 # lib/search/worker.ex:29) until lobbies free slots.  The stream ends here and says so.
                 full_at_s = t_open
                 break
             first += n
-            for i, (src, dst, after_ms, cons_clear) in enumerate(fallback):
-                got = search.move(src, dst, int(after_ms), int(cons_clear))
-                moved[i] += int(got[0].size)
-                refused[i] += int(search.engine.last_move["refused"])
+            try:
+                for i, (src, dst, after_ms, cons_clear) in enumerate(fallback):
+                    got = search.move(src, dst, int(after_ms), int(cons_clear))
+                    moved[i] += int(got[0].size)
+                    refused[i] += int((search.engine if search.world_size == 1 else search).last_move["refused"])
+            except MMError as ex:
+                if ex.status != -4:                                 # MM_ERR_FULL: no room for the moved players where they go
+                    raise
+                full_at_s = t_open
+                break
             if ttl_ms is not None:
                 for md in range(n_modes):
                     expired[md] += int(search.engine.expire(md, int(ttl_ms))[0].size)

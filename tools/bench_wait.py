@@ -15,8 +15,14 @@ route an owner had before it, timed in the same process in turns: mm_expire, mm_
 constraint word from a host table, mm_enqueue of the same rows.  The enqueue and tick figures above are restated in the
 same output (they must not have moved: k_bucket_scatter is untouched).
 
+--carry adds, on the same two-mode engine and pool, the two-call route that carries players between engines, run on one
+engine — mm_move_out, mm_expired, mm_moved_rows, mm_enqueue_stamped of the same rows — in turns with mm_move and with the
+host route, at the same three shares.  What to expect at 1 %: between the two (it spares the host gather of the host route
+and adds one 4-byte column each way to mm_move).  All three must leave the same queue depths.
+
 Usage (GPU box, repo root):  python tools/bench_wait.py [--steps 30] [--players 1000000] > profiles/wait_1m.json
-                             python tools/bench_wait.py --move > profiles/wait_move_1m.json"""
+                             python tools/bench_wait.py --move > profiles/wait_move_1m.json
+                             python tools/bench_wait.py --carry > profiles/wait_carry_1m.json"""
 import argparse
 import json
 import os
@@ -92,6 +98,67 @@ def measure_move(args, rating, cons, d_rating, d_cons, now):
     return out
 
 
+def measure_carry(args, rating, cons, d_rating, d_cons, now):
+    """mm_move, the two-call route (mm_move_out + mm_expired + mm_moved_rows + mm_enqueue_stamped) and the host route, in turns
+    on one engine: the same pool, the same old and young batch, the same players selected, the same queue depths behind."""
+    from microservice_matchmaking_amd import Engine, make_config, mode_1v1
+    n = args.players
+    cap = 2 << (n - 1).bit_length()
+    cfg = make_config([mode_1v1(window=25, region_filter=True), mode_1v1(window=100)], capacity=cap, timing=True)
+    out = {}
+    routes = ("move", "carry", "host")
+    with Engine(cfg) as eng:
+        eng.clock_set(now)
+        for label, frac in (("0pct", 0.0), ("1pct", 0.01), ("50pct", 0.5)):
+            old = int(n * frac)
+            t = {r: [] for r in routes}
+            parts = {"move_out_ms": [], "enqueue_stamped_ms": []}
+            depth = {}
+            for k in range(args.warmup + args.steps):
+                for route in routes[k % 3:] + routes[:k % 3]:
+                    eng.reset()
+                    now += 10
+                    eng.clock_set(now)
+                    if old:
+                        eng.enqueue_device(d_rating[:old], d_cons[:old])
+                    now += 100
+                    eng.clock_set(now)
+                    eng.enqueue_device(d_rating[old:], d_cons[old:])        # slot i holds player i: the owner's table is (rating, cons)
+                    t0 = time.perf_counter()
+                    if route == "move":
+                        got = eng.move(0, 1, 50)
+                        t1 = time.perf_counter()
+                        assert got[0].size == old and (got[3] != 0xFFFFFFFF).all()
+                    elif route == "carry":
+                        slots, group, _, r2, c2, s2 = eng.move_out(0, 1, 50)
+                        ta = time.perf_counter()
+                        new = eng.enqueue_stamped(r2, c2, s2, group.astype(np.uint8)) if old else np.zeros(0, np.uint32)
+                        t1 = time.perf_counter()
+                        assert slots.size == old and new.size == old and (s2 == now - 100).all()
+                        if k >= args.warmup:
+                            parts["move_out_ms"].append((ta - t0) * 1e3)
+                            parts["enqueue_stamped_ms"].append((t1 - ta) * 1e3)
+                    else:
+                        slots, group, _ = eng.expire(0, 50)
+                        r2 = rating[slots]
+                        c2 = (cons[slots] & np.uint32(0x000FFFF0)) | np.uint32(1)
+                        new = eng.enqueue(r2, c2, group.astype(np.uint8)) if old else np.zeros(0, np.uint32)
+                        t1 = time.perf_counter()
+                        assert slots.size == old and new.size == old
+                    if k >= args.warmup:
+                        t[route].append((t1 - t0) * 1e3)
+                    depth[route] = (eng.queue_depth(0).tolist(), eng.queue_depth(1).tolist())
+            assert depth["move"] == depth["host"] == depth["carry"], depth
+            m = {r: med(t[r]) for r in routes}
+            out[label] = {"selected": old, "move_call_ms": spread(t["move"]), "carry_route_ms": spread(t["carry"]),
+                          "host_route_ms": spread(t["host"]), "carry_route_parts_ms": {k: med(v) for k, v in parts.items()},
+                          "carry_over_move": m["carry"] / m["move"], "carry_over_host": m["carry"] / m["host"],
+                          "carry_between_move_and_host": bool(m["move"] <= m["carry"] <= m["host"])}
+    out["note"] = ("host time around the calls, the wrapper's numpy buffers included; the carry route and mm_move keep the original "
+                   "stamp, the host route's stamp is the time of the re-enqueue.  capacity %d" % cap)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
@@ -101,6 +168,8 @@ def main():
                     help="create the engine with the clock before the one without (two engines are two sets of allocations: "
                          "does a difference between their ticks follow the clock or the engine's place in memory?)")
     ap.add_argument("--move", action="store_true", help="also measure mm_move beside the host route it replaces")
+    ap.add_argument("--carry", action="store_true",
+                    help="also measure mm_move_out + mm_enqueue_stamped on one engine beside mm_move and the host route")
     args = ap.parse_args()
     assert args.steps >= 20, "medians of at least 20 steps"
     import torch
@@ -181,6 +250,7 @@ def main():
         expire[label] = {"expired": old, "call_ms": spread(call)}
 
     move = measure_move(args, rating, cons, d_rating, d_cons, now) if args.move else None
+    carry = measure_carry(args, rating, cons, d_rating, d_cons, now) if args.carry else None
 
     bucket = med(rows["off"]["bucket_ms"])
     out = {
@@ -204,6 +274,8 @@ def main():
     }
     if move is not None:
         out["move"] = move
+    if carry is not None:
+        out["carry"] = carry
     print(json.dumps(out, indent=1))
     off.close()
     on.close()
