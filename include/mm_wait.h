@@ -1,6 +1,7 @@
 /*
  * mm_wait.h — the engine's clock: arrival stamps, expiry of long-waiting players, their move to a
- * fallback mode — inside one engine or carried to another one with their rows and stamps — wait times.
+ * fallback mode — inside one engine or carried to another one with their rows and stamps — the
+ * rotation of a blocked lobby's players to their queue's tail, wait times.
  *
  * An extension of include/mm_engine.h (same rules: plain C types, status codes and never an
  * abort, every entry point selects the engine's HIP device itself, MM_ERR_STATE on an engine
@@ -35,6 +36,14 @@
  * for word — the same new slots (out_slot == mm_moved's column), the same queue order, the same
  * stamps: slot allocation steps over LIVE and CANCELLED slots alike, so marking the old slots before
  * or after the new ones are picked makes no difference.
+ *
+ * Un-blocking a chain is mm_rotate.  A chain has one open lobby and a tick ends with the first pass
+ * that seats nobody (docs/MATCH_CHECK.md section 4), so an anchor nobody in the queue fits stalls
+ * everybody behind it.  mm_rotate is mm_move onto the players' OWN chains, selected by the stored
+ * lobbies instead of by age: the seats of every short-handed lobby with a queue behind it are marked
+ * as mm_cancel marks them and the same players join the tail of their queue with the stamps they had.
+ * The next tick drops the emptied lobby (the stale-lobby rule) and the queue's head anchors a new one.
+ * No new matching rule: to the oracle it is mo_cancel plus mo_enqueue of the same rows.
  *
  * Not here: the NIF binding (native/mm_nif.c; INTEGRATION.md section 7 names the calls to add);
  * an ALL-OR-NOTHING move across engines (chain (A, g) and chain (B, g) of a ShardedSearch may have
@@ -91,11 +100,11 @@ int mm_clock_get(const mm_engine* e, uint32_t* now, uint32_t* enabled);
  * (lib/models/active_user.ex:57-66) is what each expiry amounts to. */
 int mm_expire(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t* n_expired);
 
-/* Entries [first, first + count) of the last mm_expire's, mm_move's or mm_move_out's list: the slot, its rating
+/* Entries [first, first + count) of the last mm_expire's, mm_move's, mm_move_out's or mm_rotate's list: the slot, its rating
  * group and the age it had reached.  Order: rating group ascending; within a group the stored lobby's
  * seats in the order mm_lobby_state lists them, then the queue from head to tail — the same on
  * every run, so an owner can publish its "no match found" replies from it.  Readable until the
- * next mm_expire, mm_move, mm_move_out, mm_reset or mm_restore.  Any output pointer may be NULL.
+ * next mm_expire, mm_move, mm_move_out, mm_rotate, mm_reset or mm_restore.  Any output pointer may be NULL.
  * MM_ERR_RANGE: the range is not inside the list.  Reference: none. */
 int mm_expired(mm_engine* e, uint32_t first, uint32_t count, uint32_t* slots, uint32_t* group,
                uint32_t* age);
@@ -126,7 +135,7 @@ int mm_expired(mm_engine* e, uint32_t first, uint32_t count, uint32_t* slots, ui
 int mm_move(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age,
             uint32_t cons_clear, uint32_t* n_selected, uint32_t* n_refused);
 
-/* Entries [first, first + count) of the last mm_move's list, fourth column: the new slot, or
+/* Entries [first, first + count) of the last mm_move's or mm_rotate's list, fourth column: the new slot, or
  * MM_NO_SLOT for a refused player.  Range rule and lifetime as mm_expired (after an mm_expire the
  * column is empty).  Reference: none. */
 int mm_moved(mm_engine* e, uint32_t first, uint32_t count, uint32_t* new_slot);
@@ -148,10 +157,40 @@ int mm_move_out(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max
 /* Entries [first, first + count) of the last mm_move_out's list, the rows: the rating, the
  * constraint word already rewritten to ((cons & ~cons_clear) & MM_CONS_USER_MASK & ~0xF) | to_mode,
  * and the stamp (the clock at the call minus the age mm_expired reports).  Range rule and lifetime
- * as mm_expired; the columns are empty after mm_expire, mm_move, mm_reset and mm_restore.  Any
+ * as mm_expired; the columns are empty after mm_expire, mm_move, mm_rotate, mm_reset and mm_restore.  Any
  * output pointer may be NULL.  Reference: none. */
 int mm_moved_rows(mm_engine* e, uint32_t first, uint32_t count, int32_t* rating, uint32_t* cons,
                   uint32_t* stamp);
+
+/* Rotates the blocked lobbies of `mode`.  For every rating group g, ascending: S = the LIVE seats of
+ * the stored lobby of chain (mode, g) in mm_lobby_state's order, len = the queue length mm_queue_slots
+ * reports at this moment (entries cancelled and not yet purged count).  The chain is selected iff
+ * 1 <= |S| <= max_seated and len >= min_queue, and then ALL of S is: all seats of a chain or none.
+ * The list is in mm_expire's order restricted to seats (group ascending, then S's order), and the
+ * effect is exactly mm_move's with to_mode == from_mode and cons_clear == 0 over that selection:
+ *   the old slot   is marked as mm_cancel marks it and held until the mode's next purge — a rotation
+ *                  of k players needs k FREE slots beside them;
+ *   the new entry  goes to the tail of the player's own chain, in list order, with its rating and
+ *                  its constraint word unchanged and rating group g as the group override (a player
+ *                  placed by override stays in its group), in a new slot taken from the ring exactly
+ *                  as mm_enqueue takes them for a batch of *n_selected;
+ *   the stamp      of the new slot is the old slot's: the player's age goes on.
+ * Nobody can be refused (the mode seats them already).  mm_expired reads old slot, group and age,
+ * mm_moved the new slots, mm_moved_rows reads empty; lifetime of the lists as after mm_move.  The
+ * host mirrors end up as after mm_cancel plus mm_enqueue.  Nothing selected: MM_OK, *n_selected = 0,
+ * no slot is taken, the lists are empty.  *n_selected may be NULL.
+ * MM_ERR_INVALID_ARG: no such mode, max_seated == 0.  MM_ERR_STATE: the clock was never set.
+ * MM_ERR_FULL: fewer FREE slots than selected players — all or nothing: nothing is marked, queues,
+ * stamps, the ring position and the lists (empty) are as if nobody had been selected.  Any other
+ * failure once the first mark may be on the device leaves the engine MM_ERR_STATE until mm_reset /
+ * mm_restore, as for mm_move.  Nothing new goes into a snapshot; results never depend on mm_tuning.
+ * Cost: no queue is streamed — at most n_groups x 32 seats are looked at, two waits on the stream
+ * (one when nothing is selected).
+ * Reference: none (requeue_player/5, lib/search/worker.ex:239-248, requeues the player that did NOT
+ * fit, never the lobby it did not fit into); to the oracle a rotation is mo_cancel of the listed
+ * slots plus mo_enqueue of the same rows with their groups. */
+int mm_rotate(mm_engine* e, uint32_t mode, uint32_t max_seated, uint32_t min_queue,
+              uint32_t* n_selected);
 
 /* mm_enqueue (include/mm_engine.h) in every respect — slot choice, MM_ERR_FULL, the `group`
  * override, refused rows, out_slot, st — except that accepted player i is stamped stamp[i] instead

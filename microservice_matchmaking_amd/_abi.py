@@ -248,6 +248,9 @@ def bind(lib, prefix):
         f("enqueue_stamped").argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.POINTER(MMEnqueueStats)]
         f("enqueue_stamped").restype = C.c_int
+    if hasattr(lib, prefix + "rotate"):                   # include/mm_wait.h: a blocked lobby's players rejoin their queue's tail
+        f("rotate").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
+        f("rotate").restype = C.c_int
     return lib
 
 
@@ -518,6 +521,19 @@ class EngineBase:
         self._check(self._fn("expired")(self._h, 0, k, _ptr(slots), _ptr(group), _ptr(age)), "expired")
         self._check(self._fn("moved_rows")(self._h, 0, k, _ptr(rating), _ptr(cons), _ptr(stamp)), "moved_rows")
         return slots, group, age, rating, cons, stamp
+
+    def rotate(self, mode, max_seated, min_queue=1):
+        """mm_rotate + mm_expired + mm_moved: in every rating group of `mode` whose stored lobby holds 1..max_seated LIVE seats
+        in front of a queue of at least min_queue entries, ALL those seats leave as if cancelled and the same players join the
+        tail of their own queue — rating, constraint word, rating group and stamp unchanged — so the next tick starts a new
+        lobby from the queue's head.  -> (slots, group, age, new_slots), group ascending, mm_lobby_state's order within."""
+        n = C.c_uint32()
+        self._check(self._fn("rotate")(self._h, mode, int(max_seated), int(min_queue), C.byref(n)), "rotate")
+        k = int(n.value)
+        slots, group, age, new = (np.empty(k, dtype=np.uint32) for _ in range(4))
+        self._check(self._fn("expired")(self._h, 0, k, _ptr(slots), _ptr(group), _ptr(age)), "expired")
+        self._check(self._fn("moved")(self._h, 0, k, _ptr(new)), "moved")
+        return slots, group, age, new
 
     def enqueue_stamped(self, rating, cons, stamp, group=None):
         """mm_enqueue_stamped: `enqueue`, every accepted player stamped stamp[i] instead of the clock.  -> slots."""

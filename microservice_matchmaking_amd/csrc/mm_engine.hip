@@ -3692,6 +3692,108 @@ extern "C" int mm_moved_rows(mm_engine* e, uint32_t first, uint32_t count, int32
     return MM_OK;
 }
 
+// mm_rotate = mm_move onto the players' own chains, selected by the stored lobbies instead of by age: no queue is
+// streamed, k_rotate_count and k_rotate_scatter are one workgroup each over the mode's LobbyDev records.  As in move_impl
+// the count comes back BEFORE anything is marked (pick_free_slots, MM_ERR_FULL with nothing changed); then the scatter,
+// the stamped bucketing of the gathered rows (k_bucket_scatter writes stamp[new slot] = the gathered stamp: no stamping
+// kernel) and the four columns come back behind ONE more wait.  Failures from k_rotate_scatter on as expire_impl's.
+static int rotate_impl(mm_engine* e, uint32_t mode, uint32_t max_seated, uint32_t min_queue, uint32_t* n_selected,
+                       bool* marked_on_device)
+{
+    const uint32_t cap = e->cfg.capacity;
+    RotateParams R;
+    memset(&R, 0, sizeof(R));
+    R.mode = mode;
+    R.n_groups = e->cfg.n_groups;
+    R.capacity = cap;
+    R.teams = e->cfg.modes[mode].teams;
+    R.max_seated = max_seated;
+    R.min_queue = min_queue;
+    R.chains = e->d_chains;
+    R.stamp = e->d_stamp;
+    R.state = e->d_state;
+    R.base = e->d_wt_rows;                                    // (wt_max_chunks > n_groups: room for a word per group)
+    R.total = e->d_wt_rows + (size_t)e->wt_max_chunks * WT_ROWS;
+    hipLaunchKernelGGL(k_rotate_count, dim3(1), dim3(WT_THREADS), 0, e->stream, R);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, R.total, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const uint32_t k = e->h_counters[1];
+    if (k > cap || k > e->cfg.n_groups * WT_SEATS) return MM_ERR_INTERNAL;
+    if (k == 0u) return MM_OK;
+    MMTRY(move_alloc(e));
+    // the old slots stay held until the mode's next purge: the pool needs k FREE slots beside them
+    std::vector<uint32_t> sel;
+    bool contiguous = false;
+    if (!pick_free_slots(e, k, sel, &contiguous)) return MM_ERR_FULL;
+    if (!contiguous) {
+        MMTRY(ensure_staging(e, k));
+        HIPCHK(e, hipMemcpyAsync(e->d_in_sel, sel.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    }
+    MoveCols M;
+    M.q_rating = nullptr;
+    M.q_cons = nullptr;
+    M.rating = (int32_t*)e->d_mv_cols;
+    M.cons = e->d_mv_cols + cap;
+    M.stamp = e->d_mv_cols + 2u * (size_t)cap;
+    M.group = e->d_mv_group;
+    M.keep = 0u;
+    M.to_mode = mode;
+    uint32_t* const d_list = e->d_wt_out;
+    uint32_t* const d_new = e->d_mv_cols + 3u * (size_t)cap;
+    *marked_on_device = true;
+    hipLaunchKernelGGL(k_rotate_scatter, dim3(1), dim3(WT_THREADS), 0, e->stream, R, e->clock_now, d_list, d_list + cap,
+                       d_list + 2u * (size_t)cap, M);
+    HIPCHK(e, hipGetLastError());
+    MMTRY(enqueue_device_launch(e, k, M.rating, M.cons, M.group, contiguous ? NULL : e->d_in_sel, d_new, M.stamp));
+    e->x_slot.resize(k); e->x_group.resize(k); e->x_age.resize(k); e->x_new.resize(k);
+    HIPCHK(e, hipMemcpyAsync(e->x_slot.data(), d_list, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->x_group.data(), d_list + cap, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->x_age.data(), d_list + 2u * (size_t)cap, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->x_new.data(), d_new, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));           // `sel` must outlive its copy, too
+    if (e->h_counters[1] != 0u) return MM_ERR_INTERNAL;   // nobody can be refused: the mode seats them already
+    // the host mirrors: the old slots as mm_cancel leaves them, the new ones as mm_enqueue does
+    uint32_t marked = 0;
+    for (uint32_t i = 0; i < k; ++i) {
+        const uint32_t sl = e->x_slot[i];
+        if (sl < cap && e->h_state[sl] == MM_ST_LIVE) { e->h_state[sl] = MM_ST_CANCELLED; ++marked; }
+    }
+    for (uint32_t i = 0; i < k; ++i) {
+        const uint32_t sl = e->x_new[i];
+        if (sl < cap && e->h_state[sl] == MM_ST_FREE) e->h_state[sl] = MM_ST_LIVE;
+        else return MM_ERR_INTERNAL;
+    }
+    e->cancel_pending += k;
+    e->next_slot = contiguous ? (uint32_t)(((unsigned long long)e->next_slot + k) % cap) : (sel[k - 1] + 1u) % cap;
+    e->live_upper += k;
+    if (n_selected) *n_selected = k;
+    return marked == k ? MM_OK : MM_ERR_INTERNAL;             // (the device's ActiveUser mirror and the host's disagree)
+}
+
+extern "C" int mm_rotate(mm_engine* e, uint32_t mode, uint32_t max_seated, uint32_t min_queue, uint32_t* n_selected)
+{
+    if (!e || mode >= e->cfg.n_modes || max_seated == 0u) return MM_ERR_INVALID_ARG;
+    if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
+    ON_ENGINE_DEVICE(e);
+    RoctxRange rr("mm_rotate");
+    e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
+    e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
+    if (n_selected) *n_selected = 0;
+    bool marked_on_device = false;
+    const int rc = guarded([&]() -> int { return rotate_impl(e, mode, max_seated, min_queue, n_selected, &marked_on_device); });
+    if (rc != MM_OK) {
+        // as mm_move: no half-filled list, and an engine whose device may hold marks the host does not is poisoned
+        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
+        if (n_selected) *n_selected = 0;
+        if (marked_on_device) {
+            (void)hipStreamSynchronize(e->stream);
+            e->poisoned = true;
+        }
+    }
+    return rc;
+}
+
 extern "C" int mm_wait_stats(mm_engine* e, uint32_t mode, mm_wait_group* per_group)
 {
     return guarded([&]() -> int {

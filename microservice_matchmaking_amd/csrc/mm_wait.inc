@@ -1,5 +1,6 @@
 // mm_wait.inc — the clock of include/mm_wait.h on the device: expiry selection as a stable stream compaction over a
-// mode's queues, the same selection gathering the rows of a move into another mode (mm_move), wait statistics.  Included by mm_engine.hip (ChainDev, LobbyDev, dev_min_u32, wave_incl_scan, the WT_* chunk geometry); the host
+// mode's queues, the same selection gathering the rows of a move into another mode (mm_move), the rotation of blocked
+// lobbies' seats to their queues' tails (mm_rotate), wait statistics.  Included by mm_engine.hip (ChainDev, LobbyDev, dev_min_u32, wave_incl_scan, the WT_* chunk geometry); the host
 // functions that launch these kernels (wait_alloc .. mm_wait_stats) are there, like the pair and team host loops.
 // k_wait_matched sits beside k_pack_results in mm_engine.hip, whose PackArgs it shares.  DESIGN.md §4.6.
 //
@@ -280,6 +281,85 @@ __global__ __launch_bounds__(WT_THREADS) void k_move_stamp(uint32_t n, uint32_t 
     if (i >= n) return;
     const uint32_t s = new_slot[i];
     if (s < capacity) stamp[s] = old_stamp[i];
+}
+
+// mm_rotate (include/mm_wait.h): the LIVE seats of the stored lobbies of one mode leave and rejoin their own queue's
+// tail.  No queue is streamed: a chain is selected by its LobbyDev record, state[] of its seats and ChainDev.len alone, so
+// both kernels are ONE workgroup — a wave per rating group (groups wave, wave + WT_WAVES, ...), a lane per seat in
+// wait_seat's order, at most MM_MAX_GROUPS x WT_SEATS gathers in all.
+struct RotateParams {
+    uint32_t mode, n_groups, capacity, teams;
+    uint32_t max_seated, min_queue;
+    const ChainDev* chains;
+    const uint32_t* stamp;
+    uint8_t* state;
+    uint32_t* base;                           // [n_groups] rank of the group's first seat in the list (k_rotate_count)
+    uint32_t* total;                          // the players selected
+};
+
+// Lane `lane`'s seat of chain (mode, g): is it LIVE, and is the chain selected — 1 <= LIVE seats <= max_seated and a queue
+// of at least min_queue entries (ChainDev.len: entries cancelled and not yet purged count)?  `m`: the LIVE lanes.
+// The same for every lane of a wave; every lane of the wave must call it (ballot).
+static __device__ __forceinline__ bool rotate_chain(const RotateParams& P, uint32_t g, int lane, uint32_t& sl, uint32_t& t,
+                                                    uint32_t& i, unsigned long long& m)
+{
+    const ChainDev& ch = P.chains[P.mode * P.n_groups + g];
+    sl = MM_NO_SLOT; t = 0; i = 0;
+    if ((uint32_t)lane < WT_SEATS && wait_seat_at(ch.lobby, P.teams, (uint32_t)lane, t, i)) sl = ch.lobby.slot[t][i];
+    m = __ballot(sl < P.capacity && P.state[sl] == MM_ST_LIVE);
+    const uint32_t c = (uint32_t)__popcll(m);
+    return c >= 1u && c <= P.max_seated && ch.len >= P.min_queue;
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_rotate_count(RotateParams P)
+{
+    __shared__ uint32_t s_cnt[MM_MAX_GROUPS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t g = (uint32_t)wave; g < P.n_groups && g < MM_MAX_GROUPS; g += WT_WAVES) {
+        uint32_t sl, t, i;
+        unsigned long long m;
+        const bool sel = rotate_chain(P, g, lane, sl, t, i, m);
+        if (lane == 0) s_cnt[g] = sel ? (uint32_t)__popcll(m) : 0u;
+    }
+    __syncthreads();
+    if (tid == 0) {                           // an exclusive scan over at most MM_MAX_GROUPS counts
+        uint32_t run = 0;
+        for (uint32_t g = 0; g < P.n_groups && g < MM_MAX_GROUPS; ++g) {
+            P.base[g] = run;
+            run += s_cnt[g];
+        }
+        *P.total = run;
+    }
+}
+
+// The list columns (WaitParams' out_*: slot | rating group | age), the rows of the enqueue that follows (MoveCols: rating
+// and constraint word as the LobbyDev record holds them, the group byte, stamp[slot] itself) and the marks of k_cancel.
+// A slot sits in one lobby, once: the marks of one wave are read by no other, so every wave selects what k_rotate_count
+// counted — and within a wave the ballot of rotate_chain has read state[] before the first mark is written.
+__global__ __launch_bounds__(WT_THREADS) void k_rotate_scatter(RotateParams P, uint32_t now, uint32_t* __restrict__ out_slot,
+                                                               uint32_t* __restrict__ out_group, uint32_t* __restrict__ out_age,
+                                                               MoveCols M)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (uint32_t g = (uint32_t)wave; g < P.n_groups && g < MM_MAX_GROUPS; g += WT_WAVES) {
+        uint32_t sl, t, i;
+        unsigned long long m;
+        if (!rotate_chain(P, g, lane, sl, t, i, m)) continue;
+        const uint32_t at = P.base[g] + (uint32_t)__popcll(m & lt);
+        if (((m >> lane) & 1ull) && at < P.capacity) {
+            const LobbyDev& lb = P.chains[P.mode * P.n_groups + g].lobby;
+            const uint32_t st = P.stamp[sl];
+            out_slot[at] = sl;
+            out_group[at] = g;
+            out_age[at] = now - st;
+            M.rating[at] = lb.rating[t][i];
+            M.cons[at] = lb.cons[t][i];
+            M.group[at] = (uint8_t)g;
+            M.stamp[at] = st;
+            P.state[sl] = MM_ST_CANCELLED;
+        }
+    }
 }
 
 static __device__ __forceinline__ uint32_t wait_bucket(uint32_t age) { return age ? 64u - (uint32_t)__clzll((long long)age) : 0u; }

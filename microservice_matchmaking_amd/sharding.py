@@ -15,7 +15,8 @@ counters / gather results — and, off the matching path, to carry the players o
 (to_mode, g): `ShardedSearch.move` is mm_move_out on every rank, one all-gather of the selected
 rows with their stamps, mm_enqueue_stamped on the new owners.  Unlike mm_move on one engine it is
 not all-or-nothing: a destination without room raises on every rank after the sources have expired
-their players.
+their players.  `ShardedSearch.rotate` (mm_rotate) is chain-local again: every rank rotates the chains
+it owns, no collective.
 
 What this does NOT do, and why: split ONE chain across ranks with a
 rating-bucket halo all-gather.  A chain has one open lobby (lobby_state.ex:90-91) and one
@@ -225,6 +226,14 @@ class ShardedSearch:
         new[rows[here, 6]] = got[here]
         self.last_move = {"selected": int(old.size), "taken": int(ok.sum()), "refused": int((~ok).sum())}
         return old, group, age, new
+
+    def rotate(self, mode, max_seated, min_queue=1):
+        """mm_rotate (include/mm_wait.h).  Chain-local: a rotated player rejoins the chain it sits in, so every rank rotates
+        the chains it owns and no data travels — unlike `move` this is no collective.  The players keep their global arrival
+        index under their new slot.  -> (slots, group, age, new_slots) over this rank's chains."""
+        got = self.engine.rotate(mode, max_seated, min_queue)
+        self.local_to_global[got[3].astype(np.int64)] = self.local_to_global[got[0].astype(np.int64)]
+        return got
 
     def tick(self, mode=0):
         return self.engine.tick(mode)

@@ -46,7 +46,7 @@ def stream_schedule(qps, seconds, tick_ms, seed):
 
 
 def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=True, batches=None, ttl_ms=None,
-               fallback=None):
+               fallback=None, rotate=None):
     """Drive `search` (a sharding.ShardedSearch: one engine + the chains this rank owns) through
     the schedule.  Returns a dict with per-mode latency arrays (real, floor), matched players,
     per-tick cost and a digest per chain of everything it emitted, in order.
@@ -65,10 +65,17 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
     refused — on several ranks every rank calls the move collectively, sharding.ShardedSearch.move, and the sums over the
     ranks are the one-engine figures), `wait_ms` and `depth_max`.  A move that finds a destination without room
     (MM_ERR_FULL, on every rank) ends the stream like a refused batch: `full_at_s`.  With a fallback on several ranks a batch
-    refused on ONE rank ends the stream on all of them (one all-reduced flag a period): the moves are collectives."""
+    refused on ONE rank ends the stream on all of them (one all-reduced flag a period): the moves are collectives.
+    `rotate`: {"max_seated": [per mode], "min_queue": 1, "rounds": R} of mm_rotate (include/mm_wait.h): every period, after a
+    mode's tick, up to R rounds of rotate-then-tick un-block the chains whose open lobby nobody in the queue fits (a mode
+    whose max_seated is 0 is left alone).  The rounds of a mode end when a rotate selected nobody or a round's tick emitted
+    nothing; on several ranks each of the two is the maximum over the ranks (one all-reduce each), so every chain goes through
+    the rounds it would go through on one engine.  Every round's lobbies go into the same latency arrays, wait figures and
+    digests.  The clock runs as for ttl_ms; the result also holds `rotated` (players per mode, this rank's) and
+    `rotate_rounds` (rounds run per mode).  A rotation without room (MM_ERR_FULL) ends the stream: `full_at_s`."""
     assert batches is None or len(batches) == len(schedule)
     fallback = list(fallback or ())
-    clocked = ttl_ms is not None or bool(fallback)
+    clocked = ttl_ms is not None or bool(fallback) or rotate is not None
     cfg = search.cfg
     n_modes, n_groups = int(cfg.n_modes), int(cfg.n_groups)
     total = sum(s[2] for s in schedule)
@@ -85,6 +92,39 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
     wait_ms = [[] for _ in range(n_modes)]
     depth_max = [0] * n_modes
     moved, refused = [0] * len(fallback), [0] * len(fallback)
+    rotated, rotate_rounds = [0] * n_modes, [0] * n_modes
+    if rotate is not None:
+        rot_seated = [int(x) for x in rotate["max_seated"]]
+        rot_queue, rot_rounds = int(rotate.get("min_queue", 1)), int(rotate.get("rounds", 1))
+        assert len(rot_seated) == n_modes
+
+    def over_ranks(*flags):
+        """Each flag: true on any rank (one all-reduce for all of them; on one rank the flags themselves)."""
+        if search.world_size == 1:
+            return flags
+        return tuple(v > 0 for v in search.max_over_ranks([1.0 if f else 0.0 for f in flags]))
+
+    def tick_mode(md, t_close):
+        """One tick of mode md into the latency arrays, wait figures and digests -> lobbies emitted."""
+        nonlocal matched
+        m = search.tick(md)
+        t1 = time.perf_counter()
+        if clocked:
+            if len(m):
+                wait_ms[md].append(search.engine.matches_wait().ravel().astype(np.float64))
+            depth_max[md] = max(depth_max[md], int(search.engine.queue_depth(md).sum()))
+        if len(m):
+            ids = search.global_ids(m)
+            flat = ids.ravel()
+            real[md].append((t1 - t_start) - arrival[flat])
+            floor[md].append(t_close - arrival[flat])
+            matched += flat.size
+            for g in np.unique(m.group):
+                sel = np.ascontiguousarray(ids[m.group == g], dtype="<i8")
+                hashers[(md, int(g))].update(sel.tobytes())
+                emitted[(md, int(g))] += int(sel.shape[0])
+        return len(m)
+
     # (a generation-2 collection of the interpreter's heap is a pause of tens of milliseconds in one tick of a real-time
     # run: nothing here makes reference cycles, so the collector rests until the stream is over)
     import gc
@@ -140,22 +180,30 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
                 for md in range(n_modes):
                     expired[md] += int(search.engine.expire(md, int(ttl_ms))[0].size)
             for md in range(n_modes):
-                m = search.tick(md)
-                t1 = time.perf_counter()
-                if clocked:
-                    if len(m):
-                        wait_ms[md].append(search.engine.matches_wait().ravel().astype(np.float64))
-                    depth_max[md] = max(depth_max[md], int(search.engine.queue_depth(md).sum()))
-                if len(m):
-                    ids = search.global_ids(m)
-                    flat = ids.ravel()
-                    real[md].append((t1 - t_start) - arrival[flat])
-                    floor[md].append(t_close - arrival[flat])
-                    matched += flat.size
-                    for g in np.unique(m.group):
-                        sel = np.ascontiguousarray(ids[m.group == g], dtype="<i8")
-                        hashers[(md, int(g))].update(sel.tobytes())
-                        emitted[(md, int(g))] += int(sel.shape[0])
+                tick_mode(md, t_close)
+                if rotate is None or rot_seated[md] == 0:
+                    continue
+                for _ in range(rot_rounds):
+                    k_sel, full = 0, False
+                    try:
+                        k_sel = int(search.rotate(md, rot_seated[md], rot_queue)[0].size)
+                    except MMError as ex:
+                        if ex.status != -4:                         # MM_ERR_FULL: no free slots beside the rotated players
+                            raise
+                        full = True
+                    rotated[md] += k_sel
+                    some, full = over_ranks(k_sel > 0, full)        # one decision for all ranks: they tick the same rounds
+                    if full:
+                        full_at_s = t_open
+                    if full or not some:
+                        break
+                    rotate_rounds[md] += 1
+                    if not over_ranks(tick_mode(md, t_close) > 0)[0]:
+                        break
+                if full_at_s is not None:
+                    break
+            if full_at_s is not None:
+                break
             tick_cost.append(time.perf_counter() - t0)
     finally:
         # whatever ends the loop (a refused batch is handled above; a failed tick, Ctrl-C): the interpreter gets its collector back
@@ -176,6 +224,8 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
         out["expired"] = expired
     if fallback:
         out.update({"moved": moved, "refused": refused})
+    if rotate is not None:
+        out.update({"rotated": rotated, "rotate_rounds": rotate_rounds})
     return out
 
 

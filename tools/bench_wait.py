@@ -20,9 +20,15 @@ engine — mm_move_out, mm_expired, mm_moved_rows, mm_enqueue_stamped of the sam
 host route, at the same three shares.  What to expect at 1 %: between the two (it spares the host gather of the host route
 and adds one 4-byte column each way to mm_move).  All three must leave the same queue depths.
 
+--rotate adds mm_rotate on cfg-2's pool with a stored anchor in every rating group (an anchor of a region nobody else is
+from, ticked into the stored lobby before the pool arrives) beside the host route it replaces — mm_lobby_state per rating
+group, the owner's table, mm_cancel, mm_enqueue_stamped — in turns on the same engine; both must hand out the same slots and
+leave the same queues.
+
 Usage (GPU box, repo root):  python tools/bench_wait.py [--steps 30] [--players 1000000] > profiles/wait_1m.json
                              python tools/bench_wait.py --move > profiles/wait_move_1m.json
-                             python tools/bench_wait.py --carry > profiles/wait_carry_1m.json"""
+                             python tools/bench_wait.py --carry > profiles/wait_carry_1m.json
+                             python tools/bench_wait.py --rotate > profiles/wait_rotate_1m.json"""
 import argparse
 import json
 import os
@@ -159,6 +165,65 @@ def measure_carry(args, rating, cons, d_rating, d_cons, now):
     return out
 
 
+def measure_rotate(args, d_rating, d_cons, now):
+    """mm_rotate and the host route, in turns on one engine: the same pool behind the same stored anchors, the same seats
+    selected, the same new slots and queues behind."""
+    from microservice_matchmaking_amd import Engine, make_config, mode_1v1
+    from microservice_matchmaking_amd._abi import cons_make
+    n = args.players
+    cap = 1 << (n - 1).bit_length()
+    if cap - n < 64:
+        cap *= 2
+    cfg = make_config([mode_1v1(window=25, region_filter=True)], capacity=cap, timing=True)
+    G = int(cfg.n_groups)
+    a_rating = np.asarray([(cfg.groups[g].from_ + cfg.groups[g].to) // 2 for g in range(G)], np.int32)
+    a_cons = cons_make(0, np.full(G, 200))                       # a region of their own: nobody in the pool fits them
+    t = {"rotate": [], "host": []}
+    parts = {"lobby_state_ms": [], "cancel_ms": [], "enqueue_stamped_ms": []}
+    seen = {}
+    with Engine(cfg) as eng:
+        eng.clock_set(now)
+        for k in range(args.warmup + args.steps):
+            for route in ("rotate", "host") if k % 2 == 0 else ("host", "rotate"):
+                eng.reset()
+                now += 10
+                eng.clock_set(now)
+                stamp0 = now
+                anchors = eng.enqueue(a_rating, a_cons)            # slots 0 .. G-1: the owner's table is (a_rating, a_cons, stamp0)
+                assert len(eng.tick(0)) == 0
+                now += 100
+                eng.clock_set(now)
+                eng.enqueue_device(d_rating, d_cons)
+                t0 = time.perf_counter()
+                if route == "rotate":
+                    old, group, age, new = eng.rotate(0, 1, 1)
+                    t1 = time.perf_counter()
+                else:
+                    seats = [eng.lobby_state(0, g)[0] for g in range(G)]
+                    ta = time.perf_counter()
+                    old = np.concatenate(seats).astype(np.uint32)
+                    group = np.repeat(np.arange(G, dtype=np.uint32), [s.size for s in seats])
+                    eng.cancel(old)
+                    tb = time.perf_counter()
+                    new = eng.enqueue_stamped(a_rating[old], a_cons[old], np.full(old.size, stamp0, np.uint32), group.astype(np.uint8))
+                    t1 = time.perf_counter()
+                    if k >= args.warmup:
+                        parts["lobby_state_ms"].append((ta - t0) * 1e3)
+                        parts["cancel_ms"].append((tb - ta) * 1e3)
+                        parts["enqueue_stamped_ms"].append((t1 - tb) * 1e3)
+                assert old.tolist() == anchors.tolist() and new.size == G
+                if k >= args.warmup:
+                    t[route].append((t1 - t0) * 1e3)
+                seen[route] = (new.tolist(), eng.queue_depth(0).tolist(), [int(eng.queue_slots(0, g)[-1]) for g in range(G)],
+                               [w["oldest_age"] for w in eng.wait_stats(0)])
+    assert seen["rotate"] == seen["host"], seen
+    return {"selected": G, "groups": G, "rotate_call_ms": spread(t["rotate"]), "host_route_ms": spread(t["host"]),
+            "host_route_parts_ms": {k: med(v) for k, v in parts.items()},
+            "rotate_over_host": med(t["rotate"]) / med(t["host"]),
+            "note": "host time around the calls, the wrapper's numpy buffers included; %d players queued behind %d stored anchors, "
+                    "capacity %d; both routes hand out the same slots and keep the anchors' stamps" % (n, G, cap)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
@@ -170,6 +235,8 @@ def main():
     ap.add_argument("--move", action="store_true", help="also measure mm_move beside the host route it replaces")
     ap.add_argument("--carry", action="store_true",
                     help="also measure mm_move_out + mm_enqueue_stamped on one engine beside mm_move and the host route")
+    ap.add_argument("--rotate", action="store_true",
+                    help="also measure mm_rotate beside the host route it replaces (mm_lobby_state per group, mm_cancel, mm_enqueue_stamped)")
     args = ap.parse_args()
     assert args.steps >= 20, "medians of at least 20 steps"
     import torch
@@ -251,6 +318,7 @@ def main():
 
     move = measure_move(args, rating, cons, d_rating, d_cons, now) if args.move else None
     carry = measure_carry(args, rating, cons, d_rating, d_cons, now) if args.carry else None
+    rotate = measure_rotate(args, d_rating, d_cons, now) if args.rotate else None
 
     bucket = med(rows["off"]["bucket_ms"])
     out = {
@@ -276,6 +344,8 @@ def main():
         out["move"] = move
     if carry is not None:
         out["carry"] = carry
+    if rotate is not None:
+        out["rotate"] = rotate
     print(json.dumps(out, indent=1))
     off.close()
     on.close()
