@@ -1,7 +1,8 @@
 /*
  * mm_wait.h — the engine's clock: arrival stamps, expiry of long-waiting players, their move to a
  * fallback mode — inside one engine or carried to another one with their rows and stamps — the
- * rotation of a blocked lobby's players to their queue's tail, wait times.
+ * rotation of a blocked lobby's players to their queue's tail, wait times, a player's place in
+ * its queue.
  *
  * An extension of include/mm_engine.h (same rules: plain C types, status codes and never an
  * abort, every entry point selects the engine's HIP device itself, MM_ERR_STATE on an engine
@@ -44,6 +45,12 @@
  * as mm_cancel marks them and the same players join the tail of their queue with the stamps they had.
  * The next tick drops the emptied lobby (the stale-lobby rule) and the queue's head anchors a new one.
  * No new matching rule: to the oracle it is mo_cancel plus mo_enqueue of the same rows.
+ *
+ * Answering a status request is mm_locate: where a slot stands in a mode right now — in which
+ * rating group's queue and at which position, how many waiting players are ahead of it, for how
+ * long it has waited, or that it sits in the stored lobby, or that a cancel or an expiry has marked
+ * it already.  It reads what mm_queue_slots, mm_lobby_state and the stamps hold, on the device, in
+ * one pass of mm_expire's walk, and changes nothing: it works with the clock off as well.
  *
  * Not here: the NIF binding (native/mm_nif.c; INTEGRATION.md section 7 names the calls to add);
  * an ALL-OR-NOTHING move across engines (chain (A, g) and chain (B, g) of a ShardedSearch may have
@@ -207,6 +214,39 @@ int mm_enqueue_stamped(mm_engine* e, uint32_t n, const int32_t* rating, const ui
  * MM_ERR_STATE: the clock was never set.
  * Reference: Search.Worker.status/0 (lib/search/worker.ex:115-117, :326-334), depth only. */
 int mm_wait_stats(mm_engine* e, uint32_t mode, mm_wait_group* per_group);
+
+#define MM_AT_NONE   0u /* not in this mode: free, matched, never handed out, >= capacity, or waiting in another mode */
+#define MM_AT_QUEUE  1u /* an entry of the queue of (mode, group)                                                      */
+#define MM_AT_LOBBY  2u /* a seat of the stored lobby of (mode, group)                                                 */
+#define MM_AT_MARKED 4u /* or-ed in: cancelled / expired / moved / rotated, still listed until the mode's next tick drops it */
+
+/* Where slots[i] stands in `mode` at this moment, for i < n; each output column has n words and any
+ * of them may be NULL.
+ *   where     MM_AT_QUEUE or MM_AT_LOBBY, with MM_AT_MARKED or-ed in when the slot is no longer LIVE
+ *             (marked by mm_cancel, mm_expire, mm_move, mm_move_out or mm_rotate and not yet dropped);
+ *             MM_AT_NONE when the slot is in no queue and no stored lobby of this mode.
+ *   group     the rating group of the chain; MM_NO_SLOT for NONE.
+ *   position  QUEUE: the index in the list mm_queue_slots(mode, group) returns, head = 0 (entries
+ *             cancelled and not yet purged count, as they do there); LOBBY: the index in
+ *             mm_lobby_state's list; MM_NO_SLOT for NONE.
+ *   ahead     QUEUE: the LIVE entries at smaller positions of the same queue — what a client shows
+ *             (the same definition for a MARKED entry); LOBBY and NONE: 0.
+ *   age       clock - stamp[slot] for every slot found, MARKED ones included; 0 for NONE, and 0
+ *             everywhere while the clock was never set (the call does not switch it on).
+ * A slot may be queried more than once: each occurrence gets the same answer.  A slot >= capacity
+ * is NONE.  n == 0: MM_OK, nothing is launched.
+ * Read-only: no queue, lobby, state, stamp, host mirror or ring position changes, the lists of
+ * mm_expired / mm_moved / mm_moved_rows stay as they are, a snapshot taken after the call is byte
+ * for byte the one taken before it; results never depend on mm_tuning.  An engine that never calls
+ * it allocates and launches nothing for it.
+ * MM_ERR_INVALID_ARG: e == NULL, no such mode, slots == NULL with n > 0, n > capacity.
+ * MM_ERR_STATE: the engine is poisoned by a failed tick.  MM_ERR_HIP / MM_ERR_OOM do NOT poison
+ * the engine (nothing was marked); the call's scratch is released and the next call starts afresh.
+ * Cost: two streams of the mode's queues (one when ahead == NULL) with two gathers per entry, one
+ * wait on the stream; nothing proportional to the capacity after the first call.
+ * Reference: Search.Worker.status/0 (lib/search/worker.ex:115-117, :326-334), depth only. */
+int mm_locate(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, uint32_t* where,
+              uint32_t* group, uint32_t* position, uint32_t* ahead, uint32_t* age);
 
 /* How long the players of the last tick's lobbies had waited: L = teams * team_size words per
  * match, laid out like mm_matches' `slots`; each word is the clock at that tick minus the seated

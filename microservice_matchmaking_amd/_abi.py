@@ -24,6 +24,7 @@ MM_MODE_PARTY_FILTER = 2
 MM_CFG_TIMING = 1
 MM_WAIT_HIST = 33
 NO_SLOT = 0xFFFFFFFF
+AT_NONE, AT_QUEUE, AT_LOBBY, AT_MARKED = 0, 1, 2, 4      # include/mm_wait.h MM_AT_*: the `where` word of mm_locate
 
 STATUS_NAMES = {
     0: "MM_OK", -1: "MM_ERR_INVALID_ARG", -2: "MM_ERR_NO_DEVICE", -3: "MM_ERR_OOM",
@@ -251,6 +252,9 @@ def bind(lib, prefix):
     if hasattr(lib, prefix + "rotate"):                   # include/mm_wait.h: a blocked lobby's players rejoin their queue's tail
         f("rotate").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
         f("rotate").restype = C.c_int
+    if hasattr(lib, prefix + "locate"):                   # include/mm_wait.h: a player's place in its queue
+        f("locate").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6
+        f("locate").restype = C.c_int
     return lib
 
 
@@ -534,6 +538,19 @@ class EngineBase:
         self._check(self._fn("expired")(self._h, 0, k, _ptr(slots), _ptr(group), _ptr(age)), "expired")
         self._check(self._fn("moved")(self._h, 0, k, _ptr(new)), "moved")
         return slots, group, age, new
+
+    def locate(self, mode, slots, ahead=True):
+        """mm_locate: where each of `slots` stands in `mode` right now.  -> (where, group, position, ahead, age), uint32
+        arrays as long as `slots`: AT_QUEUE / AT_LOBBY (| AT_MARKED once cancelled, expired, moved or rotated and not yet
+        dropped) or AT_NONE; the rating group; the index in queue_slots' / lobby_state's list; the LIVE queue entries in
+        front; clock - stamp (0 while the clock is off).  NO_SLOT for group and position of AT_NONE.  Read-only.
+        ahead=False spares the counting pass (ahead == NULL): that column comes back as None."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        assert slots.ndim == 1
+        n = slots.shape[0]
+        cols = [np.empty(n, dtype=np.uint32) if (ahead or c != 3) else None for c in range(5)]
+        self._check(self._fn("locate")(self._h, mode, n, _ptr(slots), *[_ptr(c) for c in cols]), "locate")
+        return tuple(cols)
 
     def enqueue_stamped(self, rating, cons, stamp, group=None):
         """mm_enqueue_stamped: `enqueue`, every accepted player stamped stamp[i] instead of the clock.  -> slots."""

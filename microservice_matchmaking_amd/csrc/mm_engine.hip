@@ -1117,6 +1117,13 @@ struct mm_engine {
     uint8_t* d_mv_group;       // [capacity] ... and their rating groups, the column k_bucket_* take
     uint32_t* h_mwait;         // pinned, as large as d_wt_matched: mm_matches_wait, emission order, r_L words a lobby
     uint32_t mw_n;             // lobbies of the last tick h_mwait covers (0: the clock was off at that tick)
+    // mm_locate (include/mm_wait.h): nothing below is allocated, and no kernel of it runs, before the first mm_locate
+    uint32_t* d_loc_tag;       // [capacity] query + 1 of a queried slot while a call runs; all zero between calls
+    uint32_t* d_loc_rows;      // [loc_max_chunks][WT_ROWS] + 1: d_wt_rows' layout, a buffer of the call's own (the clock may be off)
+    uint32_t loc_max_chunks;
+    uint32_t* d_loc_q;         // [loc_cap] the queried slots
+    uint32_t* d_loc_out;       // [5][loc_cap] where | group | position | ahead | age
+    uint32_t loc_cap;          // queries d_loc_q / d_loc_out have room for (they grow)
 };
 
 // Named ranges for a profiler's timeline (the reference logs nothing per attempt).  MM_ROCTX=1 makes
@@ -3472,6 +3479,104 @@ extern "C" int mm_expired(mm_engine* e, uint32_t first, uint32_t count, uint32_t
     if (group) memcpy(group, &e->x_group[first], (size_t)count * sizeof(uint32_t));
     if (age) memcpy(age, &e->x_age[first], (size_t)count * sizeof(uint32_t));
     return MM_OK;
+}
+
+// The scratch of mm_locate: the tag column and the rows at the first call (zeroed: the only work of a call that is
+// proportional to the capacity), the query and result columns grown to the longest query so far.
+static void loc_release(mm_engine* e)
+{
+    mem_release(e, e->d_loc_tag); mem_release(e, e->d_loc_rows); mem_release(e, e->d_loc_q); mem_release(e, e->d_loc_out);
+    e->loc_cap = 0;
+}
+
+static int loc_alloc(mm_engine* e, uint32_t n)
+{
+    const size_t cap = e->cfg.capacity;
+    return guarded([&]() -> int {
+        if (!e->d_loc_tag) {
+            e->loc_max_chunks = (uint32_t)(cap / WT_CHUNK + e->cfg.n_groups + 1u);          // as wait_alloc sizes d_wt_rows
+            MMTRY(dev_alloc(e, e->d_loc_rows, ((size_t)e->loc_max_chunks * WT_ROWS + 1u) * sizeof(uint32_t)));
+            uint32_t* tag = NULL;
+            MMTRY(dev_alloc(e, tag, cap * sizeof(uint32_t)));
+            const hipError_t rc = hipMemsetAsync(tag, 0, cap * sizeof(uint32_t), e->stream);
+            if (rc != hipSuccess) {
+                mem_release(e, tag);
+                e->last_hip = (int)rc;
+                return MM_ERR_HIP;
+            }
+            e->d_loc_tag = tag;                                // last: its presence says the tags are there and zero
+        }
+        if (n > e->loc_cap) {
+            uint32_t want = 1024u;
+            while (want < n) want <<= 1;                       // (n <= capacity, and a capacity fits a queue's 32-bit index)
+            if (want > cap) want = (uint32_t)cap;
+            mem_release(e, e->d_loc_q); mem_release(e, e->d_loc_out);
+            e->loc_cap = 0;
+            MMTRY(dev_alloc(e, e->d_loc_q, (size_t)want * sizeof(uint32_t)));
+            MMTRY(dev_alloc(e, e->d_loc_out, 5u * (size_t)want * sizeof(uint32_t)));
+            e->loc_cap = want;
+        }
+        return MM_OK;
+    });
+}
+
+static int locate_impl(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, uint32_t* where, uint32_t* group,
+                       uint32_t* position, uint32_t* ahead, uint32_t* age)
+{
+    MMTRY(loc_alloc(e, n));
+    const uint32_t cap = e->cfg.capacity;
+    WaitParams P = wait_params(e, mode, 0u);                   // (stamp == NULL while the clock is off: every age reads 0)
+    P.stamp = e->clock_on ? e->d_stamp : NULL;
+    P.max_chunks = e->loc_max_chunks;
+    P.rows = e->d_loc_rows;
+    P.out_slot = NULL; P.out_group = NULL; P.out_age = NULL; P.stats = NULL;
+    LocParams L;
+    L.n = n;
+    L.stride = e->loc_cap;
+    L.want_ahead = ahead ? 1u : 0u;
+    L.q = e->d_loc_q;
+    L.tag = e->d_loc_tag;
+    L.out = e->d_loc_out;
+    const unsigned long long want = e->live_upper / WT_CHUNK + e->cfg.n_groups;          // wait_grid over this call's rows
+    const uint32_t grid = (uint32_t)(want < e->loc_max_chunks ? want : e->loc_max_chunks);
+    const dim3 per_query((n + WT_THREADS - 1u) / WT_THREADS), wg(WT_THREADS);
+    HIPCHK(e, hipMemcpyAsync(e->d_loc_q, slots, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_loc_mark, per_query, wg, 0, e->stream, L, cap);
+    if (ahead) {
+        hipLaunchKernelGGL(k_loc_count, dim3(grid), wg, 0, e->stream, P);
+        hipLaunchKernelGGL(k_wait_scan, dim3(1), wg, 0, e->stream, P);
+    }
+    hipLaunchKernelGGL(k_loc_scatter, dim3(grid), wg, 0, e->stream, P, L);
+    hipLaunchKernelGGL(k_loc_collect, per_query, wg, 0, e->stream, L, cap);
+    hipLaunchKernelGGL(k_loc_clear, per_query, wg, 0, e->stream, L, cap);
+    HIPCHK(e, hipGetLastError());
+    uint32_t* const cols[5] = { where, group, position, ahead, age };
+    for (uint32_t c = 0; c < 5u; ++c)
+        if (cols[c])
+            HIPCHK(e, hipMemcpyAsync(cols[c], e->d_loc_out + (size_t)c * e->loc_cap, (size_t)n * sizeof(uint32_t),
+                                     hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return MM_OK;
+}
+
+extern "C" int mm_locate(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, uint32_t* where, uint32_t* group,
+                         uint32_t* position, uint32_t* ahead, uint32_t* age)
+{
+    return guarded([&]() -> int {
+        if (!e || mode >= e->cfg.n_modes || (n > 0u && !slots) || n > e->cfg.capacity) return MM_ERR_INVALID_ARG;
+        if (e->poisoned) return MM_ERR_STATE;
+        if (n == 0u) return MM_OK;
+        ON_ENGINE_DEVICE(e);
+        RoctxRange rr("mm_locate");
+        const int rc = guarded([&]() -> int { return locate_impl(e, mode, n, slots, where, group, position, ahead, age); });
+        if (rc != MM_OK) {
+            // nothing of the pool was written, so the engine stays usable; but a tag may be left standing: the scratch goes,
+            // and the next call starts from zeroed buffers
+            (void)hipStreamSynchronize(e->stream);
+            loc_release(e);
+        }
+        return rc;
+    });
 }
 
 // The columns of a move, at the first mm_move: both, or neither.

@@ -1,6 +1,6 @@
 // mm_wait.inc — the clock of include/mm_wait.h on the device: expiry selection as a stable stream compaction over a
 // mode's queues, the same selection gathering the rows of a move into another mode (mm_move), the rotation of blocked
-// lobbies' seats to their queues' tails (mm_rotate), wait statistics.  Included by mm_engine.hip (ChainDev, LobbyDev, dev_min_u32, wave_incl_scan, the WT_* chunk geometry); the host
+// lobbies' seats to their queues' tails (mm_rotate), wait statistics, a slot's place in its queue (mm_locate, k_loc_* at the end).  Included by mm_engine.hip (ChainDev, LobbyDev, dev_min_u32, wave_incl_scan, the WT_* chunk geometry); the host
 // functions that launch these kernels (wait_alloc .. mm_wait_stats) are there, like the pair and team host loops.
 // k_wait_matched sits beside k_pack_results in mm_engine.hip, whose PackArgs it shares.  DESIGN.md §4.6.
 //
@@ -423,4 +423,147 @@ __global__ __launch_bounds__(WT_THREADS) void k_wait_stats(WaitParams P)
         }
         __syncthreads();
     }
+}
+
+// mm_locate (include/mm_wait.h): where a queried slot stands in `mode` — one more pass of the walk above, and read-only:
+// nothing of the pool is written, only the call's own scratch.  k_loc_mark tags the queried slots (tag[slot] = query + 1;
+// tag[capacity] is all zero between calls) and presets every query's row to MM_AT_NONE; k_loc_count counts the LIVE
+// entries per wave into rows of k_wait_count's layout, which the unchanged k_wait_scan turns into ranks; k_loc_scatter
+// streams the queues again, gathers state[slot] and tag[slot] per entry, and a tagged entry writes its query's row;
+// k_loc_collect gives a duplicated slot's other queries the winner's row; k_loc_clear takes the tags off again.
+// A slot sits in one queue or one lobby, once: every row has one writer.
+struct LocParams {
+    uint32_t n, stride;                       // queries; words between the columns of `out`
+    uint32_t want_ahead;                      // 0: k_loc_count and k_wait_scan did not run, `ahead` is not asked for
+    const uint32_t* q;                        // [n] the queried slots
+    uint32_t* tag;                            // [capacity]
+    uint32_t* out;                            // [5][stride]: where | group | position | ahead | age
+};
+
+#define LOC_NONE 0u                           // MM_AT_* of include/mm_wait.h
+#define LOC_QUEUE 1u
+#define LOC_LOBBY 2u
+#define LOC_MARKED 4u
+
+static __device__ __forceinline__ void loc_write(const LocParams& L, uint32_t i, uint32_t where, uint32_t group, uint32_t position,
+                                                 uint32_t ahead, uint32_t age)
+{
+    if (i >= L.n) return;
+    L.out[i] = where;
+    L.out[(size_t)L.stride + i] = group;
+    L.out[2u * (size_t)L.stride + i] = position;
+    L.out[3u * (size_t)L.stride + i] = ahead;
+    L.out[4u * (size_t)L.stride + i] = age;
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_loc_mark(LocParams L, uint32_t capacity)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= L.n) return;
+    loc_write(L, i, LOC_NONE, MM_NO_SLOT, MM_NO_SLOT, 0u, 0u);
+    const uint32_t s = L.q[i];
+    if (s < capacity) L.tag[s] = i + 1u;      // among duplicates any one winner will do (k_loc_collect)
+}
+
+// A wave's WT_PER_WAVE queue entries from w0 on, as wait_load reads them: the slots, then state[slot] and (TAGS) tag[slot] —
+// every load of a level issued before the first one is used.  Bit r of the result: this lane's entry r is LIVE.
+template <bool TAGS>
+static __device__ __forceinline__ uint32_t loc_load(const WaitParams& P, const uint32_t* __restrict__ tag, size_t qo, uint32_t w0,
+                                                    uint32_t len, int lane, uint32_t (&sl)[WT_ITERS], uint32_t (&tg)[WT_ITERS])
+{
+    uint8_t st[WT_ITERS];
+#pragma unroll
+    for (uint32_t r = 0; r < WT_ITERS; ++r) {
+        const uint32_t i = w0 + r * 64 + lane;
+        sl[r] = i < len ? P.q_slot[qo + i] : MM_NO_SLOT;
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < WT_ITERS; ++r) {
+        const bool in = sl[r] < P.capacity;
+        st[r] = in ? P.state[sl[r]] : (uint8_t)MM_ST_FREE;
+        tg[r] = TAGS && in ? tag[sl[r]] : 0u;
+    }
+    uint32_t live = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < WT_ITERS; ++r)
+        if (st[r] == MM_ST_LIVE) live |= 1u << r;
+    return live;
+}
+
+// k_wait_count's shape with the predicate "LIVE" and no age; the seats row counts 0 (a seat has nobody ahead).
+__global__ __launch_bounds__(WT_THREADS) void k_loc_count(WaitParams P)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        uint32_t cnt = 0;
+        if (w0 < len) {
+            uint32_t sl[WT_ITERS], tg[WT_ITERS];
+            const uint32_t live = loc_load<false>(P, nullptr, qo, w0, len, lane, sl, tg);
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) cnt += (uint32_t)__popcll(__ballot((live >> r) & 1u));
+        }
+        if (lane == 0) P.rows[(size_t)b * WT_ROWS + 1u + wave] = cnt;
+        if (tid == 0) P.rows[(size_t)b * WT_ROWS] = 0u;
+    }
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_loc_scatter(WaitParams P, LocParams L)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        if (w0 < len) {
+            // LIVE entries of this queue in front of the wave: its scanned rank less the rank of the group's first queue row
+            uint32_t base = L.want_ahead ? P.rows[(size_t)b * WT_ROWS + 1u + wave] - P.rows[(size_t)(b - k) * WT_ROWS + 1u] : 0u;
+            uint32_t sl[WT_ITERS], tg[WT_ITERS];
+            const uint32_t live = loc_load<true>(P, L.tag, qo, w0, len, lane, sl, tg);
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) {
+                const bool lv = (live >> r) & 1u;
+                const unsigned long long m = __ballot(lv);
+                if (tg[r])
+                    loc_write(L, tg[r] - 1u, LOC_QUEUE | (lv ? 0u : LOC_MARKED), g, w0 + r * 64 + (uint32_t)lane,
+                              base + (uint32_t)__popcll(m & lt), P.stamp ? P.now - P.stamp[sl[r]] : 0u);
+                base += (uint32_t)__popcll(m);
+            }
+        }
+        if (wave == 0 && k == 0u && (uint32_t)lane < WT_SEATS) {
+            const uint32_t sl = wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane);
+            const uint32_t tg = sl < P.capacity ? L.tag[sl] : 0u;
+            if (tg)
+                loc_write(L, tg - 1u, LOC_LOBBY | (P.state[sl] == MM_ST_LIVE ? 0u : LOC_MARKED), g, (uint32_t)lane, 0u,
+                          P.stamp ? P.now - P.stamp[sl] : 0u);
+        }
+    }
+}
+
+// A query whose slot's tag names another query (the same slot, queried more than once) takes that query's row.  The winner's
+// row was written by the launches before this one and nobody reads a loser's row: no race.
+__global__ __launch_bounds__(WT_THREADS) void k_loc_collect(LocParams L, uint32_t capacity)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= L.n) return;
+    const uint32_t s = L.q[i];
+    if (s >= capacity) return;
+    const uint32_t t = L.tag[s];
+    if (t == 0u || t - 1u == i || t - 1u >= L.n) return;
+#pragma unroll
+    for (uint32_t c = 0; c < 5u; ++c) L.out[c * (size_t)L.stride + i] = L.out[c * (size_t)L.stride + (t - 1u)];
+}
+
+// A launch of its own behind the collect (which reads the tags): tag[] is all zero again, found or not.
+__global__ __launch_bounds__(WT_THREADS) void k_loc_clear(LocParams L, uint32_t capacity)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= L.n) return;
+    const uint32_t s = L.q[i];
+    if (s < capacity) L.tag[s] = 0u;
 }

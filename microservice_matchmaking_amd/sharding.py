@@ -16,7 +16,7 @@ counters / gather results — and, off the matching path, to carry the players o
 rows with their stamps, mm_enqueue_stamped on the new owners.  Unlike mm_move on one engine it is
 not all-or-nothing: a destination without room raises on every rank after the sources have expired
 their players.  `ShardedSearch.rotate` (mm_rotate) is chain-local again: every rank rotates the chains
-it owns, no collective.
+it owns, no collective; so is `ShardedSearch.locate` (mm_locate), a look at this rank's own chains.
 
 What this does NOT do, and why: split ONE chain across ranks with a
 rating-bucket halo all-gather.  A chain has one open lobby (lobby_state.ex:90-91) and one
@@ -234,6 +234,12 @@ class ShardedSearch:
         got = self.engine.rotate(mode, max_seated, min_queue)
         self.local_to_global[got[3].astype(np.int64)] = self.local_to_global[got[0].astype(np.int64)]
         return got
+
+    def locate(self, mode, slots):
+        """mm_locate (include/mm_wait.h).  Chain-local, as `rotate`: `slots` are this rank's engine's slots, the answer is
+        about the chains this rank owns, and there is no collective — a status request goes to the rank that holds the
+        player.  -> (where, group, position, ahead, age)."""
+        return self.engine.locate(mode, slots)
 
     def tick(self, mode=0):
         return self.engine.tick(mode)

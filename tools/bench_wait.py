@@ -25,10 +25,16 @@ from, ticked into the stored lobby before the pool arrives) beside the host rout
 group, the owner's table, mm_cancel, mm_enqueue_stamped — in turns on the same engine; both must hand out the same slots and
 leave the same queues.
 
+--locate adds mm_locate on cfg-2's pool, all of it waiting in its queues with one player in a thousand cancelled, for 1,
+1 000 and 100 000 queried slots drawn from the waiting players: the call, the same call with ahead == NULL (no counting pass)
+and the host route it replaces — mm_queue_slots and mm_lobby_state per rating group, then the numpy search over them against
+the owner's table of cancelled slots — in turns on the same engine; the call and the host route must give the same answer.
+
 Usage (GPU box, repo root):  python tools/bench_wait.py [--steps 30] [--players 1000000] > profiles/wait_1m.json
                              python tools/bench_wait.py --move > profiles/wait_move_1m.json
                              python tools/bench_wait.py --carry > profiles/wait_carry_1m.json
-                             python tools/bench_wait.py --rotate > profiles/wait_rotate_1m.json"""
+                             python tools/bench_wait.py --rotate > profiles/wait_rotate_1m.json
+                             python tools/bench_wait.py --locate > profiles/wait_locate_1m.json"""
 import argparse
 import json
 import os
@@ -224,6 +230,75 @@ def measure_rotate(args, d_rating, d_cons, now):
                     "capacity %d; both routes hand out the same slots and keep the anchors' stamps" % (n, G, cap)}
 
 
+def host_locate(eng, mode, gone, q):
+    """What mm_locate replaces: every rating group's queue and stored lobby copied to the host, then the search in numpy —
+    position and LIVE entries ahead from the lists and the owner's table of cancelled slots (`gone`), gathered per query."""
+    cap, G = int(eng.cfg.capacity), int(eng.cfg.n_groups)
+    where = np.zeros(cap, np.uint32)
+    group = np.full(cap, 0xFFFFFFFF, np.uint32)
+    position = np.full(cap, 0xFFFFFFFF, np.uint32)
+    ahead = np.zeros(cap, np.uint32)
+    for g in range(G):
+        qs = eng.queue_slots(mode, g)
+        ls = eng.lobby_state(mode, g)[0]
+        live = ~gone[qs]
+        where[qs] = 1 + 4 * gone[qs]
+        group[qs] = g
+        position[qs] = np.arange(qs.size, dtype=np.uint32)
+        ahead[qs] = np.cumsum(live, dtype=np.uint32) - live
+        where[ls] = 2 + 4 * gone[ls]
+        group[ls] = g
+        position[ls] = np.arange(ls.size, dtype=np.uint32)
+    return where[q], group[q], position[q], ahead[q]
+
+
+def measure_locate(args, d_rating, d_cons, now):
+    """mm_locate, mm_locate with ahead == NULL and the host route, in turns on one engine over the same waiting pool."""
+    from microservice_matchmaking_amd import Engine, make_config, mode_1v1
+    n = args.players
+    cap = 1 << (n - 1).bit_length()
+    cfg = make_config([mode_1v1(window=25, region_filter=True)], capacity=cap, timing=True)
+    rng = np.random.default_rng(3)
+    routes = ("locate", "no_ahead", "host")
+    out = {}
+    with Engine(cfg) as eng:
+        eng.clock_set(now)
+        eng.enqueue_device(d_rating, d_cons)                       # slot i holds player i; nobody ticks: all of them wait
+        gone = np.zeros(cap, bool)
+        gone[rng.choice(n, size=max(n // 1000, 1), replace=False)] = True
+        eng.cancel(np.flatnonzero(gone).astype(np.uint32))
+        eng.clock_set(now + 100)
+        waiting = np.flatnonzero(~gone[:n]).astype(np.uint32)
+        for nq in (1, 1000, 100000):
+            q = rng.choice(waiting, size=min(nq, waiting.size), replace=False).astype(np.uint32)
+            t = {r: [] for r in routes}
+            got = {}
+            for k in range(args.warmup + args.steps):
+                for route in routes[k % 3:] + routes[:k % 3]:
+                    t0 = time.perf_counter()
+                    if route == "locate":
+                        got[route] = eng.locate(0, q)
+                    elif route == "no_ahead":
+                        got[route] = eng.locate(0, q, ahead=False)
+                    else:
+                        got[route] = host_locate(eng, 0, gone, q)
+                    t1 = time.perf_counter()
+                    if k >= args.warmup:
+                        t[route].append((t1 - t0) * 1e3)
+            for c in range(4):
+                assert np.array_equal(got["locate"][c], got["host"][c]), ("locate and the host route differ", nq, c)
+                assert c == 3 or np.array_equal(got["locate"][c], got["no_ahead"][c]), ("ahead == NULL changes a column", nq, c)
+            assert (got["locate"][0] == 1).all() and (got["locate"][4] == 100).all()
+            m = {r: med(t[r]) for r in routes}
+            out["%d_queries" % q.size] = {"queries": int(q.size), "locate_call_ms": spread(t["locate"]),
+                                          "locate_no_ahead_call_ms": spread(t["no_ahead"]), "host_route_ms": spread(t["host"]),
+                                          "locate_over_host": m["locate"] / m["host"], "no_ahead_over_locate": m["no_ahead"] / m["locate"]}
+    out["note"] = ("host time around the calls, the wrapper's numpy buffers included; %d players waiting in %d queues, %d of them "
+                   "cancelled and not yet purged, capacity %d; the host route copies every queue of the mode (4 bytes a player) and "
+                   "builds position and ahead for the whole pool whatever the number of queries" % (n, int(cfg.n_groups), int(gone.sum()), cap))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
@@ -237,6 +312,9 @@ def main():
                     help="also measure mm_move_out + mm_enqueue_stamped on one engine beside mm_move and the host route")
     ap.add_argument("--rotate", action="store_true",
                     help="also measure mm_rotate beside the host route it replaces (mm_lobby_state per group, mm_cancel, mm_enqueue_stamped)")
+    ap.add_argument("--locate", action="store_true",
+                    help="also measure mm_locate, with and without the ahead column, beside the host route it replaces "
+                         "(mm_queue_slots and mm_lobby_state per group, the numpy search)")
     args = ap.parse_args()
     assert args.steps >= 20, "medians of at least 20 steps"
     import torch
@@ -319,6 +397,7 @@ def main():
     move = measure_move(args, rating, cons, d_rating, d_cons, now) if args.move else None
     carry = measure_carry(args, rating, cons, d_rating, d_cons, now) if args.carry else None
     rotate = measure_rotate(args, d_rating, d_cons, now) if args.rotate else None
+    locate = measure_locate(args, d_rating, d_cons, now) if args.locate else None
 
     bucket = med(rows["off"]["bucket_ms"])
     out = {
@@ -346,6 +425,8 @@ def main():
         out["carry"] = carry
     if rotate is not None:
         out["rotate"] = rotate
+    if locate is not None:
+        out["locate"] = locate
     print(json.dumps(out, indent=1))
     off.close()
     on.close()
