@@ -2,7 +2,7 @@
  * mm_wait.h — the engine's clock: arrival stamps, expiry of long-waiting players, their move to a
  * fallback mode — inside one engine or carried to another one with their rows and stamps — the
  * rotation of a blocked lobby's players to their queue's tail, wait times, a player's place in
- * its queue.
+ * its queue, how many waiting players fit a player and how far away the nearest one is.
  *
  * An extension of include/mm_engine.h (same rules: plain C types, status codes and never an
  * abort, every entry point selects the engine's HIP device itself, MM_ERR_STATE on an engine
@@ -52,13 +52,27 @@
  * it already.  It reads what mm_queue_slots, mm_lobby_state and the stamps hold, on the device, in
  * one pass of mm_expire's walk, and changes nothing: it works with the clock off as well.
  *
+ * Whether a player's wait can end at all is mm_partners.  A queue position does not predict a wait: a
+ * chain is a first fit against one anchor (docs/MATCH_CHECK.md sections 2-4), so a player with 17 others
+ * in front and nobody within its window waits for ever, and the player at the tail with a partner two
+ * entries in front leaves in the next tick.  mm_partners counts, per queried slot, the waiting players of
+ * its rating group — in its own mode or in another one, the fallback an mm_move rule would send it to —
+ * that pass step 2 of match_check against it at a window and a set of filters the caller names, splits
+ * the count by role and reports the distance to the nearest candidate, which is the window at which the
+ * player would first have a partner.  It applies the existing predicate to a question, matches nobody
+ * and changes nothing; the witness is numpy over the oracle's lists.
+ *
  * Not here: the NIF binding (native/mm_nif.c; INTEGRATION.md section 7 names the calls to add);
  * an ALL-OR-NOTHING move across engines (chain (A, g) and chain (B, g) of a ShardedSearch may have
  * different owners: mm_move_out has expired the players on their source before the destination's
  * mm_enqueue_stamped can answer MM_ERR_FULL, so a full destination loses them — sharding.py raises
  * on every rank); a device-pointer variant of mm_enqueue_stamped; mm_move itself on the stamped
  * scatter (it still stamps in a kernel of its own); matching a waiting player against a wider window
- * INSIDE its own queue (a new predicate, with no witness in the reference or the oracle).
+ * INSIDE its own queue (a new matching rule, with no witness in the reference or the oracle — mm_partners
+ * is the measurement such a decision would rest on: how many partners at window W, and nothing more);
+ * ACTING on mm_partners' answer inside the engine (an mm_move that selects by partner count); mm_partners
+ * across two engines (chain (mode, g) and chain (in_mode, g) of a ShardedSearch may have different owners:
+ * sharding.py raises for in_mode != mode).
  */
 #ifndef MM_WAIT_H
 #define MM_WAIT_H
@@ -247,6 +261,42 @@ int mm_wait_stats(mm_engine* e, uint32_t mode, mm_wait_group* per_group);
  * Reference: Search.Worker.status/0 (lib/search/worker.ex:115-117, :326-334), depth only. */
 int mm_locate(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, uint32_t* where,
               uint32_t* group, uint32_t* position, uint32_t* ahead, uint32_t* age);
+
+/* How many waiting players fit slots[i], for i < n, and how far away the nearest one is.  Any of the three outputs
+ * may be NULL, and a column that is not asked for costs nothing on the device.
+ *   the query player p   the player in slots[i], where mm_locate(mode) would find it: an entry of a queue or a seat of a
+ *                        stored lobby of `mode`, a MARKED one included.  g is the rating group of that chain (for a player
+ *                        placed by the `group` override too: mm_move's rule); p's rating and constraint word are the ones
+ *                        the engine holds — the queue entry's, or the seat's in the stored lobby.
+ *   the candidates W     the waiting players of chain (in_mode, g) in mm_wait_group's sense: the LIVE entries of the queue
+ *                        plus the LIVE seats of the stored lobby.  p's own slot is never a candidate.  in_mode may be mode.
+ *   the predicate        step 2 of match_check (docs/MATCH_CHECK.md) with p in the anchor's place, at the `window` and
+ *                        `flags` passed: W fits iff |W.rating - p.rating| <= window, and MM_MODE_REGION_FILTER => equal
+ *                        regions, and MM_MODE_PARTY_FILTER => equal parties.  The difference is exact for any two int32
+ *                        ratings, `window` is a full uint32_t, the predicate is symmetric.  cfg.modes[in_mode].window and
+ *                        .flags ask about in_mode as it matches; any other value asks "what if".
+ *   partners[i]          the candidates that fit.
+ *   by_role[i * MM_MAX_ROLES + r]   the same count split by MM_CONS_ROLE(W.cons); the row sums to partners[i].
+ *   gap[i]               the smallest |W.rating - p.rating| over the candidates that pass the two FLAG filters, the window
+ *                        ignored: the window at which p would first have a partner.  Saturates at 0xFFFFFFFE;
+ *                        MM_NO_SLOT: there is none.
+ * A slot mm_locate would answer with MM_AT_NONE in `mode` (a slot >= capacity is one) gets partners 0, a zero by_role
+ * row and gap MM_NO_SLOT.  A slot queried more than once gets the same answer each time.  n == 0, or all
+ * three outputs NULL: MM_OK, nothing is launched.
+ * Read-only, exactly as mm_locate: no queue, lobby, state, stamp, host mirror or ring position changes, the lists of
+ * mm_expired / mm_moved / mm_moved_rows stay as they are, a snapshot taken after the call is byte for byte the one taken
+ * before it; results never depend on mm_tuning; it works with the clock off.  An engine that never calls it allocates
+ * and launches nothing for it.
+ * MM_ERR_INVALID_ARG: e == NULL, no such mode or in_mode, a `flags` bit outside the two MM_MODE_* filters, slots == NULL
+ * with n > 0, n > capacity.  MM_ERR_STATE: the engine is poisoned by a failed tick.  MM_ERR_HIP / MM_ERR_OOM do NOT
+ * poison the engine; the call's scratch (and mm_locate's) is released and the next call starts afresh.
+ * Cost: mm_locate's with ahead == NULL (one stream of mode's queues, four small launches), one thread per query to
+ * build its record, then one stream of in_mode's queues (slot, rating, constraint word, one gather of state[]) per
+ * tile of 512 queries, each query tested against the entries of its own rating group only: queries x group length
+ * predicate tests in all; one wait on the stream; nothing proportional to the capacity after the first call.
+ * Reference: none.  Search.Worker.status/0 (lib/search/worker.ex:115-117, :326-334) sees the depth only. */
+int mm_partners(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags, uint32_t n,
+                const uint32_t* slots, uint32_t* partners, uint32_t* by_role, uint32_t* gap);
 
 /* How long the players of the last tick's lobbies had waited: L = teams * team_size words per
  * match, laid out like mm_matches' `slots`; each word is the clock at that tick minus the seated

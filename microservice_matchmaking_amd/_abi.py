@@ -255,6 +255,9 @@ def bind(lib, prefix):
     if hasattr(lib, prefix + "locate"):                   # include/mm_wait.h: a player's place in its queue
         f("locate").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6
         f("locate").restype = C.c_int
+    if hasattr(lib, prefix + "partners"):                 # include/mm_wait.h: how many waiting players fit a player
+        f("partners").argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p] * 4
+        f("partners").restype = C.c_int
     return lib
 
 
@@ -551,6 +554,27 @@ class EngineBase:
         cols = [np.empty(n, dtype=np.uint32) if (ahead or c != 3) else None for c in range(5)]
         self._check(self._fn("locate")(self._h, mode, n, _ptr(slots), *[_ptr(c) for c in cols]), "locate")
         return tuple(cols)
+
+    def partners(self, mode, slots, in_mode=None, window=None, flags=None, by_role=True, gap=True):
+        """mm_partners: for each of `slots`, where it waits in `mode`, the waiting players of its rating group in `in_mode`
+        (default: `mode`) that fit it at `window` and `flags` (default: in_mode's configuration) — step 2 of match_check
+        with the queried player in the anchor's place, itself never counted.  -> (partners, by_role, gap): uint32 (n,),
+        (n, MM_MAX_ROLES) split by the candidates' roles, (n,) the distance to the nearest candidate that passes the
+        filters (NO_SLOT: none; the window is ignored).  A slot that is not in `mode` reads 0, zeros, NO_SLOT.  Read-only.
+        by_role=False / gap=False spare that column's work: it comes back as None."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        assert slots.ndim == 1
+        n = slots.shape[0]
+        in_mode = mode if in_mode is None else in_mode
+        if 0 <= in_mode < self.cfg.n_modes:
+            window = self.cfg.modes[in_mode].window if window is None else window
+            flags = self.cfg.modes[in_mode].flags if flags is None else flags
+        count = np.empty(n, dtype=np.uint32)
+        roles = np.empty((n, MM_MAX_ROLES), dtype=np.uint32) if by_role else None
+        near = np.empty(n, dtype=np.uint32) if gap else None
+        self._check(self._fn("partners")(self._h, mode, in_mode, int(window or 0) & 0xFFFFFFFF, int(flags or 0) & 0xFFFFFFFF, n,
+                                         _ptr(slots), _ptr(count), _ptr(roles), _ptr(near)), "partners")
+        return count, roles, near
 
     def enqueue_stamped(self, rating, cons, stamp, group=None):
         """mm_enqueue_stamped: `enqueue`, every accepted player stamped stamp[i] instead of the clock.  -> slots."""

@@ -416,6 +416,7 @@ __global__ __launch_bounds__(256) void k_reset(uint32_t n_chains, ChainDev* __re
 #define WT_CHUNK (WT_WAVES * WT_PER_WAVE)     // queue entries per workgroup
 #define WT_ROWS (WT_WAVES + 1)                // counters per chunk: the stored lobby's seats, then one per wave
 #define WT_SEATS (MM_MAX_TEAMS * 8)           // seats a LobbyDev has room for
+#define PAR_QTILE 512                         // query records a workgroup of k_par_count* stages in LDS at a time (mm_partners)
 #include "mm_wait.inc"
 
 // ------------------------------------------------------------------------------------
@@ -1124,6 +1125,10 @@ struct mm_engine {
     uint32_t* d_loc_q;         // [loc_cap] the queried slots
     uint32_t* d_loc_out;       // [5][loc_cap] where | group | position | ahead | age
     uint32_t loc_cap;          // queries d_loc_q / d_loc_out have room for (they grow)
+    // mm_partners (include/mm_wait.h): nothing below is allocated, and no kernel of it runs, before the first mm_partners
+    uint4* d_par_rec;          // [par_cap] the query records: rating | constraint word | rating group | slot
+    uint32_t* d_par_out;       // partners[par_cap] | gap[par_cap] | by_role[par_cap][MM_MAX_ROLES]
+    uint32_t par_cap;          // queries the two have room for (they grow)
 };
 
 // Named ranges for a profiler's timeline (the reference logs nothing per attempt).  MM_ROCTX=1 makes
@@ -3520,6 +3525,13 @@ static int loc_alloc(mm_engine* e, uint32_t n)
     });
 }
 
+// wait_grid over the rows of the lookup's own scratch (mm_locate, mm_partners): the clock's rows may not exist.
+static uint32_t loc_grid(const mm_engine* e)
+{
+    const unsigned long long want = e->live_upper / WT_CHUNK + e->cfg.n_groups;
+    return (uint32_t)(want < e->loc_max_chunks ? want : e->loc_max_chunks);
+}
+
 static int locate_impl(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, uint32_t* where, uint32_t* group,
                        uint32_t* position, uint32_t* ahead, uint32_t* age)
 {
@@ -3537,8 +3549,7 @@ static int locate_impl(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* 
     L.q = e->d_loc_q;
     L.tag = e->d_loc_tag;
     L.out = e->d_loc_out;
-    const unsigned long long want = e->live_upper / WT_CHUNK + e->cfg.n_groups;          // wait_grid over this call's rows
-    const uint32_t grid = (uint32_t)(want < e->loc_max_chunks ? want : e->loc_max_chunks);
+    const uint32_t grid = loc_grid(e);
     const dim3 per_query((n + WT_THREADS - 1u) / WT_THREADS), wg(WT_THREADS);
     HIPCHK(e, hipMemcpyAsync(e->d_loc_q, slots, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(k_loc_mark, per_query, wg, 0, e->stream, L, cap);
@@ -3574,6 +3585,114 @@ extern "C" int mm_locate(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t
             // and the next call starts from zeroed buffers
             (void)hipStreamSynchronize(e->stream);
             loc_release(e);
+        }
+        return rc;
+    });
+}
+
+// The buffers of mm_partners, grown to the longest query so far; the lookup's scratch is loc_alloc's.
+static void par_release(mm_engine* e)
+{
+    mem_release(e, e->d_par_rec); mem_release(e, e->d_par_out);
+    e->par_cap = 0;
+}
+
+static int par_alloc(mm_engine* e, uint32_t n)
+{
+    if (n <= e->par_cap) return MM_OK;
+    const size_t cap = e->cfg.capacity;
+    return guarded([&]() -> int {
+        uint32_t want = 1024u;
+        while (want < n) want <<= 1;                           // (n <= capacity, as in loc_alloc)
+        if (want > cap) want = (uint32_t)cap;
+        par_release(e);
+        MMTRY(dev_alloc(e, e->d_par_rec, (size_t)want * sizeof(uint4)));
+        MMTRY(dev_alloc(e, e->d_par_out, (2u + MM_MAX_ROLES) * (size_t)want * sizeof(uint32_t)));
+        e->par_cap = want;
+        return MM_OK;
+    });
+}
+
+static int partners_impl(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags, uint32_t n,
+                         const uint32_t* slots, uint32_t* partners, uint32_t* by_role, uint32_t* gap)
+{
+    MMTRY(loc_alloc(e, n));
+    MMTRY(par_alloc(e, n));
+    const uint32_t cap = e->cfg.capacity;
+    WaitParams P = wait_params(e, mode, 0u);                   // the lookup: mm_locate's passes, `ahead` off
+    P.stamp = e->clock_on ? e->d_stamp : NULL;
+    P.max_chunks = e->loc_max_chunks;
+    P.rows = e->d_loc_rows;
+    P.out_slot = NULL; P.out_group = NULL; P.out_age = NULL; P.stats = NULL;
+    LocParams L;
+    L.n = n;
+    L.stride = e->loc_cap;
+    L.want_ahead = 0u;
+    L.q = e->d_loc_q;
+    L.tag = e->d_loc_tag;
+    L.out = e->d_loc_out;
+    WaitParams C = P;                                          // the count: the same walk over in_mode's chains
+    C.mode = in_mode;
+    C.teams = e->cfg.modes[in_mode].teams;
+    ParParams Q;
+    Q.n = n;
+    Q.stride = e->par_cap;
+    Q.window = window;
+    Q.eqmask = ((flags & MM_MODE_REGION_FILTER) ? (0xFFu << 4) : 0u) | ((flags & MM_MODE_PARTY_FILTER) ? (0xFu << 12) : 0u);
+    Q.loc_stride = e->loc_cap;
+    Q.q = e->d_loc_q;
+    Q.loc = e->d_loc_out;
+    Q.q_rating = e->d_q_rating;
+    Q.q_cons = e->d_q_cons;
+    Q.rec = e->d_par_rec;
+    Q.out = e->d_par_out;
+    const uint32_t grid = loc_grid(e);
+    // the count's grid: `grid` workgroups stride over the chunks, and as many times that over the query tiles as keeps the
+    // whole near 2048 workgroups — a short queue with many queries spreads over the tiles, a long one keeps its registers
+    const uint32_t n_tiles = (n + PAR_QTILE - 1u) / PAR_QTILE, room = 2048u / grid ? 2048u / grid : 1u;
+    Q.gx = grid;
+    const uint32_t gy = n_tiles < room ? n_tiles : room;
+    const dim3 per_query((n + WT_THREADS - 1u) / WT_THREADS), wg(WT_THREADS), cg(grid * gy);
+    HIPCHK(e, hipMemcpyAsync(e->d_loc_q, slots, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_loc_mark, per_query, wg, 0, e->stream, L, cap);
+    hipLaunchKernelGGL(k_loc_scatter, dim3(grid), wg, 0, e->stream, P, L);
+    hipLaunchKernelGGL(k_loc_collect, per_query, wg, 0, e->stream, L, cap);
+    hipLaunchKernelGGL(k_loc_clear, per_query, wg, 0, e->stream, L, cap);
+    hipLaunchKernelGGL(k_par_gather, per_query, wg, 0, e->stream, P, Q);
+    if (by_role && gap) hipLaunchKernelGGL(k_par_count_all, cg, wg, 0, e->stream, C, Q);
+    else if (by_role) hipLaunchKernelGGL(k_par_count_role, cg, wg, 0, e->stream, C, Q);
+    else if (gap) hipLaunchKernelGGL(k_par_count_gap, cg, wg, 0, e->stream, C, Q);
+    else hipLaunchKernelGGL(k_par_count, cg, wg, 0, e->stream, C, Q);
+    HIPCHK(e, hipGetLastError());
+    if (partners)
+        HIPCHK(e, hipMemcpyAsync(partners, e->d_par_out, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    if (gap)
+        HIPCHK(e, hipMemcpyAsync(gap, e->d_par_out + e->par_cap, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    if (by_role)
+        HIPCHK(e, hipMemcpyAsync(by_role, e->d_par_out + 2u * (size_t)e->par_cap, (size_t)n * MM_MAX_ROLES * sizeof(uint32_t),
+                                 hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return MM_OK;
+}
+
+extern "C" int mm_partners(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags, uint32_t n,
+                           const uint32_t* slots, uint32_t* partners, uint32_t* by_role, uint32_t* gap)
+{
+    return guarded([&]() -> int {
+        if (!e || mode >= e->cfg.n_modes || in_mode >= e->cfg.n_modes || (flags & ~(MM_MODE_REGION_FILTER | MM_MODE_PARTY_FILTER)) ||
+            (n > 0u && !slots) || n > e->cfg.capacity)
+            return MM_ERR_INVALID_ARG;
+        if (e->poisoned) return MM_ERR_STATE;
+        if (n == 0u || (!partners && !by_role && !gap)) return MM_OK;   // nothing asked for: nothing is launched
+        ON_ENGINE_DEVICE(e);
+        RoctxRange rr("mm_partners");
+        const int rc = guarded([&]() -> int { return partners_impl(e, mode, in_mode, window, flags, n, slots, partners, by_role, gap); });
+        if (rc != MM_OK) {
+            // as in mm_locate: nothing of the pool was written, the engine stays usable; a tag may be left standing, so the
+            // lookup's scratch goes with this call's buffers and the next call starts afresh
+            (void)hipStreamSynchronize(e->stream);
+            loc_release(e);
+            par_release(e);
         }
         return rc;
     });

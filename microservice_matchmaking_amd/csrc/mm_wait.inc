@@ -567,3 +567,201 @@ __global__ __launch_bounds__(WT_THREADS) void k_loc_clear(LocParams L, uint32_t 
     const uint32_t s = L.q[i];
     if (s < capacity) L.tag[s] = 0u;
 }
+
+// mm_partners (include/mm_wait.h): how many waiting players of chain (in_mode, g) fit a queried player at a window and a
+// set of filters the caller names — step 2 of match_check (docs/MATCH_CHECK.md) with the queried player in the anchor's
+// place — and how far away the nearest one is.  Read-only, like mm_locate, whose passes (k_loc_mark / k_loc_scatter /
+// k_loc_collect / k_loc_clear, launched as they are, `ahead` off) find every query's chain and position first.
+// k_par_gather, one thread per query, then builds the query's record — rating | constraint word | rating group | slot, from
+// q_rating / q_cons at the position or from the LobbyDev seat; group MM_NO_SLOT for a slot that is not in the mode — and
+// presets its result words.  k_par_count* stream in_mode's queues in the walk's chunks: a wave keeps its WT_PER_WAVE entries
+// (slot, rating, constraint word, LIVE mask) in registers, the workgroup stages the queries of its chunk's rating group out
+// of a tile of PAR_QTILE records into LDS and every wave loops over them — the query is wave-uniform, its fields are
+// broadcast LDS reads — counting with ballot + popcount into the query's LDS words; a tile's non-zero words are merged
+// into the global result with one atomic each.  Integer adds and minima commute: the result is exact in any order.
+// The queried player itself is excluded by SLOT, inside the test (a slot sits in one queue or one lobby, once): with
+// in_mode == mode it would fit itself at distance 0, and a minimum cannot be corrected afterwards.
+#if !defined(PAR_QTILE)
+#error "mm_wait.inc: define PAR_QTILE beside the WT_* chunk geometry before including this file (mm_engine.hip does)"
+#endif
+
+struct ParParams {
+    uint32_t n, stride;                       // queries; queries `rec` and the columns of `out` have room for
+    uint32_t gx;                              // workgroups striding over the chunks; gridDim.x / gx of them over the query tiles
+    uint32_t window, eqmask;                  // the predicate: |rating difference| <= window, (cons ^ cons) & eqmask == 0
+    uint32_t loc_stride;
+    const uint32_t* q;                        // [n] the queried slots (mm_locate's scratch)
+    const uint32_t* loc;                      // [5][loc_stride] mm_locate's rows: where | group | position | .. | ..
+    const int32_t* q_rating;
+    const uint32_t* q_cons;
+    uint4* rec;                               // [n] x rating | y constraint word | z rating group (MM_NO_SLOT: none) | w slot
+    uint32_t* out;                            // partners[stride] | gap[stride] | by_role[stride][MM_MAX_ROLES]
+};
+
+// P: the walk's parameters for the mode the queries are looked up in.
+__global__ __launch_bounds__(WT_THREADS) void k_par_gather(WaitParams P, ParParams Q)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Q.n) return;
+    const uint32_t where = Q.loc[i] & (LOC_QUEUE | LOC_LOBBY);
+    const uint32_t g = Q.loc[(size_t)Q.loc_stride + i], pos = Q.loc[2u * (size_t)Q.loc_stride + i];
+    uint4 r;
+    r.x = 0u; r.y = 0u; r.z = MM_NO_SLOT; r.w = Q.q[i];
+    if (g < P.n_groups) {
+        if (where == LOC_QUEUE && pos < P.capacity) {
+            const size_t at = (size_t)(P.mode * P.n_groups + g) * P.capacity + pos;
+            r.x = (uint32_t)Q.q_rating[at];
+            r.y = Q.q_cons[at];
+            r.z = g;
+        } else if (where == LOC_LOBBY) {
+            const LobbyDev& lb = P.chains[P.mode * P.n_groups + g].lobby;
+            uint32_t t = 0, s = 0;
+            if (wait_seat_at(lb, P.teams, pos, t, s)) {
+                r.x = (uint32_t)lb.rating[t][s];
+                r.y = lb.cons[t][s];
+                r.z = g;
+            }
+        }
+    }
+    Q.rec[i] = r;
+    Q.out[i] = 0u;
+    Q.out[(size_t)Q.stride + i] = MM_NO_SLOT;
+#pragma unroll
+    for (uint32_t k = 0; k < MM_MAX_ROLES; ++k) Q.out[2u * (size_t)Q.stride + (size_t)i * MM_MAX_ROLES + k] = 0u;
+}
+
+// One register row of candidates against one query: sl, rt, cn this lane's candidate's slot, rating and constraint word.
+// A candidate that does not wait (not LIVE, or past the queue's end) carries PAR_DEAD in its constraint word, a bit no
+// constraint word has (MM_CONS_USER_MASK) and no staged query carries: the filter test of the predicate rejects it, so
+// liveness costs no instruction and no lane mask per row.  The difference of two int32 ratings as an ordered unsigned
+// subtraction: exact up to 2^32 - 1.  Every lane of the wave must call it (ballot).
+#define PAR_DEAD 0x80000000u
+template <bool ROLES, bool GAP>
+static __device__ __forceinline__ void par_row(const ParParams& Q, const uint4& q, uint32_t sl, int32_t rt, uint32_t cn,
+                                               uint32_t& cnt, uint32_t& dmin, uint32_t* __restrict__ role_row)
+{
+    const bool ok = sl != q.w && ((cn ^ q.y) & (Q.eqmask | PAR_DEAD)) == 0u;
+    const int32_t qr = (int32_t)q.x;
+    const uint32_t d = rt >= qr ? (uint32_t)rt - (uint32_t)qr : (uint32_t)qr - (uint32_t)rt;
+    const bool fit = ok && d <= Q.window;
+    cnt += (uint32_t)__popcll(__ballot(fit));
+    if (ROLES && fit) {
+        atomicAdd(&role_row[(cn >> 16) & (MM_MAX_ROLES - 1u)], 1u);   // MM_CONS_ROLE: below n_roles <= MM_MAX_ROLES by mm_enqueue's rule
+    }
+    if (GAP && ok) dmin = dev_min_u32(dmin, dev_min_u32(d, 0xFFFFFFFEu));
+}
+
+// P: the walk's parameters for in_mode.  Workgroup blockIdx.x % gx strides over the chunks, blockIdx.x / gx over the tiles.
+template <bool ROLES, bool GAP>
+static __device__ __forceinline__ void par_count_body(const WaitParams& P, const ParParams& Q)
+{
+    __shared__ uint4 s_rec[PAR_QTILE];                    // the kept queries: x rating | y constraint word | z query | w slot
+    __shared__ uint32_t s_cnt[PAR_QTILE];
+    __shared__ uint32_t s_gap[GAP ? PAR_QTILE : 1];
+    __shared__ uint32_t s_role[ROLES ? PAR_QTILE * MM_MAX_ROLES : 1];
+    __shared__ uint32_t s_nk;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: what depends on the wave alone costs no lane mask
+    const uint32_t gx = Q.gx ? Q.gx : 1u, bx = blockIdx.x % gx, by = blockIdx.x / gx, gy = gridDim.x / gx;
+    const uint32_t n_tiles = (Q.n + PAR_QTILE - 1u) / PAR_QTILE;
+    if (by >= gy) return;
+    for (uint32_t b = bx;; b += gx) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        const bool rows = w0 < len, seats = wave == 0 && k == 0u;
+        uint32_t sl[WT_ITERS], cn[WT_ITERS];
+        int32_t rt[WT_ITERS];
+        uint32_t s_sl = MM_NO_SLOT, s_cn = PAR_DEAD;
+        int32_t s_rt = 0;
+        if (rows) {                                       // the three streamed columns, then the gather of state[]
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) {
+                const uint32_t i = w0 + r * 64 + lane;
+                const bool in = i < len;
+                sl[r] = in ? P.q_slot[qo + i] : MM_NO_SLOT;
+                rt[r] = in ? Q.q_rating[qo + i] : 0;
+                cn[r] = in ? Q.q_cons[qo + i] : 0u;
+            }
+            uint8_t st[WT_ITERS];
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) st[r] = sl[r] < P.capacity ? P.state[sl[r]] : (uint8_t)MM_ST_FREE;
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) cn[r] = st[r] == MM_ST_LIVE ? cn[r] & ~PAR_DEAD : PAR_DEAD;
+        }
+        if (seats) {                                      // the stored lobby's seats, as k_move_scatter reads them (at most WT_SEATS: a lane past the last finds none)
+            const LobbyDev& lb = P.chains[P.mode * P.n_groups + g].lobby;
+            uint32_t t = 0, i = 0;
+            if (wait_seat_at(lb, P.teams, (uint32_t)lane, t, i)) {
+                s_sl = lb.slot[t][i];
+                s_rt = lb.rating[t][i];
+                s_cn = s_sl < P.capacity && P.state[s_sl] == MM_ST_LIVE ? lb.cons[t][i] & ~PAR_DEAD : PAR_DEAD;
+            }
+        }
+        for (uint32_t tile = by; tile < n_tiles; tile += gy) {
+            if (tid == 0) s_nk = 0u;
+            __syncthreads();
+            for (uint32_t x = (uint32_t)tid; x < PAR_QTILE; x += WT_THREADS) {
+                const uint32_t qi = tile * PAR_QTILE + x;
+                if (qi >= Q.n) continue;
+                uint4 q = Q.rec[qi];
+                if (q.z != g) continue;
+                const uint32_t j = atomicAdd(&s_nk, 1u);  // (j < PAR_QTILE: at most one per record of the tile)
+                q.y &= ~PAR_DEAD;
+                q.z = qi;
+                s_rec[j] = q;
+                s_cnt[j] = 0u;
+                if (GAP) s_gap[j] = MM_NO_SLOT;
+                if (ROLES) {
+#pragma unroll
+                    for (uint32_t r = 0; r < MM_MAX_ROLES; ++r) s_role[j * MM_MAX_ROLES + r] = 0u;
+                }
+            }
+            __syncthreads();
+            const uint32_t nk = dev_min_u32(s_nk, PAR_QTILE);
+            if (rows) {
+#pragma unroll 1
+                for (uint32_t j = 0; j < nk; ++j) {
+                    const uint4 q = s_rec[j];
+                    uint32_t* const role_row = ROLES ? &s_role[j * MM_MAX_ROLES] : s_role;
+                    uint32_t cnt = 0u, dmin = MM_NO_SLOT;
+#pragma unroll
+                    for (uint32_t r = 0; r < WT_ITERS; ++r) par_row<ROLES, GAP>(Q, q, sl[r], rt[r], cn[r], cnt, dmin, role_row);
+                    if (lane == 0 && cnt) atomicAdd(&s_cnt[j], cnt);
+                    if (GAP && dmin != MM_NO_SLOT && dmin < s_gap[j]) atomicMin(&s_gap[j], dmin);
+                }
+            }
+            if (seats) {                                  // one more row, of wave 0 of the group's first chunk alone
+#pragma unroll 1
+                for (uint32_t j = 0; j < nk; ++j) {
+                    const uint4 q = s_rec[j];
+                    uint32_t cnt = 0u, dmin = MM_NO_SLOT;
+                    par_row<ROLES, GAP>(Q, q, s_sl, s_rt, s_cn, cnt, dmin, ROLES ? &s_role[j * MM_MAX_ROLES] : s_role);
+                    if (lane == 0 && cnt) atomicAdd(&s_cnt[j], cnt);
+                    if (GAP && dmin != MM_NO_SLOT && dmin < s_gap[j]) atomicMin(&s_gap[j], dmin);
+                }
+            }
+            __syncthreads();
+            for (uint32_t j = (uint32_t)tid; j < nk; j += WT_THREADS) {
+                const uint32_t qi = s_rec[j].z;
+                if (s_cnt[j]) atomicAdd(&Q.out[qi], s_cnt[j]);
+                if (GAP && s_gap[j] != MM_NO_SLOT) atomicMin(&Q.out[(size_t)Q.stride + qi], s_gap[j]);
+            }
+            if (ROLES) {
+                for (uint32_t x = (uint32_t)tid; x < nk * MM_MAX_ROLES; x += WT_THREADS) {
+                    const uint32_t v = s_role[x];
+                    if (v) atomicAdd(&Q.out[2u * (size_t)Q.stride + (size_t)s_rec[x / MM_MAX_ROLES].z * MM_MAX_ROLES + x % MM_MAX_ROLES], v);
+                }
+            }
+            // (the next tile's first barrier stands between these reads and its staging writes)
+        }
+        __syncthreads();                                  // ... and this one before the next chunk's
+    }
+}
+
+// partners only | + by_role | + gap | all three: a column nobody asked for costs nothing
+__global__ __launch_bounds__(WT_THREADS) void k_par_count(WaitParams P, ParParams Q) { par_count_body<false, false>(P, Q); }
+__global__ __launch_bounds__(WT_THREADS) void k_par_count_role(WaitParams P, ParParams Q) { par_count_body<true, false>(P, Q); }
+__global__ __launch_bounds__(WT_THREADS) void k_par_count_gap(WaitParams P, ParParams Q) { par_count_body<false, true>(P, Q); }
+__global__ __launch_bounds__(WT_THREADS) void k_par_count_all(WaitParams P, ParParams Q) { par_count_body<true, true>(P, Q); }

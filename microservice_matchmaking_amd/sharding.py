@@ -16,7 +16,7 @@ counters / gather results — and, off the matching path, to carry the players o
 rows with their stamps, mm_enqueue_stamped on the new owners.  Unlike mm_move on one engine it is
 not all-or-nothing: a destination without room raises on every rank after the sources have expired
 their players.  `ShardedSearch.rotate` (mm_rotate) is chain-local again: every rank rotates the chains
-it owns, no collective; so is `ShardedSearch.locate` (mm_locate), a look at this rank's own chains.
+it owns, no collective; so are `ShardedSearch.locate` (mm_locate) and `ShardedSearch.partners` (mm_partners, in_mode == mode), looks at this rank's own chains.
 
 What this does NOT do, and why: split ONE chain across ranks with a
 rating-bucket halo all-gather.  A chain has one open lobby (lobby_state.ex:90-91) and one
@@ -240,6 +240,17 @@ class ShardedSearch:
         about the chains this rank owns, and there is no collective — a status request goes to the rank that holds the
         player.  -> (where, group, position, ahead, age)."""
         return self.engine.locate(mode, slots)
+
+    def partners(self, mode, slots, in_mode=None, window=None, flags=None, by_role=True, gap=True):
+        """mm_partners (include/mm_wait.h) for in_mode == mode.  Chain-local, as `locate`: the candidates are the waiting
+        players of the chain the queried player sits in, which this rank owns — no collective.  With in_mode != mode the
+        chains (mode, g) and (in_mode, g) may have different owners and the query rows would have to travel between ranks:
+        not built, NotImplementedError on every rank.  -> (partners, by_role, gap)."""
+        if in_mode is not None and in_mode != mode:
+            raise NotImplementedError("ShardedSearch.partners with in_mode != mode: chain (mode %d, g) and chain (in_mode %d, g) "
+                                      "may have different owners, and carrying query rows between ranks is not built"
+                                      % (mode, in_mode))
+        return self.engine.partners(mode, slots, None, window, flags, by_role, gap)
 
     def tick(self, mode=0):
         return self.engine.tick(mode)

@@ -1,0 +1,37 @@
+"""mm_partners (include/mm_wait.h) on a real MI355X: the drivers of tests/test_partners.py on the product's library, against
+numpy over the oracle — chains of every length at which the walk's geometry changes, query counts around the tile of
+queries, exact distances, filters, self-exclusion, marks, seats, roles, several rating groups, NONE, duplicates, NULL
+outputs, errors, the closed form, the random script, ShardedSearch — grouped into five scenarios.  Each runs in a process of
+its own (tests/partners_gpu_worker.py) under its own time limit."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "partners_gpu_worker.py")
+
+# seconds: hang guards, a generous multiple of what the oracle's side of a scenario takes (every scenario takes seconds)
+LIMITS = {"chain_lengths": 120, "query_counts": 120, "predicate_and_marks": 120, "places_and_calls": 120, "script": 120}
+
+
+# After a scenario that hung (time limit) or died of a signal (abort, segmentation fault: what a GPU fault looks like from
+# here) nothing more is started on the card from this module: the remaining scenarios fail at once and say why.
+STOPPED = []
+
+
+@pytest.mark.parametrize("case", sorted(LIMITS))
+def test_gpu_partners(case):
+    assert not STOPPED, "not started: %s" % STOPPED[0]
+    try:
+        p = subprocess.run([sys.executable, WORKER, case], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                           timeout=LIMITS[case])
+    except subprocess.TimeoutExpired as ex:
+        STOPPED.append("%s did not end within %d s" % (case, LIMITS[case]))
+        raise AssertionError("%s; output so far: %s" % (STOPPED[0], (ex.stdout or "")[-4000:]))
+    print(p.stdout)
+    if p.returncode < 0 or p.returncode in (124, 134, 137, 139):
+        STOPPED.append("%s ended with status %d" % (case, p.returncode))
+    assert p.returncode == 0, p.stdout[-4000:]
+    assert "%s ok" % case in p.stdout
