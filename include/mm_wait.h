@@ -66,8 +66,8 @@
  * an ALL-OR-NOTHING move across engines (chain (A, g) and chain (B, g) of a ShardedSearch may have
  * different owners: mm_move_out has expired the players on their source before the destination's
  * mm_enqueue_stamped can answer MM_ERR_FULL, so a full destination loses them — sharding.py raises
- * on every rank); a device-pointer variant of mm_enqueue_stamped; mm_move itself on the stamped
- * scatter (it still stamps in a kernel of its own); matching a waiting player against a wider window
+ * on every rank); a device-pointer variant of mm_enqueue_stamped (mm_move and mm_rotate hand their
+ * gathered stamps to the stamped scatter inside the engine); matching a waiting player against a wider window
  * INSIDE its own queue (a new matching rule, with no witness in the reference or the oracle — mm_partners
  * is the measurement such a decision would rest on: how many partners at window W, and nothing more);
  * ACTING on mm_partners' answer inside the engine (an mm_move that selects by partner count); mm_partners

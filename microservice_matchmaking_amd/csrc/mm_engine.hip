@@ -998,6 +998,20 @@ static __device__ __forceinline__ bool team_chain_is_fast(const struct TeamChain
 
 struct MemBlock { void* p; bool pinned; };   // a buffer the engine owns: hipMalloc'ed, or hipHostMalloc'ed (pinned)
 
+// The lists the last mm_expire, mm_move, mm_move_out or mm_rotate left on the host (include/mm_wait.h), row i of every
+// filled column the same player; a column the call does not have stays empty.
+struct WaitLists {
+    std::vector<uint32_t> slot, group, age;   // mm_expired: every one of the four calls
+    std::vector<uint32_t> new_slot;           // mm_moved: the fourth column after an mm_move or mm_rotate
+    std::vector<int32_t> rating;              // mm_moved_rows: the rows themselves after an mm_move_out —
+    std::vector<uint32_t> cons, stamp;        //     rating | rewritten constraint word | stamp
+    void clear()
+    {
+        slot.clear(); group.clear(); age.clear(); new_slot.clear();
+        rating.clear(); cons.clear(); stamp.clear();
+    }
+};
+
 struct mm_engine {
     mm_config cfg;
     std::vector<MemBlock> mem;          // every d_* and pinned h_* buffer below (dev_alloc / pin_alloc)
@@ -1105,23 +1119,18 @@ struct mm_engine {
     bool clock_on;
     uint32_t clock_now;
     uint32_t* d_stamp;         // [capacity] the clock when the slot's player was enqueued
-    uint32_t* d_wt_rows;       // [wt_max_chunks][WT_ROWS] + 1: k_wait_count's counters / k_wait_scan's ranks, the total behind them
-    uint32_t wt_max_chunks;
+    uint32_t* d_wt_rows;       // [wait_max_chunks][WT_ROWS] + 1: k_wait_count's counters / k_wait_scan's ranks, the total behind them
     uint32_t* d_wt_out;        // [3][capacity] the last mm_expire's list on the device: slot | rating group | age
     WaitGroupDev* d_wt_stats;  // [MM_MAX_GROUPS]
     uint32_t* d_wt_matched;    // waits of the last tick's matched players (k_wait_matched)
-    std::vector<uint32_t> x_slot, x_group, x_age;   // the last mm_expire's or mm_move's list (mm_expired)
-    std::vector<uint32_t> x_new;                    // ... its fourth column after an mm_move: the new slots (mm_moved)
-    std::vector<int32_t> x_rating;                  // ... and after an mm_move_out the rows themselves (mm_moved_rows):
-    std::vector<uint32_t> x_cons, x_stamp;          //     rating | rewritten constraint word | stamp
+    WaitLists x;               // the last marking call's list (mm_expired, mm_moved, mm_moved_rows)
     uint32_t* d_mv_cols;       // [4][capacity] mm_move's rows: rating | constraint word | stamp | new slot (allocated at the first mm_move)
     uint8_t* d_mv_group;       // [capacity] ... and their rating groups, the column k_bucket_* take
     uint32_t* h_mwait;         // pinned, as large as d_wt_matched: mm_matches_wait, emission order, r_L words a lobby
     uint32_t mw_n;             // lobbies of the last tick h_mwait covers (0: the clock was off at that tick)
     // mm_locate (include/mm_wait.h): nothing below is allocated, and no kernel of it runs, before the first mm_locate
     uint32_t* d_loc_tag;       // [capacity] query + 1 of a queried slot while a call runs; all zero between calls
-    uint32_t* d_loc_rows;      // [loc_max_chunks][WT_ROWS] + 1: d_wt_rows' layout, a buffer of the call's own (the clock may be off)
-    uint32_t loc_max_chunks;
+    uint32_t* d_loc_rows;      // [wait_max_chunks][WT_ROWS] + 1: d_wt_rows' layout, a buffer of the call's own (the clock may be off)
     uint32_t* d_loc_q;         // [loc_cap] the queried slots
     uint32_t* d_loc_out;       // [5][loc_cap] where | group | position | ahead | age
     uint32_t loc_cap;          // queries d_loc_q / d_loc_out have room for (they grow)
@@ -1701,8 +1710,7 @@ extern "C" int mm_reset(mm_engine* e)
         e->cancel_pending = 0;
         e->r_n = 0;
         e->mw_n = 0;
-        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();   // (the clock itself goes on: include/mm_wait.h)
-        e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
+        e->x.clear();                                      // (the clock itself goes on: include/mm_wait.h)
         e->live_upper = 0;
         std::fill(e->tk_last_len.begin(), e->tk_last_len.end(), 0u);
         const int rc = engine_reset_device(e);
@@ -1733,8 +1741,8 @@ static int ensure_staging(mm_engine* e, size_t n)
 
 // The bucketing of a batch, queued on the engine's stream with the copy of its refusal counter behind it; all pointers
 // are device pointers.  Nothing is waited for: enqueue_device_impl does that for the two enqueue entry points, mm_move
-// puts its own kernel and copies behind this first (one wait for all of it).
-// d_in_stamp (mm_enqueue_stamped only): the batch's own stamps, scattered with the rows instead of the clock.
+// and mm_rotate put the copies of their list behind this first (one wait for all of it).
+// d_in_stamp (mm_enqueue_stamped, mm_move, mm_rotate): the batch's own stamps, scattered with the rows instead of the clock.
 static int enqueue_device_launch(mm_engine* e, uint32_t n, const int32_t* d_rating, const uint32_t* d_cons,
                                  const uint8_t* d_group, const uint32_t* d_slot_sel, uint32_t* d_out_slot,
                                  const uint32_t* d_in_stamp = nullptr)
@@ -1823,6 +1831,13 @@ static int pick_free_slots(const mm_engine* e, uint32_t n, std::vector<uint32_t>
     return sel.size() == n;
 }
 
+// The ring position behind a batch of n that pick_free_slots placed: refused rows use up their positions too.
+static uint32_t ring_after(const mm_engine* e, uint32_t n, const std::vector<uint32_t>& sel, bool contiguous)
+{
+    const uint32_t cap = e->cfg.capacity;
+    return contiguous ? (uint32_t)(((unsigned long long)e->next_slot + n) % cap) : (sel[n - 1] + 1u) % cap;
+}
+
 // mm_enqueue, and with `stamp` mm_enqueue_stamped (include/mm_wait.h): the same call in every respect but the stamps.
 static int enqueue_host(mm_engine* e, uint32_t n, const int32_t* rating, const uint32_t* cons, const uint8_t* group,
                         const uint32_t* stamp, bool stamped, uint32_t* out_slot, mm_enqueue_stats* st)
@@ -1869,8 +1884,7 @@ static int enqueue_host(mm_engine* e, uint32_t n, const int32_t* rating, const u
                                   stamped ? e->d_in_stamp : NULL));   // syncs: `sel` outlives the copy
         for (uint32_t i = 0; i < n; ++i)
             if (slots[i] != MM_NO_SLOT) e->h_state[slots[i]] = MM_ST_LIVE;
-        e->next_slot = contiguous ? (uint32_t)(((unsigned long long)e->next_slot + n) % e->cfg.capacity)
-                                  : (sel[n - 1] + 1u) % e->cfg.capacity;
+        e->next_slot = ring_after(e, n, sel, contiguous);
         e->live_upper += n - rejected;
         if (st) {
             st->accepted = n - rejected;
@@ -3329,15 +3343,18 @@ extern "C" int mm_restore(mm_engine* e, const void* buf, uint64_t bytes)
 static_assert(sizeof(WaitGroupDev) == sizeof(mm_wait_group) && offsetof(WaitGroupDev, age_sum) == offsetof(mm_wait_group, age_sum) &&
               offsetof(WaitGroupDev, hist) == offsetof(mm_wait_group, hist) && MM_WAIT_HIST == 33u, "WaitGroupDev is mm_wait_group");
 
+// The chunks of one mode's walk, at the most: its queues hold at most `capacity` players between them, and a group has at
+// least one chunk — sum of ceil(len / WT_CHUNK) <= capacity / WT_CHUNK + groups.  The rows of the clock (d_wt_rows) and of
+// the lookup (d_loc_rows) are sized by it.
+static uint32_t wait_max_chunks(const mm_engine* e) { return (uint32_t)(e->cfg.capacity / WT_CHUNK + e->cfg.n_groups + 1u); }
+
 // The device arrays of the feature, at the first mm_clock_set (or a version-2 mm_restore): all six, or none.
 static int wait_alloc(mm_engine* e)
 {
     if (e->d_stamp) return MM_OK;
     const size_t cap = e->cfg.capacity;
-    // the queues of one mode hold at most `capacity` players between them: sum of ceil(len / WT_CHUNK) <= capacity / WT_CHUNK + groups
-    e->wt_max_chunks = (uint32_t)(cap / WT_CHUNK + e->cfg.n_groups + 1u);
     const int rc = guarded([&]() -> int {          // (also a bad_alloc of the registry ends in the clean-up below)
-        MMTRY(dev_alloc(e, e->d_wt_rows, ((size_t)e->wt_max_chunks * WT_ROWS + 1u) * sizeof(uint32_t)));
+        MMTRY(dev_alloc(e, e->d_wt_rows, ((size_t)wait_max_chunks(e) * WT_ROWS + 1u) * sizeof(uint32_t)));
         MMTRY(dev_alloc(e, e->d_wt_out, 3u * cap * sizeof(uint32_t)));
         MMTRY(dev_alloc(e, e->d_wt_stats, MM_MAX_GROUPS * sizeof(WaitGroupDev)));
         MMTRY(dev_alloc(e, e->d_wt_matched, (cap + (size_t)MM_MAX_LOBBY * MM_MAX_GROUPS + 64u) * sizeof(uint32_t)));
@@ -3361,7 +3378,7 @@ static WaitParams wait_params(const mm_engine* e, uint32_t mode, uint32_t max_ag
     P.teams = e->cfg.modes[mode].teams;
     P.now = e->clock_now;
     P.max_age = max_age;
-    P.max_chunks = e->wt_max_chunks;
+    P.max_chunks = wait_max_chunks(e);
     P.chains = e->d_chains;
     P.q_slot = e->d_q_slot;
     P.stamp = e->d_stamp;
@@ -3374,12 +3391,13 @@ static WaitParams wait_params(const mm_engine* e, uint32_t mode, uint32_t max_ag
     return P;
 }
 
-// Workgroups for a pass over the mode's chunks: enough for everybody who can be queued (live_upper bounds the players of
-// all modes), never more than there are chunks; the kernels stride over the chunks, so a smaller grid is only slower.
+// Workgroups for a pass over the mode's chunks, the clock's calls and the lookup's alike: enough for everybody who can be
+// queued (live_upper bounds the players of all modes), never more than there are chunks; the kernels stride over the
+// chunks, so a smaller grid is only slower.
 static uint32_t wait_grid(const mm_engine* e)
 {
-    const unsigned long long want = e->live_upper / WT_CHUNK + e->cfg.n_groups;
-    return (uint32_t)(want < e->wt_max_chunks ? want : e->wt_max_chunks);
+    const unsigned long long want = e->live_upper / WT_CHUNK + e->cfg.n_groups, most = wait_max_chunks(e);
+    return (uint32_t)(want < most ? want : most);
 }
 
 extern "C" int mm_clock_set(mm_engine* e, uint32_t now)
@@ -3413,58 +3431,29 @@ extern "C" int mm_clock_get(const mm_engine* e, uint32_t* now, uint32_t* enabled
     return MM_OK;
 }
 
-// *marked_on_device: k_wait_scatter has been queued — from there on the device's ActiveUser mirror may hold marks the
-// host's does not know yet, and a failure must not leave the engine usable (mm_expire below).
-static int expire_impl(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t* n_expired, bool* marked_on_device)
-{
-    {
-        const WaitParams P = wait_params(e, mode, max_age);
-        const uint32_t grid = wait_grid(e);
-        uint32_t* const d_total = e->d_wt_rows + (size_t)e->wt_max_chunks * WT_ROWS;
-        hipLaunchKernelGGL(k_wait_count, dim3(grid), dim3(WT_THREADS), 0, e->stream, P);
-        hipLaunchKernelGGL(k_wait_scan, dim3(1), dim3(WT_THREADS), 0, e->stream, P);
-        HIPCHK(e, hipGetLastError());
-        *marked_on_device = true;
-        hipLaunchKernelGGL(k_wait_scatter, dim3(grid), dim3(WT_THREADS), 0, e->stream, P);
-        HIPCHK(e, hipGetLastError());
-        HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        const uint32_t k = e->h_counters[1];
-        if (k > e->cfg.capacity) return MM_ERR_INTERNAL;
-        if (k == 0u) return MM_OK;
-        e->x_slot.resize(k); e->x_group.resize(k); e->x_age.resize(k);
-        HIPCHK(e, hipMemcpyAsync(e->x_slot.data(), P.out_slot, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipMemcpyAsync(e->x_group.data(), P.out_group, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipMemcpyAsync(e->x_age.data(), P.out_age, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        // the host mirrors, as mm_cancel leaves them for these slots
-        uint32_t marked = 0;
-        for (uint32_t i = 0; i < k; ++i) {
-            const uint32_t sl = e->x_slot[i];
-            if (sl < e->cfg.capacity && e->h_state[sl] == MM_ST_LIVE) { e->h_state[sl] = MM_ST_CANCELLED; ++marked; }
-        }
-        e->cancel_pending += k;
-        if (n_expired) *n_expired = k;
-        return marked == k ? MM_OK : MM_ERR_INTERNAL;         // (the device's ActiveUser mirror and the host's disagree)
-    }
-}
+// ---- the marking calls (mm_expire, mm_move, mm_move_out, mm_rotate): one entry protocol, and the stages their bodies share ----
 
-extern "C" int mm_expire(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t* n_expired)
+// The entry of a marking call, behind its own argument and MM_ERR_STATE checks: the last call's lists go and the
+// out-counters read 0, then `body(&marked_on_device)` runs under `guarded`.  The body sets the flag right before it queues
+// its first marking kernel: from there on the device's ActiveUser mirror may hold marks the host's does not know yet.  A
+// failure leaves no half-filled list for mm_expired / mm_moved / mm_moved_rows and zeroed counters; and once the flag is
+// set, h_state and cancel_pending may lack marks the device has — the pool is as undefined as after a tick that failed
+// half way, and the engine answers MM_ERR_STATE until mm_reset or mm_restore (mm_engine.h).
+template <class Body>
+static int marking_call(mm_engine* e, const char* name, std::initializer_list<uint32_t*> counters, Body&& body)
 {
-    if (!e || mode >= e->cfg.n_modes) return MM_ERR_INVALID_ARG;
-    if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
     ON_ENGINE_DEVICE(e);
-    RoctxRange rr("mm_expire");
-    e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
-    e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
-    if (n_expired) *n_expired = 0;
+    RoctxRange rr(name);
+    const auto nothing = [&]() {
+        e->x.clear();
+        for (uint32_t* c : counters)
+            if (c) *c = 0;
+    };
+    nothing();
     bool marked_on_device = false;
-    const int rc = guarded([&]() -> int { return expire_impl(e, mode, max_age, n_expired, &marked_on_device); });
+    const int rc = guarded([&]() -> int { return body(&marked_on_device); });
     if (rc != MM_OK) {
-        // no half-filled list for mm_expired; and once the marks may be on the device while h_state and cancel_pending do
-        // not have them, the pool is as undefined as after a tick that failed half way: mm_reset or mm_restore (mm_engine.h)
-        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear();
-        if (n_expired) *n_expired = 0;
+        nothing();
         if (marked_on_device) {
             (void)hipStreamSynchronize(e->stream);
             e->poisoned = true;
@@ -3473,16 +3462,98 @@ extern "C" int mm_expire(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t
     return rc;
 }
 
+// How many a count selected: the word at d_total, behind ONE wait on the stream.
+static int read_selected(mm_engine* e, const uint32_t* d_total, uint32_t* k)
+{
+    HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    *k = e->h_counters[1];
+    return *k > e->cfg.capacity ? MM_ERR_INTERNAL : MM_OK;
+}
+
+// The selection by age: k_wait_count and k_wait_scan over P's mode, and the total comes back.  and_mark (mm_expire only,
+// which needs no slot and so cannot be refused): the MARKING kernel k_wait_scatter is queued too, in FRONT of that wait —
+// one round trip fewer — and *and_mark is set first, as marking_call asks.  Everybody else passes nothing and learns the
+// count before anything is marked.
+static int wait_select(mm_engine* e, const WaitParams& P, uint32_t grid, uint32_t* k, bool* and_mark = nullptr)
+{
+    hipLaunchKernelGGL(k_wait_count, dim3(grid), dim3(WT_THREADS), 0, e->stream, P);
+    hipLaunchKernelGGL(k_wait_scan, dim3(1), dim3(WT_THREADS), 0, e->stream, P);
+    HIPCHK(e, hipGetLastError());
+    if (and_mark) {
+        *and_mark = true;
+        hipLaunchKernelGGL(k_wait_scatter, dim3(grid), dim3(WT_THREADS), 0, e->stream, P);
+        HIPCHK(e, hipGetLastError());
+    }
+    return read_selected(e, P.rows + (size_t)P.max_chunks * WT_ROWS, k);
+}
+
+// The list of k players on its way to the host, queued: slot, rating group and age from d_wt_out (every scatter writes
+// them there), then the new slots (d_new: mm_move, mm_rotate) or the rows (mm_move_out).  The caller waits.
+static int fetch_list(mm_engine* e, uint32_t k, const uint32_t* d_new, const MoveCols* rows)
+{
+    const size_t cap = e->cfg.capacity, bytes = (size_t)k * sizeof(uint32_t);
+    WaitLists& x = e->x;
+    x.slot.resize(k); x.group.resize(k); x.age.resize(k);
+    if (d_new) x.new_slot.resize(k);
+    if (rows) { x.rating.resize(k); x.cons.resize(k); x.stamp.resize(k); }
+    HIPCHK(e, hipMemcpyAsync(x.slot.data(), e->d_wt_out, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(x.group.data(), e->d_wt_out + cap, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(x.age.data(), e->d_wt_out + 2u * cap, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (d_new) HIPCHK(e, hipMemcpyAsync(x.new_slot.data(), d_new, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (rows) {
+        HIPCHK(e, hipMemcpyAsync(x.rating.data(), rows->rating, bytes, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipMemcpyAsync(x.cons.data(), rows->cons, bytes, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipMemcpyAsync(x.stamp.data(), rows->stamp, bytes, hipMemcpyDeviceToHost, e->stream));
+    }
+    return MM_OK;
+}
+
+// The host mirrors of the marks, as mm_cancel leaves them for the list's k slots.  MM_ERR_INTERNAL: a listed slot was not
+// LIVE on the host — the device's ActiveUser mirror and the host's disagree.
+static int mirror_marks(mm_engine* e, uint32_t k)
+{
+    // (locals: a byte store may alias anything, so through `e` every iteration would load the vectors' pointers again —
+    // at half a million rows these loops are a tenth of the call)
+    const uint32_t cap = e->cfg.capacity;
+    const uint32_t* const list = e->x.slot.data();
+    uint8_t* const state = e->h_state.data();
+    uint32_t marked = 0;
+    for (uint32_t i = 0; i < k; ++i) {
+        const uint32_t sl = list[i];
+        if (sl < cap && state[sl] == MM_ST_LIVE) { state[sl] = MM_ST_CANCELLED; ++marked; }
+    }
+    e->cancel_pending += k;
+    return marked == k ? MM_OK : MM_ERR_INTERNAL;
+}
+
+// mm_expire: count, scan and scatter in one go, the total, then the list's three columns and the host mirrors.
+extern "C" int mm_expire(mm_engine* e, uint32_t mode, uint32_t max_age, uint32_t* n_expired)
+{
+    if (!e || mode >= e->cfg.n_modes) return MM_ERR_INVALID_ARG;
+    if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
+    return marking_call(e, "mm_expire", { n_expired }, [&](bool* marked_on_device) -> int {
+        uint32_t k = 0;
+        // (with the flag: k_wait_scatter is queued in here, so from this call on a failure poisons the engine)
+        MMTRY(wait_select(e, wait_params(e, mode, max_age), wait_grid(e), &k, marked_on_device));
+        if (k == 0u) return MM_OK;
+        MMTRY(fetch_list(e, k, nullptr, nullptr));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (n_expired) *n_expired = k;
+        return mirror_marks(e, k);
+    });
+}
+
 extern "C" int mm_expired(mm_engine* e, uint32_t first, uint32_t count, uint32_t* slots, uint32_t* group, uint32_t* age)
 {
     if (!e) return MM_ERR_INVALID_ARG;
     if (e->poisoned) return MM_ERR_STATE;
-    const size_t n = e->x_slot.size();
+    const size_t n = e->x.slot.size();
     if (first > n || count > n - first) return MM_ERR_RANGE;
     if (count == 0) return MM_OK;
-    if (slots) memcpy(slots, &e->x_slot[first], (size_t)count * sizeof(uint32_t));
-    if (group) memcpy(group, &e->x_group[first], (size_t)count * sizeof(uint32_t));
-    if (age) memcpy(age, &e->x_age[first], (size_t)count * sizeof(uint32_t));
+    if (slots) memcpy(slots, &e->x.slot[first], (size_t)count * sizeof(uint32_t));
+    if (group) memcpy(group, &e->x.group[first], (size_t)count * sizeof(uint32_t));
+    if (age) memcpy(age, &e->x.age[first], (size_t)count * sizeof(uint32_t));
     return MM_OK;
 }
 
@@ -3499,8 +3570,7 @@ static int loc_alloc(mm_engine* e, uint32_t n)
     const size_t cap = e->cfg.capacity;
     return guarded([&]() -> int {
         if (!e->d_loc_tag) {
-            e->loc_max_chunks = (uint32_t)(cap / WT_CHUNK + e->cfg.n_groups + 1u);          // as wait_alloc sizes d_wt_rows
-            MMTRY(dev_alloc(e, e->d_loc_rows, ((size_t)e->loc_max_chunks * WT_ROWS + 1u) * sizeof(uint32_t)));
+            MMTRY(dev_alloc(e, e->d_loc_rows, ((size_t)wait_max_chunks(e) * WT_ROWS + 1u) * sizeof(uint32_t)));   // as wait_alloc sizes d_wt_rows
             uint32_t* tag = NULL;
             MMTRY(dev_alloc(e, tag, cap * sizeof(uint32_t)));
             const hipError_t rc = hipMemsetAsync(tag, 0, cap * sizeof(uint32_t), e->stream);
@@ -3525,41 +3595,46 @@ static int loc_alloc(mm_engine* e, uint32_t n)
     });
 }
 
-// wait_grid over the rows of the lookup's own scratch (mm_locate, mm_partners): the clock's rows may not exist.
-static uint32_t loc_grid(const mm_engine* e)
+// The lookup mm_locate and mm_partners share, queued into loc_alloc's scratch: the queried slots go to the device, then
+// k_loc_mark, k_loc_count and the unchanged k_wait_scan when `ahead` is wanted, k_loc_scatter, k_loc_collect, k_loc_clear —
+// where | group | position | ahead | age of every query in d_loc_out, loc_cap words a column.  The launches are neither
+// checked nor waited for here: the caller's hipGetLastError and its one wait cover them.  *walk: the parameters of the
+// pass over `mode` (mm_partners walks in_mode with a copy).
+static int loc_launch(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, bool want_ahead, WaitParams* walk)
 {
-    const unsigned long long want = e->live_upper / WT_CHUNK + e->cfg.n_groups;
-    return (uint32_t)(want < e->loc_max_chunks ? want : e->loc_max_chunks);
-}
-
-static int locate_impl(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, uint32_t* where, uint32_t* group,
-                       uint32_t* position, uint32_t* ahead, uint32_t* age)
-{
-    MMTRY(loc_alloc(e, n));
     const uint32_t cap = e->cfg.capacity;
     WaitParams P = wait_params(e, mode, 0u);                   // (stamp == NULL while the clock is off: every age reads 0)
     P.stamp = e->clock_on ? e->d_stamp : NULL;
-    P.max_chunks = e->loc_max_chunks;
-    P.rows = e->d_loc_rows;
+    P.rows = e->d_loc_rows;                                    // the lookup's own rows: the clock's may not exist
     P.out_slot = NULL; P.out_group = NULL; P.out_age = NULL; P.stats = NULL;
     LocParams L;
     L.n = n;
     L.stride = e->loc_cap;
-    L.want_ahead = ahead ? 1u : 0u;
+    L.want_ahead = want_ahead ? 1u : 0u;
     L.q = e->d_loc_q;
     L.tag = e->d_loc_tag;
     L.out = e->d_loc_out;
-    const uint32_t grid = loc_grid(e);
+    const uint32_t grid = wait_grid(e);
     const dim3 per_query((n + WT_THREADS - 1u) / WT_THREADS), wg(WT_THREADS);
     HIPCHK(e, hipMemcpyAsync(e->d_loc_q, slots, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(k_loc_mark, per_query, wg, 0, e->stream, L, cap);
-    if (ahead) {
+    if (want_ahead) {
         hipLaunchKernelGGL(k_loc_count, dim3(grid), wg, 0, e->stream, P);
         hipLaunchKernelGGL(k_wait_scan, dim3(1), wg, 0, e->stream, P);
     }
     hipLaunchKernelGGL(k_loc_scatter, dim3(grid), wg, 0, e->stream, P, L);
     hipLaunchKernelGGL(k_loc_collect, per_query, wg, 0, e->stream, L, cap);
     hipLaunchKernelGGL(k_loc_clear, per_query, wg, 0, e->stream, L, cap);
+    *walk = P;
+    return MM_OK;
+}
+
+static int locate_impl(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, uint32_t* where, uint32_t* group,
+                       uint32_t* position, uint32_t* ahead, uint32_t* age)
+{
+    MMTRY(loc_alloc(e, n));
+    WaitParams P;
+    MMTRY(loc_launch(e, mode, n, slots, ahead != NULL, &P));
     HIPCHK(e, hipGetLastError());
     uint32_t* const cols[5] = { where, group, position, ahead, age };
     for (uint32_t c = 0; c < 5u; ++c)
@@ -3618,19 +3693,8 @@ static int partners_impl(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t
 {
     MMTRY(loc_alloc(e, n));
     MMTRY(par_alloc(e, n));
-    const uint32_t cap = e->cfg.capacity;
-    WaitParams P = wait_params(e, mode, 0u);                   // the lookup: mm_locate's passes, `ahead` off
-    P.stamp = e->clock_on ? e->d_stamp : NULL;
-    P.max_chunks = e->loc_max_chunks;
-    P.rows = e->d_loc_rows;
-    P.out_slot = NULL; P.out_group = NULL; P.out_age = NULL; P.stats = NULL;
-    LocParams L;
-    L.n = n;
-    L.stride = e->loc_cap;
-    L.want_ahead = 0u;
-    L.q = e->d_loc_q;
-    L.tag = e->d_loc_tag;
-    L.out = e->d_loc_out;
+    WaitParams P;                                              // the lookup: mm_locate's passes, `ahead` off
+    MMTRY(loc_launch(e, mode, n, slots, false, &P));
     WaitParams C = P;                                          // the count: the same walk over in_mode's chains
     C.mode = in_mode;
     C.teams = e->cfg.modes[in_mode].teams;
@@ -3646,18 +3710,13 @@ static int partners_impl(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t
     Q.q_cons = e->d_q_cons;
     Q.rec = e->d_par_rec;
     Q.out = e->d_par_out;
-    const uint32_t grid = loc_grid(e);
+    const uint32_t grid = wait_grid(e);
     // the count's grid: `grid` workgroups stride over the chunks, and as many times that over the query tiles as keeps the
     // whole near 2048 workgroups — a short queue with many queries spreads over the tiles, a long one keeps its registers
     const uint32_t n_tiles = (n + PAR_QTILE - 1u) / PAR_QTILE, room = 2048u / grid ? 2048u / grid : 1u;
     Q.gx = grid;
     const uint32_t gy = n_tiles < room ? n_tiles : room;
     const dim3 per_query((n + WT_THREADS - 1u) / WT_THREADS), wg(WT_THREADS), cg(grid * gy);
-    HIPCHK(e, hipMemcpyAsync(e->d_loc_q, slots, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_loc_mark, per_query, wg, 0, e->stream, L, cap);
-    hipLaunchKernelGGL(k_loc_scatter, dim3(grid), wg, 0, e->stream, P, L);
-    hipLaunchKernelGGL(k_loc_collect, per_query, wg, 0, e->stream, L, cap);
-    hipLaunchKernelGGL(k_loc_clear, per_query, wg, 0, e->stream, L, cap);
     hipLaunchKernelGGL(k_par_gather, per_query, wg, 0, e->stream, P, Q);
     if (by_role && gap) hipLaunchKernelGGL(k_par_count_all, cg, wg, 0, e->stream, C, Q);
     else if (by_role) hipLaunchKernelGGL(k_par_count_role, cg, wg, 0, e->stream, C, Q);
@@ -3711,78 +3770,81 @@ static int move_alloc(mm_engine* e)
     return rc;
 }
 
-// mm_move = the selection of mm_expire, then an enqueue of the selected rows into the other mode without leaving the
-// device.  The count comes back BEFORE anything is marked: the slots are picked on the host (pick_free_slots, as for any
-// mm_enqueue), and a pool without room for them refuses the call with nothing changed.  From k_move_scatter on the
-// rule is expire_impl's: a failure leaves marks the host does not know, so the caller poisons the engine.
-static int move_impl(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
-                     uint32_t* n_selected, uint32_t* n_refused, bool* marked_on_device)
+// The columns k_move_scatter and k_rotate_scatter gather beside the list (move_alloc's), for to_mode.  from_queue: the rows
+// come from the queues' own columns and the LobbyDev records with the word rewritten (k_move_scatter); otherwise from the
+// LobbyDev records alone and as they are (k_rotate_scatter reads neither the queue columns nor `keep`).
+static MoveCols move_cols(const mm_engine* e, uint32_t cons_clear, uint32_t to_mode, bool from_queue)
 {
-    MMTRY(move_alloc(e));
-    const WaitParams P = wait_params(e, from_mode, max_age);
-    const uint32_t grid = wait_grid(e), cap = e->cfg.capacity;
-    uint32_t* const d_total = e->d_wt_rows + (size_t)e->wt_max_chunks * WT_ROWS;
-    hipLaunchKernelGGL(k_wait_count, dim3(grid), dim3(WT_THREADS), 0, e->stream, P);
-    hipLaunchKernelGGL(k_wait_scan, dim3(1), dim3(WT_THREADS), 0, e->stream, P);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    const uint32_t k = e->h_counters[1];
-    if (k > cap) return MM_ERR_INTERNAL;
-    if (k == 0u) return MM_OK;
-    // the old slots stay held until from_mode's next purge: the pool needs k FREE slots beside them
-    std::vector<uint32_t> sel;
-    bool contiguous = false;
-    if (!pick_free_slots(e, k, sel, &contiguous)) return MM_ERR_FULL;
-    if (!contiguous) {
-        MMTRY(ensure_staging(e, k));
-        HIPCHK(e, hipMemcpyAsync(e->d_in_sel, sel.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    }
+    const size_t cap = e->cfg.capacity;
     MoveCols M;
-    M.q_rating = e->d_q_rating;
-    M.q_cons = e->d_q_cons;
+    M.q_rating = from_queue ? e->d_q_rating : nullptr;
+    M.q_cons = from_queue ? e->d_q_cons : nullptr;
     M.rating = (int32_t*)e->d_mv_cols;
     M.cons = e->d_mv_cols + cap;
-    M.stamp = e->d_mv_cols + 2u * (size_t)cap;
+    M.stamp = e->d_mv_cols + 2u * cap;
     M.group = e->d_mv_group;
     M.keep = ~cons_clear & MM_CONS_USER_MASK & ~0xFu;
     M.to_mode = to_mode;
-    uint32_t* const d_new = e->d_mv_cols + 3u * (size_t)cap;
-    *marked_on_device = true;
-    hipLaunchKernelGGL(k_move_scatter, dim3(grid), dim3(WT_THREADS), 0, e->stream, P, M);
-    HIPCHK(e, hipGetLastError());
-    MMTRY(enqueue_device_launch(e, k, M.rating, M.cons, M.group, contiguous ? NULL : e->d_in_sel, d_new));
-    hipLaunchKernelGGL(k_move_stamp, dim3((k + WT_THREADS - 1u) / WT_THREADS), dim3(WT_THREADS), 0, e->stream, k, cap, d_new,
-                       M.stamp, e->d_stamp);
-    HIPCHK(e, hipGetLastError());
-    e->x_slot.resize(k); e->x_group.resize(k); e->x_age.resize(k); e->x_new.resize(k);
-    HIPCHK(e, hipMemcpyAsync(e->x_slot.data(), P.out_slot, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->x_group.data(), P.out_group, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->x_age.data(), P.out_age, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->x_new.data(), d_new, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));           // `sel` must outlive its copy, too
-    const uint32_t rejected = e->h_counters[1];
-    // the host mirrors: the old slots as mm_cancel leaves them, the new ones as mm_enqueue does
-    uint32_t marked = 0, seated = 0;
-    for (uint32_t i = 0; i < k; ++i) {
-        const uint32_t sl = e->x_slot[i];
-        if (sl < cap && e->h_state[sl] == MM_ST_LIVE) { e->h_state[sl] = MM_ST_CANCELLED; ++marked; }
-    }
-    for (uint32_t i = 0; i < k; ++i) {
-        const uint32_t sl = e->x_new[i];
-        if (sl == MM_NO_SLOT) continue;
-        if (sl < cap && e->h_state[sl] == MM_ST_FREE) { e->h_state[sl] = MM_ST_LIVE; ++seated; }
-        else return MM_ERR_INTERNAL;
-    }
-    e->cancel_pending += k;
-    e->next_slot = contiguous ? (uint32_t)(((unsigned long long)e->next_slot + k) % cap) : (sel[k - 1] + 1u) % cap;
-    if (rejected > k || seated != k - rejected) return MM_ERR_INTERNAL;
-    e->live_upper += seated;
-    if (n_selected) *n_selected = k;
-    if (n_refused) *n_refused = rejected;
-    return marked == k ? MM_OK : MM_ERR_INTERNAL;             // (the device's ActiveUser mirror and the host's disagree)
+    return M;
 }
 
+// k new slots as mm_enqueue takes them (pick_free_slots): the plain ring range, or `sel` staged in d_in_sel when a waiting
+// player is in the way.  MM_ERR_FULL: fewer FREE slots than that, and nothing has changed.  `sel` must outlive its copy:
+// the caller's next wait.
+static int take_slots(mm_engine* e, uint32_t k, std::vector<uint32_t>& sel, bool* contiguous)
+{
+    if (!pick_free_slots(e, k, sel, contiguous)) return MM_ERR_FULL;
+    if (!*contiguous) {
+        MMTRY(ensure_staging(e, k));
+        HIPCHK(e, hipMemcpyAsync(e->d_in_sel, sel.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    }
+    return MM_OK;
+}
+
+// The second half of mm_move and mm_rotate, behind the count: the k selected players leave their slots and are enqueued
+// again from M's columns without leaving the device.  The slots are taken FIRST — the old ones stay held until their
+// mode's next purge, so the pool needs k FREE slots beside them, and a pool without them refuses the call with nothing
+// changed.  Then `scatter` queues the call's marking kernel (the list into d_wt_out, the rows into M, state[] marked); the
+// rows go through the bucketing with their gathered stamps — k_bucket_scatter<true> writes stamp[new slot] = the player's
+// own, and nothing for a refused row — its out_slot column is the list's fourth; the four columns come back behind ONE
+// wait with the refusal counter; the host mirrors follow: the old slots as mm_cancel leaves them, the new ones as
+// mm_enqueue does.  From the scatter on a failure poisons the engine (marking_call), so on the MM_ERR_INTERNAL paths — a
+// refused row of a rotation, a new slot that was not FREE, mirrors that disagree — it does not matter how far h_state,
+// cancel_pending, the ring position and live_upper have got: nothing reads them before mm_reset or mm_restore.
+template <class Scatter>
+static int requeue_selected(mm_engine* e, uint32_t k, const MoveCols& M, bool* marked_on_device, Scatter&& scatter, uint32_t* refused)
+{
+    const uint32_t cap = e->cfg.capacity;
+    std::vector<uint32_t> sel;
+    bool contiguous = false;
+    MMTRY(take_slots(e, k, sel, &contiguous));
+    uint32_t* const d_new = e->d_mv_cols + 3u * (size_t)cap;
+    *marked_on_device = true;
+    scatter();
+    HIPCHK(e, hipGetLastError());
+    MMTRY(enqueue_device_launch(e, k, M.rating, M.cons, M.group, contiguous ? NULL : e->d_in_sel, d_new, M.stamp));
+    MMTRY(fetch_list(e, k, d_new, nullptr));
+    HIPCHK(e, hipStreamSynchronize(e->stream));           // `sel` must outlive its copy, too
+    const uint32_t rejected = e->h_counters[1];
+    const int agree = mirror_marks(e, k);
+    const uint32_t* const got = e->x.new_slot.data();
+    uint8_t* const state = e->h_state.data();              // (locals, as in mirror_marks)
+    uint32_t seated = 0;
+    for (uint32_t i = 0; i < k; ++i) {
+        const uint32_t sl = got[i];
+        if (sl == MM_NO_SLOT) continue;                    // a refused row: expired only
+        if (sl < cap && state[sl] == MM_ST_FREE) { state[sl] = MM_ST_LIVE; ++seated; }
+        else return MM_ERR_INTERNAL;
+    }
+    e->next_slot = ring_after(e, k, sel, contiguous);
+    if (rejected > k || seated != k - rejected) return MM_ERR_INTERNAL;
+    e->live_upper += seated;
+    *refused = rejected;
+    return agree;
+}
+
+// mm_move = the selection of mm_expire, then requeue_selected into the other mode.  The count comes back BEFORE anything
+// is marked; k_move_scatter is k_wait_scatter with the rows gathered beside the list.  Two waits in all.
 extern "C" int mm_move(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
                        uint32_t* n_selected, uint32_t* n_refused)
 {
@@ -3790,90 +3852,37 @@ extern "C" int mm_move(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint3
         (cons_clear & (~MM_CONS_USER_MASK | 0xFu)))
         return MM_ERR_INVALID_ARG;
     if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
-    ON_ENGINE_DEVICE(e);
-    RoctxRange rr("mm_move");
-    e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
-    e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
-    if (n_selected) *n_selected = 0;
-    if (n_refused) *n_refused = 0;
-    bool marked_on_device = false;
-    const int rc = guarded([&]() -> int {
-        return move_impl(e, from_mode, to_mode, max_age, cons_clear, n_selected, n_refused, &marked_on_device);
+    return marking_call(e, "mm_move", { n_selected, n_refused }, [&](bool* marked_on_device) -> int {
+        MMTRY(move_alloc(e));
+        const WaitParams P = wait_params(e, from_mode, max_age);
+        const uint32_t grid = wait_grid(e);
+        uint32_t k = 0, refused = 0;
+        MMTRY(wait_select(e, P, grid, &k));
+        if (k == 0u) return MM_OK;
+        const MoveCols M = move_cols(e, cons_clear, to_mode, true);
+        MMTRY(requeue_selected(e, k, M, marked_on_device, [&]() {
+            hipLaunchKernelGGL(k_move_scatter, dim3(grid), dim3(WT_THREADS), 0, e->stream, P, M);
+        }, &refused));
+        if (n_selected) *n_selected = k;
+        if (n_refused) *n_refused = refused;
+        return MM_OK;
     });
-    if (rc != MM_OK) {
-        // as mm_expire: no half-filled list, and an engine whose device may hold marks the host does not is poisoned
-        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
-        if (n_selected) *n_selected = 0;
-        if (n_refused) *n_refused = 0;
-        if (marked_on_device) {
-            (void)hipStreamSynchronize(e->stream);
-            e->poisoned = true;
-        }
-    }
-    return rc;
 }
 
 extern "C" int mm_moved(mm_engine* e, uint32_t first, uint32_t count, uint32_t* new_slot)
 {
     if (!e) return MM_ERR_INVALID_ARG;
     if (e->poisoned) return MM_ERR_STATE;
-    const size_t n = e->x_new.size();
+    const size_t n = e->x.new_slot.size();
     if (first > n || count > n - first) return MM_ERR_RANGE;
     if (count == 0 || !new_slot) return MM_OK;
-    memcpy(new_slot, &e->x_new[first], (size_t)count * sizeof(uint32_t));
+    memcpy(new_slot, &e->x.new_slot[first], (size_t)count * sizeof(uint32_t));
     return MM_OK;
 }
 
 // mm_move_out = the first half of mm_move: the selection and marks of mm_expire with k_move_scatter's rows beside the
 // list, and no enqueue — no slot is picked, no other queue touched.  One round trip for the count (nothing selected:
-// nothing more is launched), then the six columns come back together.  Failures as expire_impl's.
-static int move_out_impl(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
-                         uint32_t* n_selected, bool* marked_on_device)
-{
-    MMTRY(move_alloc(e));
-    const WaitParams P = wait_params(e, from_mode, max_age);
-    const uint32_t grid = wait_grid(e), cap = e->cfg.capacity;
-    uint32_t* const d_total = e->d_wt_rows + (size_t)e->wt_max_chunks * WT_ROWS;
-    hipLaunchKernelGGL(k_wait_count, dim3(grid), dim3(WT_THREADS), 0, e->stream, P);
-    hipLaunchKernelGGL(k_wait_scan, dim3(1), dim3(WT_THREADS), 0, e->stream, P);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    const uint32_t k = e->h_counters[1];
-    if (k > cap) return MM_ERR_INTERNAL;
-    if (k == 0u) return MM_OK;
-    MoveCols M;
-    M.q_rating = e->d_q_rating;
-    M.q_cons = e->d_q_cons;
-    M.rating = (int32_t*)e->d_mv_cols;
-    M.cons = e->d_mv_cols + cap;
-    M.stamp = e->d_mv_cols + 2u * (size_t)cap;
-    M.group = e->d_mv_group;
-    M.keep = ~cons_clear & MM_CONS_USER_MASK & ~0xFu;
-    M.to_mode = to_mode;
-    *marked_on_device = true;
-    hipLaunchKernelGGL(k_move_scatter, dim3(grid), dim3(WT_THREADS), 0, e->stream, P, M);
-    HIPCHK(e, hipGetLastError());
-    e->x_slot.resize(k); e->x_group.resize(k); e->x_age.resize(k);
-    e->x_rating.resize(k); e->x_cons.resize(k); e->x_stamp.resize(k);
-    HIPCHK(e, hipMemcpyAsync(e->x_slot.data(), P.out_slot, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->x_group.data(), P.out_group, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->x_age.data(), P.out_age, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->x_rating.data(), M.rating, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->x_cons.data(), M.cons, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->x_stamp.data(), M.stamp, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    // the host mirrors, as mm_cancel leaves them for these slots
-    uint32_t marked = 0;
-    for (uint32_t i = 0; i < k; ++i) {
-        const uint32_t sl = e->x_slot[i];
-        if (sl < cap && e->h_state[sl] == MM_ST_LIVE) { e->h_state[sl] = MM_ST_CANCELLED; ++marked; }
-    }
-    e->cancel_pending += k;
-    if (n_selected) *n_selected = k;
-    return marked == k ? MM_OK : MM_ERR_INTERNAL;             // (the device's ActiveUser mirror and the host's disagree)
-}
-
+// nothing more is launched), then the six columns come back together.
 extern "C" int mm_move_out(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
                            uint32_t* n_selected)
 {
@@ -3881,141 +3890,76 @@ extern "C" int mm_move_out(mm_engine* e, uint32_t from_mode, uint32_t to_mode, u
         (cons_clear & (~MM_CONS_USER_MASK | 0xFu)))
         return MM_ERR_INVALID_ARG;
     if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
-    ON_ENGINE_DEVICE(e);
-    RoctxRange rr("mm_move_out");
-    e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
-    e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
-    if (n_selected) *n_selected = 0;
-    bool marked_on_device = false;
-    const int rc = guarded([&]() -> int {
-        return move_out_impl(e, from_mode, to_mode, max_age, cons_clear, n_selected, &marked_on_device);
+    return marking_call(e, "mm_move_out", { n_selected }, [&](bool* marked_on_device) -> int {
+        MMTRY(move_alloc(e));
+        const WaitParams P = wait_params(e, from_mode, max_age);
+        const uint32_t grid = wait_grid(e);
+        uint32_t k = 0;
+        MMTRY(wait_select(e, P, grid, &k));
+        if (k == 0u) return MM_OK;
+        const MoveCols M = move_cols(e, cons_clear, to_mode, true);
+        *marked_on_device = true;
+        hipLaunchKernelGGL(k_move_scatter, dim3(grid), dim3(WT_THREADS), 0, e->stream, P, M);
+        HIPCHK(e, hipGetLastError());
+        MMTRY(fetch_list(e, k, nullptr, &M));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (n_selected) *n_selected = k;
+        return mirror_marks(e, k);
     });
-    if (rc != MM_OK) {
-        // as mm_expire: no half-filled list, and an engine whose device may hold marks the host does not is poisoned
-        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear();
-        e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
-        if (n_selected) *n_selected = 0;
-        if (marked_on_device) {
-            (void)hipStreamSynchronize(e->stream);
-            e->poisoned = true;
-        }
-    }
-    return rc;
 }
 
 extern "C" int mm_moved_rows(mm_engine* e, uint32_t first, uint32_t count, int32_t* rating, uint32_t* cons, uint32_t* stamp)
 {
     if (!e) return MM_ERR_INVALID_ARG;
     if (e->poisoned) return MM_ERR_STATE;
-    const size_t n = e->x_stamp.size();
+    const size_t n = e->x.stamp.size();
     if (first > n || count > n - first) return MM_ERR_RANGE;
     if (count == 0) return MM_OK;
-    if (rating) memcpy(rating, &e->x_rating[first], (size_t)count * sizeof(int32_t));
-    if (cons) memcpy(cons, &e->x_cons[first], (size_t)count * sizeof(uint32_t));
-    if (stamp) memcpy(stamp, &e->x_stamp[first], (size_t)count * sizeof(uint32_t));
+    if (rating) memcpy(rating, &e->x.rating[first], (size_t)count * sizeof(int32_t));
+    if (cons) memcpy(cons, &e->x.cons[first], (size_t)count * sizeof(uint32_t));
+    if (stamp) memcpy(stamp, &e->x.stamp[first], (size_t)count * sizeof(uint32_t));
     return MM_OK;
 }
 
 // mm_rotate = mm_move onto the players' own chains, selected by the stored lobbies instead of by age: no queue is
-// streamed, k_rotate_count and k_rotate_scatter are one workgroup each over the mode's LobbyDev records.  As in move_impl
-// the count comes back BEFORE anything is marked (pick_free_slots, MM_ERR_FULL with nothing changed); then the scatter,
-// the stamped bucketing of the gathered rows (k_bucket_scatter writes stamp[new slot] = the gathered stamp: no stamping
-// kernel) and the four columns come back behind ONE more wait.  Failures from k_rotate_scatter on as expire_impl's.
-static int rotate_impl(mm_engine* e, uint32_t mode, uint32_t max_seated, uint32_t min_queue, uint32_t* n_selected,
-                       bool* marked_on_device)
-{
-    const uint32_t cap = e->cfg.capacity;
-    RotateParams R;
-    memset(&R, 0, sizeof(R));
-    R.mode = mode;
-    R.n_groups = e->cfg.n_groups;
-    R.capacity = cap;
-    R.teams = e->cfg.modes[mode].teams;
-    R.max_seated = max_seated;
-    R.min_queue = min_queue;
-    R.chains = e->d_chains;
-    R.stamp = e->d_stamp;
-    R.state = e->d_state;
-    R.base = e->d_wt_rows;                                    // (wt_max_chunks > n_groups: room for a word per group)
-    R.total = e->d_wt_rows + (size_t)e->wt_max_chunks * WT_ROWS;
-    hipLaunchKernelGGL(k_rotate_count, dim3(1), dim3(WT_THREADS), 0, e->stream, R);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(e->h_counters + 1, R.total, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    const uint32_t k = e->h_counters[1];
-    if (k > cap || k > e->cfg.n_groups * WT_SEATS) return MM_ERR_INTERNAL;
-    if (k == 0u) return MM_OK;
-    MMTRY(move_alloc(e));
-    // the old slots stay held until the mode's next purge: the pool needs k FREE slots beside them
-    std::vector<uint32_t> sel;
-    bool contiguous = false;
-    if (!pick_free_slots(e, k, sel, &contiguous)) return MM_ERR_FULL;
-    if (!contiguous) {
-        MMTRY(ensure_staging(e, k));
-        HIPCHK(e, hipMemcpyAsync(e->d_in_sel, sel.data(), (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    }
-    MoveCols M;
-    M.q_rating = nullptr;
-    M.q_cons = nullptr;
-    M.rating = (int32_t*)e->d_mv_cols;
-    M.cons = e->d_mv_cols + cap;
-    M.stamp = e->d_mv_cols + 2u * (size_t)cap;
-    M.group = e->d_mv_group;
-    M.keep = 0u;
-    M.to_mode = mode;
-    uint32_t* const d_list = e->d_wt_out;
-    uint32_t* const d_new = e->d_mv_cols + 3u * (size_t)cap;
-    *marked_on_device = true;
-    hipLaunchKernelGGL(k_rotate_scatter, dim3(1), dim3(WT_THREADS), 0, e->stream, R, e->clock_now, d_list, d_list + cap,
-                       d_list + 2u * (size_t)cap, M);
-    HIPCHK(e, hipGetLastError());
-    MMTRY(enqueue_device_launch(e, k, M.rating, M.cons, M.group, contiguous ? NULL : e->d_in_sel, d_new, M.stamp));
-    e->x_slot.resize(k); e->x_group.resize(k); e->x_age.resize(k); e->x_new.resize(k);
-    HIPCHK(e, hipMemcpyAsync(e->x_slot.data(), d_list, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->x_group.data(), d_list + cap, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->x_age.data(), d_list + 2u * (size_t)cap, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->x_new.data(), d_new, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));           // `sel` must outlive its copy, too
-    if (e->h_counters[1] != 0u) return MM_ERR_INTERNAL;   // nobody can be refused: the mode seats them already
-    // the host mirrors: the old slots as mm_cancel leaves them, the new ones as mm_enqueue does
-    uint32_t marked = 0;
-    for (uint32_t i = 0; i < k; ++i) {
-        const uint32_t sl = e->x_slot[i];
-        if (sl < cap && e->h_state[sl] == MM_ST_LIVE) { e->h_state[sl] = MM_ST_CANCELLED; ++marked; }
-    }
-    for (uint32_t i = 0; i < k; ++i) {
-        const uint32_t sl = e->x_new[i];
-        if (sl < cap && e->h_state[sl] == MM_ST_FREE) e->h_state[sl] = MM_ST_LIVE;
-        else return MM_ERR_INTERNAL;
-    }
-    e->cancel_pending += k;
-    e->next_slot = contiguous ? (uint32_t)(((unsigned long long)e->next_slot + k) % cap) : (sel[k - 1] + 1u) % cap;
-    e->live_upper += k;
-    if (n_selected) *n_selected = k;
-    return marked == k ? MM_OK : MM_ERR_INTERNAL;             // (the device's ActiveUser mirror and the host's disagree)
-}
-
+// streamed, k_rotate_count and k_rotate_scatter are one workgroup each over the mode's LobbyDev records.  As in mm_move
+// the count comes back BEFORE anything is marked; then requeue_selected.  Two waits (one when nothing is selected).
 extern "C" int mm_rotate(mm_engine* e, uint32_t mode, uint32_t max_seated, uint32_t min_queue, uint32_t* n_selected)
 {
     if (!e || mode >= e->cfg.n_modes || max_seated == 0u) return MM_ERR_INVALID_ARG;
     if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
-    ON_ENGINE_DEVICE(e);
-    RoctxRange rr("mm_rotate");
-    e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
-    e->x_rating.clear(); e->x_cons.clear(); e->x_stamp.clear();
-    if (n_selected) *n_selected = 0;
-    bool marked_on_device = false;
-    const int rc = guarded([&]() -> int { return rotate_impl(e, mode, max_seated, min_queue, n_selected, &marked_on_device); });
-    if (rc != MM_OK) {
-        // as mm_move: no half-filled list, and an engine whose device may hold marks the host does not is poisoned
-        e->x_slot.clear(); e->x_group.clear(); e->x_age.clear(); e->x_new.clear();
-        if (n_selected) *n_selected = 0;
-        if (marked_on_device) {
-            (void)hipStreamSynchronize(e->stream);
-            e->poisoned = true;
-        }
-    }
-    return rc;
+    return marking_call(e, "mm_rotate", { n_selected }, [&](bool* marked_on_device) -> int {
+        const uint32_t cap = e->cfg.capacity;
+        RotateParams R;
+        memset(&R, 0, sizeof(R));
+        R.mode = mode;
+        R.n_groups = e->cfg.n_groups;
+        R.capacity = cap;
+        R.teams = e->cfg.modes[mode].teams;
+        R.max_seated = max_seated;
+        R.min_queue = min_queue;
+        R.chains = e->d_chains;
+        R.stamp = e->d_stamp;
+        R.state = e->d_state;
+        R.base = e->d_wt_rows;                                    // (wait_max_chunks > n_groups: room for a word per group)
+        R.total = e->d_wt_rows + (size_t)wait_max_chunks(e) * WT_ROWS;
+        hipLaunchKernelGGL(k_rotate_count, dim3(1), dim3(WT_THREADS), 0, e->stream, R);
+        HIPCHK(e, hipGetLastError());
+        uint32_t k = 0, refused = 0;
+        MMTRY(read_selected(e, R.total, &k));
+        if (k > e->cfg.n_groups * WT_SEATS) return MM_ERR_INTERNAL;
+        if (k == 0u) return MM_OK;
+        MMTRY(move_alloc(e));
+        const MoveCols M = move_cols(e, 0u, mode, false);
+        uint32_t* const d_list = e->d_wt_out;
+        MMTRY(requeue_selected(e, k, M, marked_on_device, [&]() {
+            hipLaunchKernelGGL(k_rotate_scatter, dim3(1), dim3(WT_THREADS), 0, e->stream, R, e->clock_now, d_list, d_list + cap,
+                               d_list + 2u * (size_t)cap, M);
+        }, &refused));
+        if (refused != 0u) return MM_ERR_INTERNAL;            // nobody can be refused: the mode seats them already
+        if (n_selected) *n_selected = k;
+        return MM_OK;
+    });
 }
 
 extern "C" int mm_wait_stats(mm_engine* e, uint32_t mode, mm_wait_group* per_group)

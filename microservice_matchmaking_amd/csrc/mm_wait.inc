@@ -272,17 +272,6 @@ __global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P)
 // (mm_move), or for the host to hand to another engine's mm_enqueue_stamped (mm_move_out reads rating, word and stamp back).
 __global__ __launch_bounds__(WT_THREADS) void k_move_scatter(WaitParams P, MoveCols M) { wait_scatter_body<true>(P, M); }
 
-// After the bucketing of a move: an accepted row's new slot carries the stamp of the slot the player left
-// (k_bucket_scatter stamped it with the clock, as for any enqueue; new_slot is its out_slot column, MM_NO_SLOT = refused).
-__global__ __launch_bounds__(WT_THREADS) void k_move_stamp(uint32_t n, uint32_t capacity, const uint32_t* __restrict__ new_slot,
-                                                           const uint32_t* __restrict__ old_stamp, uint32_t* __restrict__ stamp)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t s = new_slot[i];
-    if (s < capacity) stamp[s] = old_stamp[i];
-}
-
 // mm_rotate (include/mm_wait.h): the LIVE seats of the stored lobbies of one mode leave and rejoin their own queue's
 // tail.  No queue is streamed: a chain is selected by its LobbyDev record, state[] of its seats and ChainDev.len alone, so
 // both kernels are ONE workgroup — a wave per rating group (groups wave, wave + WT_WAVES, ...), a lane per seat in

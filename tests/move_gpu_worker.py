@@ -46,6 +46,7 @@ CASES = {
     "tier_chain": lambda: print("tiers: %d -> %d" % tier_chain(Engine, OracleEngine)),
     "roles_cleared": lambda: role_cases(Engine, OracleEngine, clear=True),
     "roles_refused": lambda: print("refused %d" % role_cases(Engine, OracleEngine, clear=False)),
+    "roles_refused_wrapped": lambda: print("refused %d" % role_cases(Engine, OracleEngine, clear=False, wrap=True)),
     "full_pool": lambda: full_case(Engine, OracleEngine),
 }
 

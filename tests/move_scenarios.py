@@ -18,7 +18,7 @@ from geometry import _value, source_defines
 from helpers import assert_same_state
 from microservice_matchmaking_amd._abi import NO_SLOT, MMError, cons_make
 from microservice_matchmaking_amd.config import make_config, mode_1v1, mode_team
-from wait_scenarios import U32, Tracker, assert_wait_stats, expire_both, random_batch, tick_both
+from wait_scenarios import U32, Tracker, assert_wait_stats, chunk_length, expire_both, random_batch, tick_both
 
 ROLE_MASK = 0xF << 16                                     # MM_CONS_ROLE's field
 USER_MASK = 0x000FFFFF                                    # MM_CONS_USER_MASK
@@ -329,14 +329,34 @@ def tier_chain(engine_cls, oracle_cls, n=900, capacity=8192):
         return s01[0].size, s12[0].size
 
 
-def role_cases(engine_cls, oracle_cls, clear, n=1200, capacity=8192):
+def role_cases(engine_cls, oracle_cls, clear, n=1200, capacity=8192, wrap=False):
     """From the five-role 5v5 into the one-role 5v5.  clear=True: cons_clear takes the role field away and everybody is
     accepted with role 0.  clear=False: roles >= 1 are refused — expired only, NO_SLOT in the new column, their ring positions
-    used up — and the enqueue that follows still gets the oracle's slots."""
+    used up — and the enqueue that follows still gets the oracle's slots.
+    wrap=True: the three things at which a carried stamp can end up in the wrong slot or come from the wrong row, in ONE move —
+    WT_CHUNK + 1 players of one rating group are selected (the selection crosses a chunk of the walk and a block of the
+    bucketing), the pool ends 100 slots short of the ring range they need, so the range wraps onto the slots they still hold
+    themselves and the host hands the device a slot list that steps over them, and most rows are refused.  The players arrive
+    in batches of 97 under a clock that advances with every batch, so neighbouring rows of the list carry different stamps,
+    and no slot they can move into holds one of those values beforehand: the first mm_clock_set wrote 5 everywhere, the
+    destination's players were stamped 40, the move runs at 60.  Each accepted row's age is read back through mm_locate and
+    compared with ITS row of the list; tick_all reads the same stamps through mm_wait_stats and mm_matches_wait."""
+    if wrap:
+        n = chunk_length() + 1
+        capacity = 2 * n + 203 - 100
     cfg = four_mode_config(capacity)
     with Duo(engine_cls, oracle_cls, cfg) as d:
-        d.clock(10)
-        d.enqueue(*pool(n, 311, 2, 5))
+        if wrap:
+            d.clock(5)
+            rating, cons = pool(n, 311, 2, 5, lo=0, hi=1499)
+            for b, i in enumerate(range(0, n, 97)):
+                d.clock(10 + b)
+                d.enqueue(rating[i:i + 97], cons[i:i + 97])
+            assert 10 + b < 40
+            d.clock(40)
+        else:
+            d.clock(10)
+            d.enqueue(*pool(n, 311, 2, 5))
         d.enqueue(*pool(203, 312, 3, 1))
         d.tick(3, "the destination holds queues and stored lobbies")
         assert sum(d.a.lobby_state(3, g)[0].size for g in range(7)) > 0 and int(d.a.queue_depth(3).sum()) > 0
@@ -346,6 +366,17 @@ def role_cases(engine_cls, oracle_cls, clear, n=1200, capacity=8192):
         s, g, a, new = d.move(2, 3, 0, ROLE_MASK if clear else 0, "roles")
         assert s.size == left > 100
         role = (d.tr.cons[s] >> 16) & 0xF                      # (tr.cons of an old slot is still the word it came with)
+        if wrap:
+            ok = new != NO_SLOT
+            assert (g == 0).all() and n + 203 + n > capacity and 0 < int(ok.sum()) < n
+            assert new[ok].min() >= n and (new[ok] < n + 203).any() and (new[ok] >= n + 203).any()   # stepped over, wrapped
+            batch = np.arange(n) // 97                         # a never-ticked queue is in arrival order, and so is the list
+            assert np.array_equal(a, 50 - batch) and not np.isin(a, (0, 20, 55)).any()   # no row's age is one a stale slot gives
+            assert np.unique(a[ok]).size == np.unique(a).size > 20
+            where, grp, _, _, age = d.a.locate(3, new[ok])
+            assert (where == 1).all() and (grp == 0).all()     # MM_AT_QUEUE
+            assert np.array_equal(age, a[ok]), (np.flatnonzero(age != a[ok])[:8], age[:8], a[ok][:8])
+            assert (d.a.locate(2, s)[0] == (1 | 4)).all()      # the old slots: QUEUE | MARKED
         if clear:
             assert (new != NO_SLOT).all() and d.a.last_move["refused"] == 0
             assert ((d.tr.cons[new] >> 16) & 0xF == 0).all() and ((d.tr.cons[new] & 0xF) == 3).all()
@@ -413,7 +444,6 @@ def selected_count_edges(engine_cls, oracle_cls, counts, capacity, lobby_case=Tr
     of group 1, then of group 2.  Source and destination are 1v1 with a window of 0 and the ratings of a group are all
     different (three groups wide enough for that), so a tick seats an anchor per group and matches nobody.  lobby_case:
     the first count once more with the source ticked first, so that every group's stored lobby holds a selected seat."""
-    from wait_scenarios import chunk_length
     per = 2 * chunk_length() + 1
     cfg = make_config([mode_1v1(window=0), mode_1v1(window=0)], capacity=capacity, groups=WIDE_GROUPS)
     assert capacity >= 3 * per + max(counts) + 64

@@ -1,7 +1,8 @@
 """Every device and pinned buffer the engine allocates is freed again, on the good path and on every path that runs out
 of memory half way.  Runs on the CPU shim, whose hipMalloc / hipHostMalloc count the blocks they have handed out
 (emu_live_blocks) and fail on request (emu_fail_alloc_in: a host-heap failure of the shim — nothing of the kind exists
-for the device)."""
+for the device).  The same injection drives the one failure rule of the marking calls (mm_move, mm_move_out, mm_rotate):
+out of memory before the first mark leaves the engine as it was, behind it the engine is poisoned."""
 import ctypes as C
 import gc
 
@@ -109,3 +110,117 @@ def test_clock_that_runs_out_of_memory_can_be_set_again(shim):
         shim.emu_fail_alloc_in(0)
     e.close()
     assert shim.emu_live_blocks() == base
+
+
+# ---- the marking calls (include/mm_wait.h): a failure before the first mark leaves the engine usable, one after it poisons ----
+
+MM_ERR_STATE = -9
+MM_ERR_RANGE = -8
+WAITING = 2100                                         # three batches of 700: none reaches BK_CHUNK, together they pass it
+
+
+def waiting_engine(ticked=False):
+    """Two 1v1 modes, capacity 8192, the clock at 10, 2100 players of distinct ratings in mode 0 (a window of 0: a tick
+    matches nobody and leaves an anchor seated per rating group), then the clock at 100."""
+    e = EmuEngineSmall(make_config([mode_1v1(window=0), mode_1v1()], capacity=8192))
+    e.clock_set(10)
+    for b in range(3):
+        e.enqueue(((np.arange(700) + 700 * b) * 2).astype(np.int32), cons_make(np.zeros(700)))
+    if ticked:
+        assert len(e.tick(0)) == 0
+    e.clock_set(100)
+    return e
+
+
+def failing(shim, e, k, name, *args):
+    """The call with the k-th allocation from now failing -> (status, its out-counters)."""
+    out = [C.c_uint32(77) for _ in range(2 if name == "move" else 1)]
+    shim.emu_fail_alloc_in(k)
+    try:
+        rc = e._fn(name)(e._h, *args, *[C.byref(c) for c in out])
+    finally:
+        shim.emu_fail_alloc_in(0)
+    return rc, [int(c.value) for c in out]
+
+
+def poisoned(e):
+    return e._fn("expired")(e._h, 0, 0, None, None, None) == MM_ERR_STATE
+
+
+def assert_untouched(e, blob, tag):
+    """Not poisoned, the lists empty, the pool byte for byte what it was."""
+    assert e._fn("expired")(e._h, 0, 0, None, None, None) == 0 and e._fn("moved")(e._h, 0, 0, None) == 0, tag
+    assert e._fn("expired")(e._h, 0, 1, None, None, None) == MM_ERR_RANGE, tag
+    assert e._fn("moved")(e._h, 0, 1, None) == MM_ERR_RANGE and e._fn("moved_rows")(e._h, 0, 1, None, None, None) == MM_ERR_RANGE, tag
+    assert e.snapshot() == blob, tag
+
+
+def test_move_that_runs_out_of_memory_poisons_only_once_a_mark_may_be_on_the_device(shim):
+    """mm_move(0, 1, 5) with the k-th allocation failing, k counted up to the first k the call survives.  The allocations
+    before k_move_scatter is queued (move_alloc's blocks) fail with MM_ERR_OOM and an engine as it was; the one behind it
+    (the bucket histogram growing for 2100 rows) fails with MM_ERR_OOM and a poisoned engine: exactly one such k, and every
+    smaller k is of the first kind."""
+    base = shim.emu_live_blocks()
+    kinds = []
+    for k in range(1, 16):
+        e = waiting_engine()
+        blob = e.snapshot()
+        rc, counters = failing(shim, e, k, "move", 0, 1, 5, 0)
+        if rc == 0:
+            assert counters == [WAITING, 0], k
+            kinds.append("ok")
+        else:
+            assert rc == MM_ERR_OOM and counters == [0, 0], (k, rc, counters)
+            kinds.append("poisoned" if poisoned(e) else "usable")
+        if kinds[-1] == "usable":
+            assert_untouched(e, blob, k)
+            s = e.move(0, 1, 5)                            # the retry
+            assert s[0].size == WAITING and e.last_move == {"selected": WAITING, "refused": 0}, k
+            assert (e.enqueue(np.zeros(3, np.int32), cons_make(np.zeros(3))) != 0xFFFFFFFF).all(), k
+        elif kinds[-1] == "poisoned":
+            one = np.zeros(1, np.uint32)
+            assert e._fn("enqueue")(e._h, 1, one.ctypes.data_as(C.c_void_p), one.ctypes.data_as(C.c_void_p), None, None, None) == MM_ERR_STATE
+            assert e._fn("expire")(e._h, 0, 5, None) == MM_ERR_STATE
+            assert e._fn("expired")(e._h, 0, 0, None, None, None) == MM_ERR_STATE
+            assert e._fn("moved")(e._h, 0, 0, None) == MM_ERR_STATE
+            assert e._fn("locate")(e._h, 0, 1, one.ctypes.data_as(C.c_void_p), None, None, None, None, None) == MM_ERR_STATE
+            e.reset()
+            e.enqueue((np.arange(400) // 2).astype(np.int32), cons_make(np.ones(400)))
+            assert len(e.tick(1)) > 0
+        e.close()
+        assert shim.emu_live_blocks() == base, k
+        if kinds[-1] == "ok":
+            break
+    print("mm_move, allocation k = 1..%d: %s" % (len(kinds), kinds))
+    n_usable = kinds.index("poisoned")
+    assert n_usable >= 1 and kinds == ["usable"] * n_usable + ["poisoned", "ok"], kinds
+
+
+@pytest.mark.parametrize("name", ["move_out", "rotate"])
+def test_move_out_and_rotate_that_run_out_of_memory_stay_usable(shim, name):
+    """The same drive through the one failure of mm_move_out and mm_rotate that can be reached: move_alloc, which comes
+    before any mark.  mm_move_out allocates nothing after its mark, and a rotation selects at most n_groups x 32 players,
+    never more than one BK_CHUNK, so the bucket histogram does not grow behind k_rotate_scatter: for both only "MM_ERR_OOM,
+    engine usable, lists empty, the retry succeeds" can be asserted, for every k up to the blocks a first call allocates."""
+    args = (0, 1, 5, 0) if name == "move_out" else (0, 32, 1)
+    base = shim.emu_live_blocks()
+    with waiting_engine(ticked=name == "rotate") as e:
+        before = shim.emu_live_blocks()
+        want = getattr(e, name)(*args)
+        n_alloc = shim.emu_live_blocks() - before
+    assert want[0].size > 0 and n_alloc >= 2
+    for k in range(1, n_alloc + 2):
+        e = waiting_engine(ticked=name == "rotate")
+        blob = e.snapshot()
+        rc, counters = failing(shim, e, k, name, *args)
+        if k <= n_alloc:
+            assert rc == MM_ERR_OOM and counters == [0], (k, rc, counters)
+            assert not poisoned(e), k
+            assert_untouched(e, blob, k)
+            got = getattr(e, name)(*args)
+            assert all(np.array_equal(x, y) for x, y in zip(got, want)), k
+            assert (e.enqueue(np.zeros(3, np.int32), cons_make(np.zeros(3))) != 0xFFFFFFFF).all(), k
+        else:
+            assert rc == 0 and counters == [want[0].size], (k, rc, counters)   # past the call's own allocations
+        e.close()
+        assert shim.emu_live_blocks() == base, k

@@ -12,7 +12,7 @@ WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "move_gpu_work
 
 # seconds: hang guards of the order tests/test_gpu_wait.py uses, not measurements (every scenario takes seconds)
 LIMITS = {"script_seed1": 240, "script_seed2_restart": 240, "selected_count_edges": 240, "tier_chain": 120,
-          "roles_cleared": 120, "roles_refused": 120, "full_pool": 120}
+          "roles_cleared": 120, "roles_refused": 120, "roles_refused_wrapped": 120, "full_pool": 120}
 
 
 # After a scenario that hung (time limit) or died of a signal (abort, segmentation fault: what a GPU fault looks like from

@@ -136,6 +136,11 @@ def test_role_field_kept_roles_the_fallback_lacks_are_refused(oracle_cls, engine
     assert role_cases(engine_cls, oracle_cls, clear=False) > 0
 
 
+@pytest.mark.parametrize("engine_cls", ENGINES, **ids)
+def test_stamps_through_a_wrapped_slot_list_with_refused_rows_across_a_chunk(oracle_cls, engine_cls):
+    assert role_cases(engine_cls, oracle_cls, clear=False, wrap=True) > chunk_length() // 2
+
+
 def _ring(engine_cls, oracle_cls, in_the_way):
     """capacity 1024, next_slot at 900, 300 players move.  in_the_way False: slots 0..599 are free again, the new slots are
     900..1023, 0..175 — the plain range, wrapped.  True: the 600 waiting players hold 0..599 themselves, the free slots are
