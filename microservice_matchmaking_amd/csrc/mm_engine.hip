@@ -996,6 +996,12 @@ static __device__ __forceinline__ bool team_chain_is_fast(const struct TeamChain
 // host side: the C ABI
 // ------------------------------------------------------------------------------------
 
+struct KpRoundsState {         // all that pair_plan keeps from one tick to the next
+    bool kp_rounds_off;        // a chain found itself on two XCDs (PF_XCD): never several passes per launch again on this engine
+    uint32_t pair_pcool;       // batches for which kp_rounds stays off after a launch that gave up (a time-out: somebody else holds the CUs)
+    uint32_t pair_pstops;      // launches that gave up so far (diagnostics)
+};
+
 struct MemBlock { void* p; bool pinned; };   // a buffer the engine owns: hipMalloc'ed, or hipHostMalloc'ed (pinned)
 
 // The lists the last mm_expire, mm_move, mm_move_out or mm_rotate left on the host (include/mm_wait.h), row i of every
@@ -1057,10 +1063,7 @@ struct mm_engine {
     uint16_t* d_pk_exa[2];
     uint32_t* d_pk_bitsp[2];
     uint32_t* d_pk_headp[2];
-    // run-time state of kp_rounds (the knobs are in `tn`)
-    bool kp_rounds_off;        // a chain found itself on two XCDs (PF_XCD): never several passes per launch again on this engine
-    uint32_t pair_pcool;       // batches for which kp_rounds stays off after a launch that gave up (a time-out: somebody else holds the CUs)
-    uint32_t pair_pstops;      // launches that gave up so far (diagnostics)
+    KpRoundsState kpr;         // run-time state of kp_rounds (the knobs are in `tn`)
     unsigned long long* d_pk_pbar;   // [group] arrival words, then [group] XCD masks (one allocation)
     uint32_t round_ctr;
     uint32_t* d_pk_tilectl;
@@ -2066,6 +2069,14 @@ static int results_send(mm_engine* e, const uint32_t* n_out, uint32_t L, uint32_
     return MM_OK;
 }
 
+// Host work while the device runs a batch: what the last look's copies brought (slots released), then the lobbies of
+// this look behind them (n_out; nullptr: none yet) if they are worth a batch of copies (`min_new`, with results_early).
+static int results_ship(mm_engine* e, const uint32_t* n_out, uint32_t L, uint32_t min_new)
+{
+    MMTRY(results_absorb(e, L));
+    return n_out ? results_send(e, n_out, L, e->tn.results_early ? min_new : 0xFFFFFFFFu) : MM_OK;
+}
+
 // A look at device records through the pinned buffer (k_look): look_launch enqueues the hand-over behind whatever the
 // stream holds, look_wait returns when the records of THAT look are in `dst_host`.  The poll is bounded by the stream
 // itself: a stream that has finished (or failed) without the sequence number having arrived ends it.
@@ -2106,7 +2117,7 @@ static int look_wait(mm_engine* e)
 }
 
 // Several passes per launch (kp_rounds)?  The knob, until a PF_XCD stop switches it off for the rest of the engine's life.
-static bool kp_rounds_on(const mm_engine* e) { return e->tn.pair_persist != 0u && !e->kp_rounds_off; }
+static bool kp_rounds_on(const mm_tuning& tn, const KpRoundsState& K) { return tn.pair_persist != 0u && !K.kp_rounds_off; }
 
 // kp_round's workgroup map of a batch (PairParams.xseg): the tiles of a chain on as few XCDs as its tile count allows.
 // Up to eight chains: an XCD each, the XCDs that are left go one by one to the chain with the most tiles per XCD;
@@ -2169,331 +2180,305 @@ template <class Params>
 static void walk_params_common(Params& P, const mm_engine* e, uint32_t mode, bool purge)
 {
     memset(&P, 0, sizeof(P));
-    P.mode = mode;
-    P.n_groups = e->cfg.n_groups;
-    P.capacity = e->cfg.capacity;
-    P.purge = purge ? 1u : 0u;
-    P.out_slot_stride = e->out_slot_stride;
-    P.out_rec_stride = e->out_rec_stride;
+    P.mode = mode; P.n_groups = e->cfg.n_groups; P.capacity = e->cfg.capacity; P.purge = purge ? 1u : 0u;
+    P.out_slot_stride = e->out_slot_stride; P.out_rec_stride = e->out_rec_stride;
     P.chains = e->d_chains;
-    P.q_rating = e->d_q_rating;
-    P.q_cons = e->d_q_cons;
-    P.q_slot = e->d_q_slot;
-    P.state = e->d_state;
-    P.released = e->d_released;
-    P.n_released = e->d_counters;
-    P.out_slots = e->d_out_slots;
-    P.out_score = e->d_out_score;
-    P.out_pass = e->d_out_pass;
+    P.q_rating = e->d_q_rating; P.q_cons = e->d_q_cons; P.q_slot = e->d_q_slot;
+    P.state = e->d_state; P.released = e->d_released; P.n_released = e->d_counters;
+    P.out_slots = e->d_out_slots; P.out_score = e->d_out_score; P.out_pass = e->d_out_pass;
+}
+
+// PairParams of a tick: the engine's buffers and the knobs (mm_tuning -> PairParams).  bm / bbuf / pyq / grp and the
+// workgroup map are pair_plan's, batch by batch.
+static void pair_params(PairParams& P, const mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
+{
+    walk_params_common(P, e, mode, purge);
+    P.tune = e->tn.pair_tune; P.pinject = e->tn.pair_pinject;
+    // the first barrier of a launch is where a workgroup that found no CU is waited for (another engine's launch in the
+    // way ends within a millisecond or two); behind it everybody is on the chip and only slow, never absent
+    // — 5 ms, half a tick period of the stream (20 ms until round 5: two whole periods of spinning whenever somebody
+    // else held the CUs, and kp_round is a cheap way on); 40 x that behind it (200 ms), as before.  In 100 MHz ticks.
+    P.ptimeout0 = e->tn.pair_ptimeout_us * 100u; P.ptimeout1 = P.ptimeout0 * 40u;
+    P.window = M.window > 0xFFFFFu ? 0xFFFFFu : M.window; P.eqmask = M.eqmask;   // rating span of a fast chain < 2^20
+    P.bits_stride = e->pk_bits_stride; P.pstride = e->pk_stride; P.max_tiles = e->pk_max_tiles; P.gstride = e->pk_gstride;
+    P.pchains = e->d_pchains;
+    for (int b = 0; b < 2; ++b) {
+        P.key[b] = e->d_pk_key[b]; P.oidx[b] = e->d_pk_oidx[b];
+        P.nx16[b] = e->d_pk_nx16[b]; P.bits[b] = e->d_pk_bits[b];
+        P.exa[b] = e->d_pk_exa[b]; P.bitsp[b] = e->d_pk_bitsp[b]; P.headp[b] = e->d_pk_headp[b];
+    }
+    P.scratch = e->d_pk_scratch; P.wpre = e->d_pk_wpre; P.g16 = e->d_pk_g16;
+    P.rec2[0] = e->d_pk_scratch; P.rec2[1] = e->d_pk_rec1;
+    P.tilectl = e->d_pk_tilectl; P.grec = e->d_pk_grec;
+    P.pbar = e->d_pk_pbar;
+    P.pxmask = (uint32_t*)(e->d_pk_pbar + MM_MAX_GROUPS);
+    P.pyield = (uint32_t*)(e->d_pk_pbar + MM_MAX_GROUPS) + MM_MAX_GROUPS;
+}
+
+// The opening launches of the pair path: the chains' records, the packed keys, next[] for everybody.
+static int pair_open(mm_engine* e, const PairParams& P, uint32_t bound)
+{
+    const uint32_t G = e->cfg.n_groups;
+    if (e->tn.pair_tune & 0x10000u) HIPCHK(e, hipMemsetAsync(e->d_pk_grec, 0, (size_t)G * e->pk_gstride * sizeof(uint4), e->stream));   // (diagnostics)
+    hipLaunchKernelGGL(kp_init, dim3(G), dim3(1024), 0, e->stream, P, e->cfg.capacity);
+    hipLaunchKernelGGL(kp_pack, dim3((bound + 32u + 1023u) / 1024u, G), dim3(1024), 0, e->stream, P);
+    // A workgroup walks its anchors eight at a time (one wave each).  256 anchors per workgroup (round 5; 2048 until then,
+    // "to keep a big pool's staging traffic low"): the kernel is bound by instruction issue, the anchors of the wide rating
+    // groups cost 2-3x those of the narrow ones, and 147 + 98 heavy workgroups of 2048 anchors landed four to a CU —
+    // 299 us for the 1M pool against 148 us with 256 anchors a workgroup (157 / 173 us with 512 / 1024;
+    // profiles/r05_ab_nx_seg.txt).  The staged window (NXI_STAGE entries from L2) is read 8192 / 256 times per entry: 130 MB.
+    // (a 10M pool keeps its 2048: the grid is sized by the POOL for every rating group — the host does not know the chains'
+    // lengths yet — and a quarter of a million workgroups that only find out they have nothing to do are not free)
+    uint32_t seg = 256u, stage = NXI_STAGE;
+    while (seg < NXI_SEG && (unsigned long long)bound > 8192ull * seg) seg <<= 1;
+    if (e->tn.pair_nxseg) seg = e->tn.pair_nxseg;               // MM_PAIR_NXSEG / MM_PAIR_NXSTAGE (experiments)
+    if (e->tn.pair_nxstage) stage = e->tn.pair_nxstage;
+    if (stage < seg + 64u) stage = seg + 64u;
+    if (stage > NXI_STAGE) stage = NXI_STAGE;
+    const bool timing = (e->cfg.flags & MM_CFG_TIMING) != 0;
+    if (timing) HIPCHK(e, hipEventRecord(e->ev_nx[0], e->stream));
+    hipLaunchKernelGGL(kp_nx_init, dim3((bound + seg - 1u) / seg + 1u, G), dim3(NXI_THREADS), 0, e->stream, P, seg, stage);
+    if (timing) { HIPCHK(e, hipEventRecord(e->ev_nx[1], e->stream)); e->ev_nx_set = true; }
+    HIPCHK(e, hipGetLastError());
+    return MM_OK;
+}
+
+// ---- the tiled rounds' batch logic: a plan per look at the chains (pair_plan: no HIP, no engine), then its launches ----
+enum PairNext : uint32_t { PN_DONE, PN_COMPACT, PN_ROUNDS, PN_ROUND };   // the tiled stage is over | compact only | a kp_rounds batch | a kp_round batch
+struct PairLoop {                              // a tick's state from look to look
+    bool first = true;                         // no look yet
+    bool after_persist = false;                // the look directly behind a kp_rounds launch: only there is PairChain.pfail news
+    uint32_t last_tp = 0;                      // the tile length of the tick's last batch (it never grows: pair_plan)
+    uint32_t idle_looks = 0;                   // looks in a row at which no tiled chain had retired a pass or left the tiled stage
+    unsigned long long last_progress = ~0ull;
+};
+struct PairPlan {
+    PairNext next;
+    uint32_t ask;                              // PN_COMPACT: the kp_ask_compact mask that goes first (0: the chains asked themselves)
+    uint32_t tp, tiles;                        // the batch's tile length, the longest chain's tiles
+    uint32_t slots;                            // the batch's grid: 8 x slots workgroups by the map in PairParams.xseg (0: the plain (tiles, G) grid)
+    uint32_t passes;                           // PN_ROUND: kp_round launches behind the one that only prepares
+    bool ship;                                 // sent_no leaves for the host behind the launches (PN_DONE: behind kp_late's)
+    uint32_t sent_no[MM_MAX_GROUPS];           // the lobbies every chain had emitted at this look
+};
+
+// What the tiled stage does behind this look at the chains' records `pcs`.  Fills the batch's part of PairParams in place
+// (bm, bbuf, pyq, grp, the workgroup map).  MM_ERR_INTERNAL: the watchdog.
+static int pair_plan(const PairChain* pcs, uint32_t G, const mm_tuning& tn, PairLoop& L, KpRoundsState& K, mm_path_stats& ps,
+                     PairParams& P, PairPlan& out)
+{
+    // A pass without a change ends a chain, so a tick is finite; a look + a batch retires at least one pass of every tiled
+    // chain, or is one of the few kinds that retire none and are each followed by one that does (a compaction-only look; a
+    // kp_rounds launch that stopped at its first barrier, after which kp_rounds stays off for 16 batches).  The watchdog
+    // counts the looks in a row at which nothing had moved: passes retired + chains still tiled + compactions done.
+    // counted in looks that bound was 3 x capacity round trips (tens of minutes at 2^24 before MM_ERR_INTERNAL,
+    // and 3u * capacity wraps above 1.43e9).  Counted in PASSES it is tight.
+    unsigned long long progress = 0;
+    bool tiled = false, compact = false, want_fit = false;
+    uint32_t longest = 0, yield_q = 0, gl = 0;         // (gl: the longest chain, yield_q: the queue length at which it ends the batch)
+    const bool behind = L.after_persist, first = L.first;
+    L.after_persist = L.first = false;
+    for (uint32_t g = 0; g < G; ++g) {
+        const PairChain& pc = pcs[g];
+        P.bm[g] = 0; P.bbuf[g] = 0;
+        out.sent_no[g] = pc.fast ? pc.n_out : 0u;
+        if (!pc.fast) continue;
+        progress += (unsigned long long)pc.passes + ((unsigned long long)pc.m << 32) + (pc.stage == PS_TILED ? 1u : 0u) + pc.want_compact;
+        if (pc.ppass > ps.pair_rounds_passes) ps.pair_rounds_passes = pc.ppass;
+        if (pc.rounds > ps.pair_tiled_passes) ps.pair_tiled_passes = pc.rounds;
+        if (pc.stage != PS_TILED) continue;
+        // (pfail is written by kp_init and by kp_rounds' epilogue only and stays in the record: it is looked at once,
+        // at the look directly behind the launch that wrote it — a later look of the tick would count the same stop again
+        // and start the cool-down anew)
+        const uint32_t why = pc.pfail & 0xFFu;
+        if (behind && pc.pfail && why == PF_YIELD) ++ps.pair_yields;
+        else if (behind && pc.pfail) {
+            // the last kp_rounds launch gave up on this chain (its state is committed): one launch per pass for a while.
+            // A chain that found itself on two XCDs says the dispatch is not what the map assumes: never again.
+            ++K.pair_pstops; K.pair_pcool = 16u;
+            if (why == PF_XCD) { K.kp_rounds_off = true; ++ps.pair_stops_xcd; }
+            else if (why == PF_INJECT) ++ps.pair_stops_inject;
+            else ++ps.pair_stops_timeout;
+            ps.degraded = 1;
+            if (tn.debug) fprintf(stderr, "[mm-pair] g%u: kp_rounds stopped (reason %u, iteration %u)\n", g, why, pc.pfail >> 8);
+        }
+        P.bm[g] = pc.m; P.bbuf[g] = (uint8_t)pc.buf;   // constant until the next compaction, i.e. for the whole batch
+        tiled = true;
+        compact |= pc.want_compact != 0;
+        longest = pc.m > longest ? pc.m : longest;
+    }
+    L.idle_looks = progress == L.last_progress ? L.idle_looks + 1u : 0u;
+    L.last_progress = progress;
+    if (L.idle_looks > 64u) return MM_ERR_INTERNAL;
+    out.next = PN_DONE; out.ask = 0;
+    // the chains' LDS-resident ends (kp_late) run next: what the tiled rounds have emitted since the last look leaves meanwhile
+    out.ship = !first;
+    if (!tiled) return MM_OK;
+    const bool on = kp_rounds_on(tn, K), reach = (longest + PK_TMAX - 1u) / PK_TMAX <= tn.pair_ptiles;
+    // kp_rounds wants a chain within `pair_ptiles` tiles, and a pass costs in proportion to the tile length: a chain whose
+    // QUEUED players would fit the tiles of a shorter length (or kp_rounds at all) while its index space does not is
+    // compacted now rather than at 75 % alive.  Only the longest chain decides the tile length.
+    for (uint32_t g = 1; g < G; ++g)
+        if (P.bm[g] > P.bm[gl]) gl = g;
+    if (on && !K.pair_pcool && !compact && !tn.pair_tile_fixed && P.bm[gl]) {
+        const PairChain& pc = pcs[gl];
+        // the capacity the chain's index space has to get under for the next shorter tile length (or for kp_rounds)
+        uint32_t capq = tn.pair_ptiles * PK_TMAX;
+        for (uint32_t tlen = PK_TMAX; tlen >= PK_TMAX / 4u && pc.m <= tn.pair_ptiles * tlen; tlen >>= 1) capq = tn.pair_ptiles * (tlen >> 1);
+        if (pc.m <= tn.pair_ptiles * (PK_TMAX / 4u)) capq = PL_MAX - 1u;          // shortest tiles already: next is kp_late
+        if (pc.qlen <= capq && pc.m > capq && capq >= PL_MAX) { out.ask = 1u << gl; compact = true; }
+        else {
+            if (pc.m > tn.pair_ptiles * PK_TMAX) want_fit = true;          // not yet within kp_rounds' reach: a short batch
+            yield_q = capq;                                                // compact (and, in kp_rounds, end the batch) at this length
+        }
+    }
+    // several passes per launch (kp_rounds) when every chain's tiles fit the CUs of one XCD
+    bool persist = on && !compact && reach;
+    if (persist && K.pair_pcool) { --K.pair_pcool; persist = false; ps.degraded = 1; }
+    // (a batch that kp_rounds would have taken, walked launch by launch because it is off: a fall-back's timing)
+    if (!on && !compact && reach) ps.degraded = 1;
+    // tile length of this batch: the smallest that keeps the longest chain within the cap (the walk costs one dependent
+    // load per tile, everything else is proportional to the tile).
+    // ONE cap for the tile count whether this batch is kp_rounds' or kp_round's (round 5): the tile length of a tick must
+    // never GROW.  An entry next[i] = NX_FAR says "nobody fits inside the horizon", and the horizon is two tiles of the
+    // length it was computed at; the walk resolves it by scanning from the end of the CURRENT horizon — right for an
+    // equal or shorter tile length (it scans a superset), wrong for a longer one (the stretch between the two horizons
+    // is never looked at: a later partner, or none).  Until round 5 a kp_round batch was sized for 40 tiles and a
+    // kp_rounds batch for 32: a chain of 33-40 tiles of length T walked launch by launch — the cool-down after a stop of
+    // kp_rounds, or while ANOTHER chain was still too long for kp_rounds — came back to kp_rounds at 2 T.  Found by
+    // tests/stress.py with MM_PAIR_PTILES=5 (seed 130203984: 46 lobbies of one chain missing), on the device and on
+    // the shim; it needs a stop of kp_rounds (or the knob) to happen, which is why no default run ever met it.
+    const uint32_t tiles_max = on && tn.pair_ptiles < tn.pair_tiles_max ? tn.pair_ptiles : tn.pair_tiles_max;
+    uint32_t tp = PK_TMAX;
+    if (!tn.pair_tile_fixed)
+        for (uint32_t cand = PK_TMAX / 4u; cand < PK_TMAX; cand <<= 1)    // (an eighth was measured: slower, the fixed cost of a round takes over)
+            if ((longest + cand - 1u) / cand <= tiles_max) { tp = cand; break; }
+    if (L.last_tp && tp > L.last_tp && !compact) {
+        // (the cap changed in mid-tick — kp_rounds turned off for good by a PF_XCD stop — or a knob: every tiled chain is
+        // compacted first, which turns its NX_FAR entries into "not computed")
+        out.ask = 0xFFFFFFFFu; compact = true; L.last_tp = 0;
+    }
+    const uint32_t tiles = (longest + tp - 1u) / tp;
+    out.tp = tp; out.tiles = tiles; out.ship = !compact;
+    if (compact) { out.next = PN_COMPACT; return MM_OK; }   // look at the new lengths before the next batch
+    L.last_tp = tp;
+    for (uint32_t g = 0; g < G; ++g) P.pyq[g] = g == gl ? yield_q : 0u;
+    // chains of many tiles: a second level of the route, rebuilt behind every round (kp_group)
+    P.grp = (tn.pair_group_min && tiles >= tn.pair_group_min && tp == PK_TMAX) ? PK_GS : 0u;
+    // the batch's workgroup map: a chain's tiles together on one XCD (mm_pair.inc, PairParams.xseg)
+    P.xslots = 0;
+    uint32_t tof[MM_MAX_GROUPS];
+    for (uint32_t g = 0; g < G; ++g) tof[g] = P.bm[g] ? (P.bm[g] + tp - 1u) / tp : 0u;
+    if (persist) {
+        // every chain's workgroups on ONE XCD, a CU each: they talk through that XCD's L2 and must all be on the chip
+        out.slots = pair_xcd_map(P, tof, G, true);
+        if (out.slots) {
+            P.grp = 0; L.after_persist = true; out.next = PN_ROUNDS;
+            return MM_OK;
+        }
+        P.xslots = 0;
+    }
+    out.slots = tn.pair_xcd ? pair_xcd_map(P, tof, G) : 0u;
+    out.passes = want_fit && tn.pair_batch > 12u ? 12u : tn.pair_batch;
+    out.next = PN_ROUND;
+    return MM_OK;
+}
+
+// The enqueues of a plan, with the kernels compiled for its tile length.
+template <uint32_t TP>
+static void pair_launch_tp(mm_engine* e, const PairParams& P, const PairPlan& pl, uint32_t G)
+{
+    if (pl.next == PN_ROUNDS) {
+        // (the arrival words are zero: kp_init at the start of the tick, kc_commit behind every batch)
+        // (the batch ends by itself when the longest chain can be compacted into shorter tiles: it may be long)
+        const uint32_t K = e->tn.pair_pbatch, slice = MM_PERSIST_SLICE ? MM_PERSIST_SLICE : K + 1u;
+        for (uint32_t it = 0; it <= K; it += slice)
+            hipLaunchKernelGGL(kp_rounds<TP>, dim3(8u * pl.slots), dim3(PT_THREADS), 0, e->stream, P, it, it + slice < K + 1u ? it + slice : K + 1u, K);
+        ++e->ps.pair_rounds_launches;
+    } else if (pl.next == PN_ROUND) {
+        // one launch per pass; the first of a batch only prepares, the commit brings the latest parity back into the
+        // chains' committed state
+        const dim3 rgrid = pl.slots ? dim3(8u * pl.slots) : dim3(pl.tiles, G);
+        const uint32_t ngr = P.grp ? (pl.tiles + P.grp - 1u) / P.grp : 0u;
+        uint32_t r = e->round_ctr;
+        for (uint32_t b = 0; b <= pl.passes; ++b) {
+            hipLaunchKernelGGL(kp_round<TP>, rgrid, dim3(PT_THREADS), 0, e->stream, P, r, b ? 0u : 1u);
+            ++r;
+            if (P.grp) hipLaunchKernelGGL(kp_group<TP>, dim3(ngr, G), dim3(1024), 0, e->stream, P, r);
+        }
+        e->ps.pair_round_launches += pl.passes;
+        hipLaunchKernelGGL(kp_round_commit<TP>, dim3(pl.tiles, G), dim3(256), 0, e->stream, P, r);
+        hipLaunchKernelGGL(kp_round_stage, dim3(G), dim3(64), 0, e->stream, P, r);
+        e->round_ctr = r;
+    } else if (pl.ask)
+        hipLaunchKernelGGL(kp_ask_compact, dim3(G), dim3(64), 0, e->stream, P, pl.ask);
+    // the four compaction kernels look at PairChain.want_compact themselves (a chain that does not want one costs them a few
+    // microseconds): they are enqueued behind EVERY batch, so a chain that ends its batch for a compaction — the 75 % rule,
+    // the yield, the fit — is compacted before the host looks again, one look per batch instead of two
+    hipLaunchKernelGGL(kc_words<TP>, dim3(pl.tiles, G), dim3(256), 0, e->stream, P);
+    hipLaunchKernelGGL(kc_plan<TP>, dim3(G), dim3(1024), 0, e->stream, P);
+    hipLaunchKernelGGL(kc_scatter<TP>, dim3(pl.tiles, G), dim3(1024), 0, e->stream, P);
+    hipLaunchKernelGGL(kc_commit<TP>, dim3(G), dim3(1024), 0, e->stream, P);
+}
+
+// ... one dispatch over the three tile lengths
+static int pair_launch(mm_engine* e, const PairParams& P, const PairPlan& pl, uint32_t G)
+{
+    if (pl.tp == PK_TMAX) pair_launch_tp<PK_TMAX>(e, P, pl, G);
+    else if (pl.tp == PK_TMAX / 2u) pair_launch_tp<PK_TMAX / 2u>(e, P, pl, G);
+    else pair_launch_tp<PK_TMAX / 4u>(e, P, pl, G);
+    HIPCHK(e, hipGetLastError());
+    return MM_OK;
+}
+
+static void report_pair_look(const mm_engine* e, uint32_t guard, uint32_t last_tp);
+// A look at the chains' records (h_pchains), and what the engine keeps of every look.
+static int pair_look(mm_engine* e, uint32_t G, uint32_t L, uint32_t guard, uint32_t last_tp)
+{
+    MMTRY(look_launch(e, e->d_pchains, e->h_pchains, G * sizeof(PairChain)));
+    MMTRY(look_wait(e));
+    ++e->ps.host_looks;
+    if (e->tn.debug && guard >= 200u && guard % 200u == 0u) report_pair_look(e, guard, last_tp);   // (a tick that looks at its chains hundreds of times)
+    uint32_t bf[MM_MAX_GROUPS];
+    for (uint32_t g = 0; g < G; ++g) {         // (what the tiled path had done when kp_late took over: the last look's is kept)
+        const PairChain& pc = e->h_pchains[g];
+        bf[g] = pc.before;
+        e->ps_hand[0][g] = pc.fast ? pc.passes : 0u; e->ps_hand[1][g] = pc.fast ? pc.n_out : 0u;
+        e->ps_hand[2][g] = pc.fast ? pc.ppass : 0u; e->ps_hand[3][g] = pc.fast ? pc.ptm[15] : 0u;
+    }
+    if (!e->r_based) results_set_bases(e, bf, L);   // (the first look sizes the groups' regions of the match list)
+    return MM_OK;
 }
 
 // The pair path (mm_pair.inc) for every chain of `mode` it is eligible for; the others are
 // left to k_walk (PairChain.fast == 0).  All launches are asynchronous on the engine stream.
 static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
 {
-    const mm_config& cfg = e->cfg;
-    const uint32_t G = cfg.n_groups;
+    const uint32_t G = e->cfg.n_groups;
     PairParams P;
-    walk_params_common(P, e, mode, purge);
-    // the knobs (mm_tuning -> PairParams)
-    P.tune = e->tn.pair_tune;
-    P.pinject = e->tn.pair_pinject;
-    // the first barrier of a launch is where a workgroup that found no CU is waited for (another engine's launch in the
-    // way ends within a millisecond or two); behind it everybody is on the chip and only slow, never absent
-    // — 5 ms, half a tick period of the stream (20 ms until round 5: two whole periods of spinning whenever somebody
-    // else held the CUs, and kp_round is a cheap way on); 40 x that behind it (200 ms), as before.  In 100 MHz ticks.
-    P.ptimeout0 = e->tn.pair_ptimeout_us * 100u;
-    P.ptimeout1 = P.ptimeout0 * 40u;
-    P.window = M.window > 0xFFFFFu ? 0xFFFFFu : M.window;   // rating span of a fast chain < 2^20
-    P.eqmask = M.eqmask;
-    P.bits_stride = e->pk_bits_stride;
-    P.pstride = e->pk_stride;
-    P.pchains = e->d_pchains;
-    for (int b = 0; b < 2; ++b) {
-        P.key[b] = e->d_pk_key[b]; P.oidx[b] = e->d_pk_oidx[b];
-        P.nx16[b] = e->d_pk_nx16[b]; P.bits[b] = e->d_pk_bits[b];
-    }
-    P.scratch = e->d_pk_scratch;
-    P.wpre = e->d_pk_wpre;
-    P.g16 = e->d_pk_g16;
-    P.rec2[0] = e->d_pk_scratch;
-    P.rec2[1] = e->d_pk_rec1;
-    for (int b = 0; b < 2; ++b) { P.exa[b] = e->d_pk_exa[b]; P.bitsp[b] = e->d_pk_bitsp[b]; P.headp[b] = e->d_pk_headp[b]; }
-    P.tilectl = e->d_pk_tilectl;
-    P.max_tiles = e->pk_max_tiles;
-    P.grec = e->d_pk_grec;
-    P.gstride = e->pk_gstride;
-    P.grp = 0;
-    P.pbar = e->d_pk_pbar;
-    P.pxmask = (uint32_t*)(e->d_pk_pbar + MM_MAX_GROUPS);
-    P.pyield = (uint32_t*)(e->d_pk_pbar + MM_MAX_GROUPS) + MM_MAX_GROUPS;
-    const unsigned long long bound64 = e->live_upper < cfg.capacity ? e->live_upper : cfg.capacity;
-    const uint32_t bound = (uint32_t)bound64;
-    if (e->tn.pair_tune & 0x10000u) HIPCHK(e, hipMemsetAsync(e->d_pk_grec, 0, (size_t)G * e->pk_gstride * sizeof(uint4), e->stream));   // (diagnostics)
-    hipLaunchKernelGGL(kp_init, dim3(G), dim3(1024), 0, e->stream, P, cfg.capacity);
-    hipLaunchKernelGGL(kp_pack, dim3((bound + 32u + 1023u) / 1024u, G), dim3(1024), 0, e->stream, P);
-    {
-        // A workgroup walks its anchors eight at a time (one wave each).  256 anchors per workgroup (round 5; 2048 until then,
-        // "to keep a big pool's staging traffic low"): the kernel is bound by instruction issue, the anchors of the wide rating
-        // groups cost 2-3x those of the narrow ones, and 147 + 98 heavy workgroups of 2048 anchors landed four to a CU —
-        // 299 us for the 1M pool against 148 us with 256 anchors a workgroup (157 / 173 us with 512 / 1024;
-        // profiles/r05_ab_nx_seg.txt).  The staged window (NXI_STAGE entries from L2) is read 8192 / 256 times per entry: 130 MB.
-        // (a 10M pool keeps its 2048: the grid is sized by the POOL for every rating group — the host does not know the chains'
-        // lengths yet — and a quarter of a million workgroups that only find out they have nothing to do are not free)
-        uint32_t seg = 256u, stage = NXI_STAGE;
-        while (seg < NXI_SEG && (unsigned long long)bound > 8192ull * seg) seg <<= 1;
-        if (e->tn.pair_nxseg) seg = e->tn.pair_nxseg;               // MM_PAIR_NXSEG / MM_PAIR_NXSTAGE (experiments)
-        if (e->tn.pair_nxstage) stage = e->tn.pair_nxstage;
-        if (stage < seg + 64u) stage = seg + 64u;
-        if (stage > NXI_STAGE) stage = NXI_STAGE;
-        const bool timing = (cfg.flags & MM_CFG_TIMING) != 0;
-        if (timing) HIPCHK(e, hipEventRecord(e->ev_nx[0], e->stream));
-        hipLaunchKernelGGL(kp_nx_init, dim3((bound + seg - 1u) / seg + 1u, G), dim3(NXI_THREADS), 0, e->stream, P, seg, stage);
-        if (timing) { HIPCHK(e, hipEventRecord(e->ev_nx[1], e->stream)); e->ev_nx_set = true; }
-    }
-    HIPCHK(e, hipGetLastError());
-    uint32_t tail_no[MM_MAX_GROUPS];
-    bool tail_send = false;
+    pair_params(P, e, mode, M, purge);
+    const uint32_t bound = (uint32_t)(e->live_upper < e->cfg.capacity ? e->live_upper : e->cfg.capacity);
+    MMTRY(pair_open(e, P, bound));
     memset(e->ps_hand, 0, sizeof(e->ps_hand));
+    PairPlan plan; plan.ship = false;
     // ---- tiled rounds for the chains that do not fit one workgroup's LDS ----
     if (bound >= PL_MAX) {
-        uint32_t tiles = (bound + PK_T - 1u) / PK_T + 1u;
-        if (tiles > e->pk_max_tiles) tiles = e->pk_max_tiles;
-        bool after_persist = false;            // the look directly behind a kp_rounds launch: only there is PairChain.pfail news
-        uint32_t last_tp = 0;                  // the tile length of the tick's last batch (it never grows: below)
-        uint32_t idle_looks = 0;               // looks in a row at which no tiled chain had retired a pass or left the tiled stage
-        unsigned long long last_progress = ~0ull;
+        const mm_tuning tn = e->tn;
+        PairLoop loop;
         for (uint32_t guard = 0;; ++guard) {
-            // A pass without a change ends a chain, so a tick is finite; an iteration (a look + a batch) retires at least one pass
-            // of every tiled chain, or is one of the few kinds that retire none and are each followed by one that does (a
-            // compaction-only look; a kp_rounds launch that stopped at its first barrier, after which kp_rounds stays off for
-            // 16 batches).  The watchdog counts the looks in a row at which nothing had moved.
-            // counted in looks that bound was 3 x capacity round trips (tens of minutes at 2^24 before MM_ERR_INTERNAL,
-            // and 3u * capacity wraps above 1.43e9).  Counted in PASSES it is tight: see idle_looks below.
-            if (idle_looks > 64u) return MM_ERR_INTERNAL;
-            MMTRY(look_launch(e, e->d_pchains, e->h_pchains, G * sizeof(PairChain)));
-            MMTRY(look_wait(e));
-            ++e->ps.host_looks;
-            if (e->tn.debug && guard >= 200u && guard % 200u == 0u) {           // (a tick that looks at its chains hundreds of times)
-                fprintf(stderr, "[mm-pair] look %u: cool-down %u, persist %d, last tile length %u;", guard, e->pair_pcool, (int)kp_rounds_on(e), last_tp);
-                for (uint32_t g = 0; g < G; ++g) {
-                    const PairChain& pc = e->h_pchains[g];
-                    if (pc.fast) fprintf(stderr, " g%u[stage %u m %u qlen %u passes %u compact %u pfail 0x%x]", g, pc.stage, pc.m, pc.qlen, pc.passes, pc.want_compact, pc.pfail);
-                }
-                fprintf(stderr, "\n");
-            }
-            {   // the watchdog: passes retired + chains still tiled + compactions done must move; the looks that move nothing (a
-                // compaction-only look, a kp_rounds launch that stopped at its first barrier) are each followed by one that does
-                unsigned long long progress = 0;
-                for (uint32_t g = 0; g < G; ++g) {
-                    const PairChain& pc = e->h_pchains[g];
-                    if (pc.fast) progress += (unsigned long long)pc.passes + ((unsigned long long)pc.m << 32) + (pc.stage == PS_TILED ? 1u : 0u) + pc.want_compact;
-                }
-                idle_looks = progress == last_progress ? idle_looks + 1u : 0u;
-                last_progress = progress;
-            }
-            bool tiled = false, compact = false;
-            uint32_t longest = 0;
-            for (uint32_t g = 0; g < G; ++g) {
-                const PairChain& pc = e->h_pchains[g];
-                P.bm[g] = 0;
-                P.bbuf[g] = 0;
-                if (!pc.fast || pc.stage != PS_TILED) continue;
-                // (pfail is written by kp_init and by kp_rounds' epilogue only and stays in the record: it is looked at once,
-                // at the look directly behind the launch that wrote it — a later look of the tick would count the same stop again
-                // and start the cool-down anew)
-                if (after_persist && pc.pfail && (pc.pfail & 0xFFu) == PF_YIELD) ++e->ps.pair_yields;
-                if (after_persist && pc.pfail && (pc.pfail & 0xFFu) != PF_YIELD) {
-                    // the last kp_rounds launch gave up on this chain (its state is committed): one launch per pass for a while.
-                    // A chain that found itself on two XCDs says the dispatch is not what the map assumes: never again.
-                    ++e->pair_pstops;
-                    e->pair_pcool = 16u;
-                    const uint32_t why = pc.pfail & 0xFFu;
-                    if (why == PF_XCD) { e->kp_rounds_off = true; ++e->ps.pair_stops_xcd; }
-                    else if (why == PF_INJECT) ++e->ps.pair_stops_inject;
-                    else ++e->ps.pair_stops_timeout;
-                    e->ps.degraded = 1;
-                    if (e->tn.debug) fprintf(stderr, "[mm-pair] g%u: kp_rounds stopped (reason %u, iteration %u)\n", g, pc.pfail & 0xFFu, pc.pfail >> 8);
-                }
-                P.bm[g] = pc.m;                       // constant until the next compaction, i.e. for the whole batch
-                P.bbuf[g] = (uint8_t)pc.buf;
-                tiled = true;
-                compact |= pc.want_compact != 0;
-                longest = pc.m > longest ? pc.m : longest;
-            }
-            // the lobbies emitted so far leave for the host while the next batch runs (the first look sizes the groups'
-            // regions); the copies are enqueued BEHIND the batch's launches: the device does not wait for the host's calls
-            uint32_t sent_no[MM_MAX_GROUPS];
-            {
-                uint32_t bf[MM_MAX_GROUPS];
-                for (uint32_t g = 0; g < G; ++g) { bf[g] = e->h_pchains[g].before; sent_no[g] = e->h_pchains[g].fast ? e->h_pchains[g].n_out : 0u; }
-                if (!e->r_based) results_set_bases(e, bf, M.L);
-            }
-            after_persist = false;
-            for (uint32_t g = 0; g < G; ++g) {
-                const PairChain& pc = e->h_pchains[g];
-                if (!pc.fast) continue;
-                if (pc.ppass > e->ps.pair_rounds_passes) e->ps.pair_rounds_passes = pc.ppass;
-                if (pc.rounds > e->ps.pair_tiled_passes) e->ps.pair_tiled_passes = pc.rounds;
-            }
-            for (uint32_t g = 0; g < G; ++g) {         // (what the tiled path had done when kp_late took over: the last look's is kept)
-                const PairChain& pc = e->h_pchains[g];
-                e->ps_hand[0][g] = pc.fast ? pc.passes : 0u;
-                e->ps_hand[1][g] = pc.fast ? pc.n_out : 0u;
-                e->ps_hand[2][g] = pc.fast ? pc.ppass : 0u;
-                e->ps_hand[3][g] = pc.fast ? pc.ptm[15] : 0u;
-            }
-            if (!tiled) {
-                // the chains' LDS-resident ends (kp_late) run next: what the tiled rounds have emitted since the last look leaves
-                // meanwhile — enqueued BEHIND kp_late's launch, below (the device never waits for the host's copy calls)
-                if (guard) { for (uint32_t g = 0; g < G; ++g) tail_no[g] = sent_no[g]; tail_send = true; }
-                break;
-            }
-            // kp_rounds wants a chain within `pair_ptiles` tiles, and a pass costs in proportion to the tile length: a chain whose
-            // QUEUED players would fit the tiles of a shorter length (or kp_rounds at all) while its index space does not is
-            // compacted now rather than at 75 % alive.  Only the longest chain decides the tile length.
-            bool want_fit = false;
-            uint32_t yield_q = 0, yield_g = 0;
-            if (kp_rounds_on(e) && !e->pair_pcool && !compact && !e->tn.pair_tile_fixed) {
-                uint32_t gl = 0;
-                for (uint32_t g = 1; g < G; ++g)
-                    if (P.bm[g] > P.bm[gl]) gl = g;
-                const PairChain& pc = e->h_pchains[gl];
-                if (P.bm[gl]) {
-                    // the capacity the chain's index space has to get under for the next shorter tile length (or for kp_rounds)
-                    uint32_t capq = e->tn.pair_ptiles * PK_TMAX;
-                    for (uint32_t tlen = PK_TMAX; tlen >= PK_TMAX / 4u && pc.m <= e->tn.pair_ptiles * tlen; tlen >>= 1) capq = e->tn.pair_ptiles * (tlen >> 1);
-                    if (pc.m <= e->tn.pair_ptiles * (PK_TMAX / 4u)) capq = PL_MAX - 1u;          // shortest tiles already: next is kp_late
-                    if (pc.qlen <= capq && pc.m > capq && capq >= PL_MAX) {
-                        hipLaunchKernelGGL(kp_ask_compact, dim3(G), dim3(64), 0, e->stream, P, 1u << gl);
-                        compact = true;
-                    } else {
-                        if (pc.m > e->tn.pair_ptiles * PK_TMAX) want_fit = true;          // not yet within kp_rounds' reach: a short batch
-                        yield_q = capq;                                                // compact (and, in kp_rounds, end the batch) at this length
-                        yield_g = gl;
-                    }
-                }
-            }
-            // tile length of this batch: the smallest that keeps the longest chain within PK_TILES_MAX tiles (the
-            // walk costs one dependent load per tile, everything else is proportional to the tile)
-            uint32_t tp = PK_TMAX;
-            // several passes per launch (kp_rounds) when every chain's tiles fit the CUs of one XCD
-            bool persist = kp_rounds_on(e) && !compact && (longest + PK_TMAX - 1u) / PK_TMAX <= e->tn.pair_ptiles;
-            if (persist && e->pair_pcool) { --e->pair_pcool; persist = false; e->ps.degraded = 1; }
-            // (a batch that kp_rounds would have taken, walked launch by launch because it is off: a fall-back's timing)
-            if (!kp_rounds_on(e) && !compact && (longest + PK_TMAX - 1u) / PK_TMAX <= e->tn.pair_ptiles) e->ps.degraded = 1;
-            // ONE cap for the tile count whether this batch is kp_rounds' or kp_round's (round 5): the tile length of a tick must
-            // never GROW.  An entry next[i] = NX_FAR says "nobody fits inside the horizon", and the horizon is two tiles of the
-            // length it was computed at; the walk resolves it by scanning from the end of the CURRENT horizon — right for an
-            // equal or shorter tile length (it scans a superset), wrong for a longer one (the stretch between the two horizons
-            // is never looked at: a later partner, or none).  Until round 5 a kp_round batch was sized for 40 tiles and a
-            // kp_rounds batch for 32: a chain of 33-40 tiles of length T walked launch by launch — the cool-down after a stop of
-            // kp_rounds, or while ANOTHER chain was still too long for kp_rounds — came back to kp_rounds at 2 T.  Found by
-            // tests/stress.py with MM_PAIR_PTILES=5 (seed 130203984: 46 lobbies of one chain missing), on the device and on
-            // the shim; it needs a stop of kp_rounds (or the knob) to happen, which is why no default run ever met it.
-            const uint32_t cap_p = e->tn.pair_ptiles < e->tn.pair_tiles_max ? e->tn.pair_ptiles : e->tn.pair_tiles_max;
-            const uint32_t tiles_max = kp_rounds_on(e) ? cap_p : e->tn.pair_tiles_max;
-            if (!e->tn.pair_tile_fixed)
-                for (uint32_t cand = PK_TMAX / 4u; cand < PK_TMAX; cand <<= 1)    // (an eighth was measured: slower, the fixed cost of a round takes over)
-                    if ((longest + cand - 1u) / cand <= tiles_max) { tp = cand; break; }
-            if (last_tp && tp > last_tp && !compact) {
-                // (the cap changed in mid-tick — kp_rounds turned off for good by a PF_XCD stop — or a knob: every tiled chain is
-                // compacted first, which turns its NX_FAR entries into "not computed")
-                hipLaunchKernelGGL(kp_ask_compact, dim3(G), dim3(64), 0, e->stream, P, 0xFFFFFFFFu);
-                compact = true;
-                last_tp = 0;
-            }
-            tiles = (longest + tp - 1u) / tp;
-#define TILE_LAUNCH(KERNEL, GRID, BLOCK, ...)                                                                              \
-    do {                                                                                                                   \
-        if (tp == PK_TMAX) hipLaunchKernelGGL(KERNEL<PK_TMAX>, GRID, BLOCK, 0, e->stream, __VA_ARGS__);                    \
-        else if (tp == PK_TMAX / 2u) hipLaunchKernelGGL(KERNEL<PK_TMAX / 2u>, GRID, BLOCK, 0, e->stream, __VA_ARGS__);     \
-        else hipLaunchKernelGGL(KERNEL<PK_TMAX / 4u>, GRID, BLOCK, 0, e->stream, __VA_ARGS__);                             \
-    } while (0)
-            // the four compaction kernels look at PairChain.want_compact themselves (a chain that does not want one costs them a few
-            // microseconds): they are enqueued behind EVERY batch, so a chain that ends its batch for a compaction — the 75 % rule,
-            // the yield, the fit — is compacted before the host looks again, one look per batch instead of two
-#define COMPACT_LAUNCH()                                                                                                   \
-    do {                                                                                                                   \
-        TILE_LAUNCH(kc_words, dim3(tiles, G), dim3(256), P);                                                               \
-        TILE_LAUNCH(kc_plan, dim3(G), dim3(1024), P);                                                                      \
-        TILE_LAUNCH(kc_scatter, dim3(tiles, G), dim3(1024), P);                                                            \
-        TILE_LAUNCH(kc_commit, dim3(G), dim3(1024), P);                                                                    \
-    } while (0)
-            if (compact) {
-                COMPACT_LAUNCH();
-                HIPCHK(e, hipGetLastError());
-                continue;                       // look at the new lengths before the next batch
-            }
-            last_tp = tp;
-            for (uint32_t g = 0; g < G; ++g) P.pyq[g] = 0;
-            P.pyq[yield_g] = yield_q;
-            {
-                // one launch per pass; the first of a batch only prepares, the commit brings the
-                // latest parity back into the chains' committed state
-                // chains of many tiles: a second level of the route, rebuilt behind every round (kp_group)
-                P.grp = (e->tn.pair_group_min && tiles >= e->tn.pair_group_min && tp == PK_TMAX) ? PK_GS : 0u;
-                const uint32_t ngr = P.grp ? (tiles + P.grp - 1u) / P.grp : 0u;
-                // the batch's workgroup map: a chain's tiles together on one XCD (mm_pair.inc, PairParams.xseg)
-                dim3 rgrid(tiles, G);
-                P.xslots = 0;
-                uint32_t tof[MM_MAX_GROUPS];
-                for (uint32_t g = 0; g < G; ++g) tof[g] = P.bm[g] ? (P.bm[g] + tp - 1u) / tp : 0u;
-                if (persist) {
-                    // every chain's workgroups on ONE XCD, a CU each: they talk through that XCD's L2 and must all be on the chip
-                    const uint32_t slots = pair_xcd_map(P, tof, G, true);
-                    if (slots) {
-                        P.grp = 0;
-                        // (the arrival words are zero: kp_init at the start of the tick, kc_commit behind every batch)
-                        // (the batch ends by itself when the longest chain can be compacted into shorter tiles: it may be long)
-                        const uint32_t K = e->tn.pair_pbatch, slice = MM_PERSIST_SLICE ? MM_PERSIST_SLICE : K + 1u;
-                        for (uint32_t it = 0; it <= K; it += slice)
-                            TILE_LAUNCH(kp_rounds, dim3(8u * slots), dim3(PT_THREADS), P, it, it + slice < K + 1u ? it + slice : K + 1u, K);
-                        ++e->ps.pair_rounds_launches;
-                        after_persist = true;
-                        COMPACT_LAUNCH();
-                        HIPCHK(e, hipGetLastError());
-                        MMTRY(results_absorb(e, M.L));
-                        MMTRY(results_send(e, sent_no, M.L, e->tn.results_early ? MM_RESULTS_MIN_PAIR : 0xFFFFFFFFu));
-                        continue;
-                    }
-                    P.xslots = 0;
-                }
-                if (e->tn.pair_xcd) {
-                    const uint32_t slots = pair_xcd_map(P, tof, G);
-                    if (slots) rgrid = dim3(8u * slots);
-                }
-                uint32_t r = e->round_ctr;
-                TILE_LAUNCH(kp_round, rgrid, dim3(PT_THREADS), P, r, 1u);
-                ++r;
-                if (P.grp) TILE_LAUNCH(kp_group, dim3(ngr, G), dim3(1024), P, r);
-                for (uint32_t b = 0; b < (want_fit && e->tn.pair_batch > 12u ? 12u : e->tn.pair_batch); ++b) {
-                    TILE_LAUNCH(kp_round, rgrid, dim3(PT_THREADS), P, r, 0u);
-                    ++e->ps.pair_round_launches;
-                    ++r;
-                    if (P.grp) TILE_LAUNCH(kp_group, dim3(ngr, G), dim3(1024), P, r);
-                }
-                TILE_LAUNCH(kp_round_commit, dim3(tiles, G), dim3(256), P, r);
-                hipLaunchKernelGGL(kp_round_stage, dim3(G), dim3(64), 0, e->stream, P, r);
-                COMPACT_LAUNCH();
-                e->round_ctr = r;
-            }
-#undef COMPACT_LAUNCH
-#undef TILE_LAUNCH
-            HIPCHK(e, hipGetLastError());
-            // the device is busy with the batch: now the host takes what the last look's copies brought (slots released)
-            // and sends this look's lobbies after them
-            MMTRY(results_absorb(e, M.L));
-            MMTRY(results_send(e, sent_no, M.L, e->tn.results_early ? MM_RESULTS_MIN_PAIR : 0xFFFFFFFFu));
+            MMTRY(pair_look(e, G, M.L, guard, loop.last_tp));
+            MMTRY(pair_plan(e->h_pchains, G, tn, loop, e->kpr, e->ps, P, plan));
+            if (plan.next == PN_DONE) break;
+            MMTRY(pair_launch(e, P, plan, G));
+            // the lobbies emitted so far leave for the host while the batch runs; the copies are enqueued BEHIND the
+            // batch's launches: the device does not wait for the host's calls
+            if (plan.ship) MMTRY(results_ship(e, plan.sent_no, M.L, MM_RESULTS_MIN_PAIR));
         }
     }
     hipLaunchKernelGGL(kp_late, dim3(G), dim3(PL_THREADS), 0, e->stream, P);
     hipLaunchKernelGGL(kp_finish, dim3(G), dim3(1024), 0, e->stream, P);
     HIPCHK(e, hipGetLastError());
-    if (tail_send) {
-        MMTRY(results_absorb(e, M.L));
-        MMTRY(results_send(e, tail_no, M.L, e->tn.results_early ? MM_RESULTS_MIN_PAIR : 0xFFFFFFFFu));
-    }
+    if (plan.ship) MMTRY(results_ship(e, plan.sent_no, M.L, MM_RESULTS_MIN_PAIR));   // (behind kp_late's launch, as above)
     return MM_OK;
 }
 
@@ -2553,205 +2538,219 @@ static void report_team_pass(mm_engine* e, uint32_t guard)
     e->dbg_last_c = tc.dbg[4];
 }
 
+// TeamParams of a tick: the engine's buffers and the knobs (mm_tuning -> TeamParams).  The chunk order (team_order) and
+// use_f2 / seq / n_emit / hf_x (team_launch) follow look by look and pass by pass.
+static void team_params(TeamParams& P, const mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
+{
+    walk_params_common(P, e, mode, purge);
+    P.scan_cap = e->tn.team_cap; P.late_bail = 4u * e->tn.team_late + 32u; P.fwait = e->tn.team_fwait;
+    P.fix_max = e->tn.team_fix_max; P.fix_t8 = e->tn.team_fix_t8; P.fix_t4 = e->tn.team_fix_t4;
+    P.pull_xcd = e->tn.team_pull_xcd; P.nowait = e->tn.team_nowait;
+    P.debug = e->tn.debug ? (e->tn.team_batch == 1u ? 3u : 1u) : 0u;   // bit 1 (with MM_TEAM_BATCH=1): kt_f counts every F it writes — an atomic per thread
+    P.window = M.window > 0xFFFFFu ? 0xFFFFFu : M.window; P.eqmask = M.eqmask; P.M = M;
+    P.out_cap = (e->cfg.capacity + MM_MAX_LOBBY) / M.L + 1u;
+    P.bits_stride = e->pk_bits_stride; P.pstride = e->pk_stride; P.chunk_stride = e->tk_chunk_stride; P.blk_stride = e->pk_stride / 64u;
+    P.tchains = e->d_tchains;
+    // (the pair path's arrays under the team path's names, then its own)
+    P.tkey = e->d_pk_key[0]; P.sqk = e->d_pk_key[1]; P.sqp = e->d_pk_oidx[0]; P.blkbase = e->d_pk_oidx[1];
+    P.bits[0] = e->d_pk_bits[0]; P.bits[1] = e->d_pk_bits[1]; P.fv = e->d_pk_scratch; P.vis = e->d_pk_rec1;
+    P.chunk = e->d_tk_chunk; P.chunkB = e->d_tk_chunkB; P.bitsB = e->d_tk_bitsB; P.fdone = e->d_tk_fdone;
+    P.fv2 = e->d_tk_fv2; P.fpos = e->d_tk_fpos; P.memb = e->d_tk_memb; P.sqi = e->d_tk_sqi;
+}
+
+// kt_fc's order of kt_f's workgroups (TeamParams.fo_*): the chains that are still walked, by falling length, aligned at
+// their ends — made again at every look of the host at the chains, so that a chain that is done costs a pass neither
+// workgroups nor (TeamParams.act) a load.  Returns the workgroups of the order.
+static uint32_t team_order(TeamParams& P, const TeamChain* tcs, uint32_t G)
+{
+    uint32_t ord[MM_MAX_GROUPS], len[MM_MAX_GROUPS], K = 0, fo_total = 0;
+    P.act = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        const TeamChain& t = tcs[g];
+        if (!t.fast || t.m == 0u || t.done) continue;
+        P.act |= 1u << g;
+        const uint32_t n = (t.m + TT_CH - 1u) / TT_CH;
+        uint32_t at = K++;
+        while (at > 0u && len[at - 1u] < n) { ord[at] = ord[at - 1u]; len[at] = len[at - 1u]; --at; }
+        ord[at] = g; len[at] = n;
+    }
+    P.fo_n = K;
+    for (uint32_t s = 0; s < K; ++s) {
+        P.fo_chain[s] = ord[s]; P.fo_nch[s] = len[s];
+        P.fo_start[s] = fo_total; P.fo_dhi[s] = len[s];
+        fo_total += (s + 1u) * (len[s] - (s + 1u < K ? len[s + 1u] : 0u));
+    }
+    P.fo_start[K] = fo_total; P.fo_dhi[K] = 0;
+    return fo_total;
+}
+
+// Batches of passes between two looks at the chains.  The first is short (a tick of a stream seats a handful of
+// lobbies and is over after two passes); once every chain that is still walked emits at most `team_late` lobbies
+// per pass, kt_late walks them to their end in one launch (mm_team.inc) — from the first pass on when the mode has
+// seen only a few arrivals since its last (quiescent) tick: the ticks of a stream.  kt_late hands a chain back
+// after a pass that seated many lobbies after all (`late_bail`); the sub-queues are rebuilt then (it leaves no
+// tombstones behind).
+struct TeamLoop {
+    bool late_ok, late_now, force_build;       // kt_late may take this tick's chains at all | takes the next batch | the next pass needs fresh sub-queues
+    uint32_t pass, batch, n_emit;              // passes launched so far, passes of the next batch, emitter workgroups per chain
+};
+
+// What the team walk does behind this look at the chains' records `tcs` (no HIP, no engine): false when every chain is done.
+static bool team_plan(const TeamChain* tcs, uint32_t G, const mm_tuning& tn, TeamLoop& L)
+{
+    bool busy = false, late = L.late_ok;
+    uint32_t most = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        const TeamChain& t = tcs[g];
+        if (!t.fast || t.done) continue;
+        busy = true;
+        most = t.n_vis > most ? t.n_vis : most;
+        if (t.n_vis > tn.team_late) late = false;
+    }
+    if (!busy) return false;
+    if (L.late_now) {
+        // a chain came back from kt_late (a pass seated more than late_bail lobbies): the pass kernels take over,
+        // from the chain's current pass on
+        L.late_now = false;
+        if (L.pass < 2u) L.pass = 2u;                 // (no doubled rebuild: the tick is past its opening)
+        L.batch = tn.team_batch;
+        return true;
+    }
+    L.late_now = late;
+    L.n_emit = most / (TT_WAVES - 1u) + 1u;                         // (kt_fc's emitter workgroups have seven worker waves)
+    if (L.n_emit > tn.team_emit_max) L.n_emit = tn.team_emit_max;
+    // close to the switch: look again soon (a look costs a D2H round trip, an idle pass a launch)
+    L.batch = (tn.team_late && most <= 3u * tn.team_late) ? (tn.team_batch < 4u ? tn.team_batch : 4u) : tn.team_batch;
+    return true;
+}
+
+// The enqueues of a batch: kt_late's one launch, or `batch` passes of the pass kernels.
+static void team_launch(mm_engine* e, TeamParams& P, TeamLoop& L, uint32_t G, uint32_t nch, uint32_t fo_total)
+{
+    const mm_tuning& tn = e->tn;
+    if (L.late_now) {
+        hipLaunchKernelGGL(kt_late, dim3(G), dim3(TL_THREADS), 0, e->stream, P);
+        ++e->ps.team_late_launches;
+        L.force_build = true;                       // whoever comes back from kt_late needs fresh sub-queues
+        return;
+    }
+    for (uint32_t b = 0; b < L.batch; ++b, ++L.pass) {
+        // the first passes of a tick emit hundreds of lobbies each: the chase takes them two at a time (kt_f2)
+        P.use_f2 = L.pass < tn.team_f2 ? 1u : 0u;
+        // the role sub-queues are rebuilt in the first two passes (a head that sat out the first one is back in
+        // the second) and every team_rebuild passes after; in between, players that leave are tombstones in them
+        if (L.pass < 2u || L.pass % tn.team_rebuild == 0u || L.force_build) {
+            hipLaunchKernelGGL(kt_build, dim3(nch, G), dim3(TT_CH), 0, e->stream, P);
+            ++e->ps.team_build_launches;
+        }
+        L.force_build = false;
+        // the emitters ride in the chase's launch, enough waves for the lobbies the last look saw per pass (a pass
+        // that emits more than that is only slower)
+        if (++e->team_seq == 0u) e->team_seq = 1u;
+        P.seq = e->team_seq;
+        P.n_emit = L.n_emit;
+        P.hf_x = 0xFFFFFFFFu;
+        if (P.use_f2) {
+            // (the stored lobbies' fill from the heads of the queues rides in kt_f's launch: MM_TEAM_SPLIT)
+            if (tn.team_split) P.hf_x = nch;
+            hipLaunchKernelGGL(kt_f, dim3(nch + (tn.team_split ? 1u : 0u), G), dim3(TT_CH), 0, e->stream, P);
+            hipLaunchKernelGGL(kt_f2, dim3(nch, G), dim3(TT_CH), 0, e->stream, P);
+            hipLaunchKernelGGL(kt_chase, dim3(G * (1u + P.n_emit)), dim3(TC_THREADS), 0, e->stream, P);
+            ++e->ps.team_f_launches;
+        } else {
+            ++e->ps.team_fc_launches;
+            // kt_f and the chase of the pass in one launch: the chasers take F chunk by chunk as it is written
+            hipLaunchKernelGGL(kt_fc, dim3(G * (1u + P.n_emit) + fo_total), dim3(TT_CH), 0, e->stream, P);
+        }
+    }
+}
+
 // The team path (mm_team.inc).  *any is set when at least one chain was walked by it; the others
 // are left to k_walk.
 static int team_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge, bool* any)
 {
-    const mm_config& cfg = e->cfg;
-    const uint32_t G = cfg.n_groups;
+    const uint32_t G = e->cfg.n_groups;
+    const mm_tuning tn = e->tn;
+    const TeamChain* const tcs = e->h_tchains;
     *any = false;
     TeamParams P;
-    walk_params_common(P, e, mode, purge);
-    // the knobs (mm_tuning -> TeamParams)
-    P.scan_cap = e->tn.team_cap;
-    P.late_bail = 4u * e->tn.team_late + 32u;
-    P.fwait = e->tn.team_fwait;
-    P.fix_max = e->tn.team_fix_max;
-    P.fix_t8 = e->tn.team_fix_t8;
-    P.fix_t4 = e->tn.team_fix_t4;
-    P.pull_xcd = e->tn.team_pull_xcd;
-    P.nowait = e->tn.team_nowait;
-    P.debug = e->tn.debug ? (e->tn.team_batch == 1u ? 3u : 1u) : 0u;   // bit 1 (with MM_TEAM_BATCH=1): kt_f counts every F it writes — an atomic per thread
-    P.window = M.window > 0xFFFFFu ? 0xFFFFFu : M.window;
-    P.eqmask = M.eqmask;
-    P.out_cap = (cfg.capacity + MM_MAX_LOBBY) / M.L + 1u;
-    P.bits_stride = e->pk_bits_stride;
-    P.pstride = e->pk_stride;
-    P.chunk_stride = e->tk_chunk_stride;
-    P.blk_stride = e->pk_stride / 64u;
-    P.M = M;
-    P.tchains = e->d_tchains;
-    P.tkey = e->d_pk_key[0];
-    P.bits[0] = e->d_pk_bits[0];
-    P.bits[1] = e->d_pk_bits[1];
-    P.sqk = e->d_pk_key[1];
-    P.sqp = e->d_pk_oidx[0];
-    P.fv = e->d_pk_scratch;
-    P.vis = e->d_pk_rec1;
-    P.blkbase = e->d_pk_oidx[1];
-    P.chunk = e->d_tk_chunk;
-    P.fv2 = e->d_tk_fv2;
-    P.fpos = e->d_tk_fpos;
-    P.memb = e->d_tk_memb;
-    P.bitsB = e->d_tk_bitsB;
-    P.chunkB = e->d_tk_chunkB;
-    P.sqi = e->d_tk_sqi;
-    P.fdone = e->d_tk_fdone;
+    team_params(P, e, mode, M, purge);
     hipLaunchKernelGGL(kt_init, dim3(G), dim3(1024), 0, e->stream, P);
     HIPCHK(e, hipGetLastError());
     MMTRY(look_launch(e, e->d_tchains, e->h_tchains, G * sizeof(TeamChain)));
     MMTRY(look_wait(e));
     uint32_t longest = 0;
     unsigned long long arrivals = 0;
-    bool late_ok = e->tn.team_late != 0u;
+    TeamLoop L;
+    L.late_ok = tn.team_late != 0u;
     for (uint32_t g = 0; g < G; ++g) {
-        const TeamChain& t = e->h_tchains[g];
+        const TeamChain& t = tcs[g];
         if (!t.fast) continue;
         if (t.m > longest) longest = t.m;
         const uint32_t had = e->tk_last_len[mode * G + g];
         arrivals += t.before > had ? t.before - had : 0u;
-        if (t.m > TL_BITS_MAX || t.sitout) late_ok = false;      // (a head that sat out is not in the first pass's sub-queues)
+        if (t.m > TL_BITS_MAX || t.sitout) L.late_ok = false;      // (a head that sat out is not in the first pass's sub-queues)
     }
     if (!longest) return MM_OK;
     *any = true;
     const uint32_t nch = (longest + TT_CH - 1u) / TT_CH;
-    uint32_t fo_total = 0;
-    // kt_fc's order of kt_f's workgroups (TeamParams.fo_*): the chains that are still walked, by falling length, aligned at
-    // their ends — made again at every look of the host at the chains, so that a chain that is done costs a pass neither
-    // workgroups nor (TeamParams.act) a load
-    auto team_order = [&]() {
-        uint32_t ord[MM_MAX_GROUPS], len[MM_MAX_GROUPS], K = 0;
-        P.act = 0;
-        for (uint32_t g = 0; g < G; ++g) {
-            const TeamChain& t = e->h_tchains[g];
-            if (!t.fast || t.m == 0u || t.done) continue;
-            P.act |= 1u << g;
-            const uint32_t n = (t.m + TT_CH - 1u) / TT_CH;
-            uint32_t at = K++;
-            while (at > 0u && len[at - 1u] < n) { ord[at] = ord[at - 1u]; len[at] = len[at - 1u]; --at; }
-            ord[at] = g;
-            len[at] = n;
-        }
-        P.fo_n = K;
-        fo_total = 0;
-        for (uint32_t s = 0; s < K; ++s) {
-            P.fo_chain[s] = ord[s];
-            P.fo_nch[s] = len[s];
-            P.fo_start[s] = fo_total;
-            P.fo_dhi[s] = len[s];
-            fo_total += (s + 1u) * (len[s] - (s + 1u < K ? len[s + 1u] : 0u));
-        }
-        P.fo_start[K] = fo_total;
-        P.fo_dhi[K] = 0;
-    };
-    team_order();
+    uint32_t fo_total = team_order(P, tcs, G);
     hipLaunchKernelGGL(kt_pack, dim3(nch, G), dim3(TT_CH), 0, e->stream, P);
     HIPCHK(e, hipGetLastError());
-    // Batches of passes between two looks at the chains.  The first is short (a tick of a stream seats a handful of
-    // lobbies and is over after two passes); once every chain that is still walked emits at most `team_late` lobbies
-    // per pass, kt_late walks them to their end in one launch (mm_team.inc) — from the first pass on when the mode has
-    // seen only a few arrivals since its last (quiescent) tick: the ticks of a stream.  kt_late hands a chain back
-    // after a pass that seated many lobbies after all (`late_bail`); the sub-queues are rebuilt then (it leaves no
-    // tombstones behind).
-    uint32_t pass = 0, batch = e->tn.team_batch < 2u ? e->tn.team_batch : 2u;
-    uint32_t n_emit = longest / (M.L * TC_WAVES * 8u) + 1u;          // the first passes: a worker wave per lobby if an eighth of the chain is seated
-    if (n_emit > e->tn.team_emit_max) n_emit = e->tn.team_emit_max;
-    uint32_t team_no[MM_MAX_GROUPS];
-    bool team_have = false, force_build = false;
-    bool late_now = late_ok && e->tn.team_late0 != 0u && arrivals <= e->tn.team_late0;
+    L.pass = 0; L.force_build = false;
+    L.batch = tn.team_batch < 2u ? tn.team_batch : 2u;
+    L.n_emit = longest / (M.L * TC_WAVES * 8u) + 1u;          // the first passes: a worker wave per lobby if an eighth of the chain is seated
+    if (L.n_emit > tn.team_emit_max) L.n_emit = tn.team_emit_max;
+    L.late_now = L.late_ok && tn.team_late0 != 0u && arrivals <= tn.team_late0;
+    uint32_t team_no[MM_MAX_GROUPS]; bool team_have = false;
     ++e->ps.host_looks;
-    if (late_now) { hipLaunchKernelGGL(kt_build, dim3(nch, G), dim3(TT_CH), 0, e->stream, P); ++e->ps.team_build_launches; }
+    if (L.late_now) { hipLaunchKernelGGL(kt_build, dim3(nch, G), dim3(TT_CH), 0, e->stream, P); ++e->ps.team_build_launches; }
     for (uint32_t guard = 0;; ++guard) {
         // a pass that changes nothing ends a chain and every other pass seats somebody
-        if (guard > cfg.capacity + 64u) return MM_ERR_INTERNAL;
-        if (late_now) {
-            hipLaunchKernelGGL(kt_late, dim3(G), dim3(TL_THREADS), 0, e->stream, P);
-            ++e->ps.team_late_launches;
-            force_build = true;                       // whoever comes back from kt_late needs fresh sub-queues
-        } else {
-            for (uint32_t b = 0; b < batch; ++b, ++pass) {
-                // the first passes of a tick emit hundreds of lobbies each: the chase takes them two at a time (kt_f2)
-                P.use_f2 = pass < e->tn.team_f2 ? 1u : 0u;
-                // the role sub-queues are rebuilt in the first two passes (a head that sat out the first one is back in
-                // the second) and every team_rebuild passes after; in between, players that leave are tombstones in them
-                if (pass < 2u || pass % e->tn.team_rebuild == 0u || force_build) {
-                    hipLaunchKernelGGL(kt_build, dim3(nch, G), dim3(TT_CH), 0, e->stream, P);
-                    ++e->ps.team_build_launches;
-                }
-                force_build = false;
-                // the emitters ride in the chase's launch, enough waves for the lobbies the last look saw per pass (a pass
-                // that emits more than that is only slower)
-                if (++e->team_seq == 0u) e->team_seq = 1u;
-                P.seq = e->team_seq;
-                P.n_emit = n_emit;
-                P.hf_x = 0xFFFFFFFFu;
-                if (P.use_f2) {
-                    // (the stored lobbies' fill from the heads of the queues rides in kt_f's launch: MM_TEAM_SPLIT)
-                    if (e->tn.team_split) P.hf_x = nch;
-                    hipLaunchKernelGGL(kt_f, dim3(nch + (e->tn.team_split ? 1u : 0u), G), dim3(TT_CH), 0, e->stream, P);
-                    hipLaunchKernelGGL(kt_f2, dim3(nch, G), dim3(TT_CH), 0, e->stream, P);
-                    hipLaunchKernelGGL(kt_chase, dim3(G * (1u + P.n_emit)), dim3(TC_THREADS), 0, e->stream, P);
-                    ++e->ps.team_f_launches;
-                } else {
-                    ++e->ps.team_fc_launches;
-                    // kt_f and the chase of the pass in one launch: the chasers take F chunk by chunk as it is written
-                    hipLaunchKernelGGL(kt_fc, dim3(G * (1u + P.n_emit) + fo_total), dim3(TT_CH), 0, e->stream, P);
-                }
-            }
-        }
+        if (guard > e->cfg.capacity + 64u) return MM_ERR_INTERNAL;
+        const bool was_late = L.late_now;
+        team_launch(e, P, L, G, nch, fo_total);
         HIPCHK(e, hipGetLastError());
         uint32_t p0[MM_MAX_GROUPS];
-        for (uint32_t g = 0; g < G; ++g) p0[g] = e->h_tchains[g].passes;
+        for (uint32_t g = 0; g < G; ++g) p0[g] = tcs[g].passes;
         MMTRY(look_launch(e, e->d_tchains, e->h_tchains, G * sizeof(TeamChain)));
         // host work while the device runs the batch: what the last look's copies brought, then this look's lobbies
-        MMTRY(results_absorb(e, M.L));
-        if (team_have) MMTRY(results_send(e, team_no, M.L, e->tn.results_early ? MM_RESULTS_MIN_TEAM : 0xFFFFFFFFu));
+        MMTRY(results_ship(e, team_have ? team_no : nullptr, M.L, MM_RESULTS_MIN_TEAM));
         MMTRY(look_wait(e));
         ++e->ps.host_looks;
-        {   // kt_fc's chasers count the anchors whose chunk flag did not come (they looked the lobby up themselves)
-            uint32_t fl = 0;
-            for (uint32_t g = 0; g < G; ++g) if (e->h_tchains[g].fast) fl += e->h_tchains[g].flags_late;
-            e->ps.team_flags_late = fl;
-        }
-        bool busy = false, late = late_ok;
-        uint32_t most = 0;
+        if (tn.debug && was_late) report_team_late(e, p0);
+        if (tn.debug && tn.team_batch == 1u && !was_late) report_team_pass(e, guard);
+        // the lobbies emitted so far leave for the host while the next passes run (sent behind the next batch's launches);
+        // kt_fc's chasers count the anchors whose chunk flag did not come (they looked the lobby up themselves)
+        uint32_t bf[MM_MAX_GROUPS], fl = 0;
         for (uint32_t g = 0; g < G; ++g) {
-            const TeamChain& t = e->h_tchains[g];
-            if (!t.fast || t.done) continue;
-            busy = true;
-            most = t.n_vis > most ? t.n_vis : most;
-            if (t.n_vis > e->tn.team_late) late = false;
+            bf[g] = tcs[g].before;
+            team_no[g] = tcs[g].fast ? tcs[g].n_out : 0u;
+            if (tcs[g].fast) fl += tcs[g].flags_late;
         }
-        if (e->tn.debug && late_now) report_team_late(e, p0);
-        if (e->tn.debug && e->tn.team_batch == 1u && !late_now) report_team_pass(e, guard);
-        {   // the lobbies emitted so far leave for the host while the next passes run (sent behind the next batch's launches)
-            uint32_t bf[MM_MAX_GROUPS];
-            for (uint32_t g = 0; g < G; ++g) { bf[g] = e->h_tchains[g].before; team_no[g] = e->h_tchains[g].fast ? e->h_tchains[g].n_out : 0u; }
-            if (!e->r_based) results_set_bases(e, bf, M.L);
-            team_have = true;
-        }
-        if (!busy) break;
-        team_order();
-        if (late_now) {
-            // a chain came back from kt_late (a pass seated more than late_bail lobbies): the pass kernels take over,
-            // from the chain's current pass on
-            late_now = false;
-            if (pass < 2u) pass = 2u;                 // (no doubled rebuild: the tick is past its opening)
-            batch = e->tn.team_batch;
-            continue;
-        }
-        late_now = late;
-        n_emit = most / (TT_WAVES - 1u) + 1u;                         // (kt_fc's emitter workgroups have seven worker waves)
-        if (n_emit > e->tn.team_emit_max) n_emit = e->tn.team_emit_max;
-        // close to the switch: look again soon (a look costs a D2H round trip, an idle pass a launch)
-        batch = (e->tn.team_late && most <= 3u * e->tn.team_late) ? (e->tn.team_batch < 4u ? e->tn.team_batch : 4u) : e->tn.team_batch;
+        e->ps.team_flags_late = fl;
+        if (!e->r_based) results_set_bases(e, bf, M.L);
+        team_have = true;
+        if (!team_plan(tcs, G, tn, L)) break;
+        fo_total = team_order(P, tcs, G);
     }
     if (e->ps.team_flags_late) { e->ps.team_flags_late_total += e->ps.team_flags_late; e->ps.degraded = 1; }
     hipLaunchKernelGGL(kt_fin_scatter, dim3(nch, G), dim3(TT_CH), 0, e->stream, P);
     hipLaunchKernelGGL(kt_fin_copy, dim3(nch, G), dim3(TT_CH), 0, e->stream, P);
     HIPCHK(e, hipGetLastError());
-    if (e->tn.debug) report_team(e);
+    if (tn.debug) report_team(e);
     return MM_OK;
+}
+
+// MM_PAIR_DEBUG=1, every 200th look of a tick at its chains: where the tiled stage stands (stderr).
+static void report_pair_look(const mm_engine* e, uint32_t guard, uint32_t last_tp)
+{
+    fprintf(stderr, "[mm-pair] look %u: cool-down %u, persist %d, last tile length %u;", guard, e->kpr.pair_pcool, (int)kp_rounds_on(e->tn, e->kpr), last_tp);
+    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) {
+        const PairChain& pc = e->h_pchains[g];
+        if (pc.fast) fprintf(stderr, " g%u[stage %u m %u qlen %u passes %u compact %u pfail 0x%x]", g, pc.stage, pc.m, pc.qlen, pc.passes, pc.want_compact, pc.pfail);
+    }
+    fprintf(stderr, "\n");
 }
 
 // MM_PAIR_DEBUG=1: what the pair path's kernels counted and timed in this tick, per rating group (stderr).
@@ -2775,7 +2774,7 @@ static int report_pair(mm_engine* e)
         if (hp[g].ppass) {
             const uint32_t nr = hp[g].ptm[5] ? hp[g].ptm[5] : 1u;
             fprintf(stderr, "[mm-pair] g%u kp_rounds: %u passes inside persistent launches (%u launches gave up so far); tile1 cycles/pass over %u passes (barrier %u fast hops %u walk+sweepA %u apply %u | detect %u items %u long %u | graph %u resolve %u publish %u | head+arrive %u) walk loop %.0f cycles, %.1f hops\n",
-                    g, hp[g].ppass, e->pair_pstops, nr, hp[g].ptm[0] / nr, hp[g].ptm[3] / nr, hp[g].ptm[6] / nr, hp[g].ptm[9] / nr, hp[g].ptm[1] / nr,
+                    g, hp[g].ppass, e->kpr.pair_pstops, nr, hp[g].ptm[0] / nr, hp[g].ptm[3] / nr, hp[g].ptm[6] / nr, hp[g].ptm[9] / nr, hp[g].ptm[1] / nr,
                     hp[g].ptm[12] / nr, hp[g].ptm[2] / nr, hp[g].ptm[7] / nr, hp[g].ptm[8] / nr, hp[g].ptm[10] / nr, hp[g].ptm[4] / nr,
                     16.0 * hp[g].ptm[13] / nr, (double)hp[g].ptm[15] / nr);
             fprintf(stderr, "[mm-pair] g%u kp_rounds, tile 1's walker off the fast path: %u hops whose partner had left, %.0f cycles each; %u hops without a partner inside the horizon, %.0f cycles each\n",
@@ -3997,9 +3996,9 @@ extern "C" int mm_path_stats_get(mm_engine* e, mm_path_stats* out)
 {
     if (!e || !out || out->size < 2u * sizeof(uint32_t)) return MM_ERR_INVALID_ARG;
     mm_path_stats ps = e->ps;
-    ps.pair_persist_off = kp_rounds_on(e) ? 0u : 1u;
-    ps.pair_cooldown = e->pair_pcool;
-    ps.pair_stops_total = e->pair_pstops;
+    ps.pair_persist_off = kp_rounds_on(e->tn, e->kpr) ? 0u : 1u;
+    ps.pair_cooldown = e->kpr.pair_pcool;
+    ps.pair_stops_total = e->kpr.pair_pstops;
     const uint32_t n = out->size < (uint32_t)sizeof(ps) ? out->size : (uint32_t)sizeof(ps);
     ps.size = n;
     memcpy(out, &ps, n);

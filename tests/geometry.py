@@ -18,7 +18,7 @@ CONSTANTS = ("PK_T", "PK_TILES_MAX", "PK_GROUP_MIN", "PK_GS", "PL_MAX", "PL_COMP
              "NX_FAR", "TT_MIN", "TT_MAX", "TT_CH", "TT_SCAN_CAP", "TF_PAD", "TF_FAR_BITS", "TF_BW", "TL_BITS_MAX",
              "MM_RESULTS_MIN_PAIR", "MM_RESULTS_MIN_TEAM")
 TUNING = ("pair_ptiles", "pair_tiles_max", "pair_group_min", "team_cap")
-# literals of mm_engine.hip's pair_walk that have no #define: name -> the statement that holds the number
+# literals of mm_engine.hip's pair_open that have no #define: name -> the statement that holds the number
 HOST_LITERALS = {
     "NX_SEG_MIN": r"uint32_t seg = (\d+)u, stage = NXI_STAGE;",              # kp_nx_init's anchors per workgroup start here and double up to NXI_SEG
     "KP_INIT_ROW": r"hipLaunchKernelGGL\(kp_init, dim3\(G\), dim3\((\d+)\)",   # threads of the workgroup that reads the queue, eight rows unrolled
@@ -39,13 +39,19 @@ def source_defines():
 
 
 def makefile_overrides(target=EMU_SMALL_TARGET, makefile=EMU_MAKEFILE):
-    """The -DNAME=value options of one target's recipe in tests/emu/Makefile."""
+    """The -DNAME=value options of one target's recipe in tests/emu/Makefile, the Makefile's own variables expanded."""
     with open(makefile) as f:
         text = f.read().replace("\\\n", " ")
+    variables = dict(re.findall(r"^([A-Za-z_]\w*)[ \t]*\??=[ \t]*(.*)$", text, re.M))
+    for _ in range(8):                                                       # (variables that hold variables)
+        text = re.sub(r"\$\((\w+)\)", lambda m: variables.get(m.group(1), m.group(0)), text)
     m = re.search(r"^%s:.*\n((?:\t.*\n?)+)" % re.escape(target), text, re.M)
     if not m:
         raise KeyError("no target %s in %s" % (target, makefile))
-    return dict(re.findall(r"-D([A-Za-z]\w*)=(\S+)", m.group(1)))           # (not the toolchain's own: -D_FORTIFY_SOURCE)
+    over = dict(re.findall(r"-D([A-Za-z]\w*)=(\S+)", m.group(1)))           # (not the toolchain's own: -D_FORTIFY_SOURCE)
+    if not over:
+        raise KeyError("the recipe of %s in %s holds no -D option: not the tiny geometry" % (target, makefile))
+    return over
 
 
 def _value(name, texts, seen=()):

@@ -199,3 +199,18 @@ def test_the_tile_length_of_a_tick_never_grows(oracle_cls, monkeypatch, seed):
         assert_same_state(a, b, cfg, "tile length growth, seed %d" % seed)
         ps = a.path_stats()
         assert ps["pair_round_launches"] > 0 and ps["pair_rounds_launches"] > 0      # both kinds of batch were in the tick
+
+
+def test_pair_plan_keeps_its_promises():
+    """tests/emu/plan_check.cpp: pair_plan, the host's batch logic of the pair walk, called on made-up chain records for
+    a few thousand seeded look sequences with the knobs at the extremes of tests/stress.py's menus and a kp_rounds stop
+    of every kind.  The program asserts DESIGN.md's "batch logic on the host": the tile length of a tick never grows,
+    the one cap of the tile count, when a batch may be persistent, the 16 batches of a cool-down, stops counted once,
+    the watchdog's 65th idle look.  It says which one broke, with the seed."""
+    import os
+    import subprocess
+    emu = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
+    subprocess.check_call(["make", "-C", emu, "--no-print-directory", "plan_check"], stdout=subprocess.DEVNULL)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("MM_")}       # (the knobs are the program's own)
+    run = subprocess.run([os.path.join(emu, "plan_check")], env=env, capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and run.stdout.startswith("plan_check ok"), run.stdout + run.stderr
