@@ -1071,7 +1071,6 @@ __global__ __launch_bounds__(PL_THREADS) void kp_late(PairParams P)
 // players BEHIND the cursor, and next[] / the step graph only look ahead.
 // ------------------------------------------------------------------------------------
 #define PT_THREADS 1024
-#define PW_WAVES 0                   // (waves 1..PW_WAVES of kp_round kept out of the key staging; none now)
 #define PF_N 6u                      // 16-byte loads per thread with which kp_round pulls REC / bitmap through its XCD's L2
 
 static __device__ __forceinline__ uint32_t* tc_row(const PairParams& P, uint32_t row, uint32_t g)
@@ -1106,7 +1105,7 @@ static __device__ __forceinline__ void prep_stage_keys(uint32_t* s_key, const ui
     (void)PK_T;
     // (2 * PK_T + 64) / 4 groups of four keys over at least STG_T threads: at most STG per thread.  All
     // loads of a thread are issued before the first one is used (one memory latency, not STG of them).
-    constexpr uint32_t STG_T = PT_THREADS - 64u * (1u + PW_WAVES);      // the fewest threads it is called with
+    constexpr uint32_t STG_T = PT_THREADS - 64u;      // the fewest threads it is called with (kp_round: all waves but the walker)
     constexpr uint32_t STG = ((2u * PK_T + 64u) / 4u + STG_T - 1u) / STG_T;
     const uint32_t ngroups = (hl + 64u + 3u) >> 2;
     uint4 k[STG];
@@ -1608,20 +1607,29 @@ static __device__ __forceinline__ void prep_tables(const uint32_t* s_key, const 
 #undef PT_MARK
 }
 
+
 // ------------------------------------------------------------------------------------
-// kp_round: the three launches of a round fused into ONE.  Every tile's workgroup
-//   1. walks the route of pass p itself (wave 0; the same deterministic walk in every
-//      workgroup, so nobody waits for anybody),
-//   2. applies pass p to its own tile (in-tile chain, bitmap, emission),
-//   3. prepares its tile for pass p+1.
-// Everything a workgroup reads from another one (REC, exit anchors, the bitmap at the start
-// of the pass, head partners, the chain's round state) was written by the PREVIOUS launch
-// into the buffers of the other parity, so there is no intra-launch communication at all.
-// The price: a tile sees its lookahead tile as it was one pass ago.  That only ever shows
-// too many queued players (a superset), so an exit anchor may point at a partner that has
-// just left the queue; the walk checks the partner against the pass-start bitmap and rescans
-// if so (rare: the partner must have been matched in exactly the previous pass).
-// `first`: the launch that opens a batch only prepares (there is no route yet).
+// The pass that kp_round and kp_rounds share.  Both kernels do the same round by design — walk the route
+// of the pass, apply it to the own tile, prepare the tile for the next one — once per launch (kp_round) or for a
+// batch of passes with the tile resident in LDS (kp_rounds), and kp_round is where every stop of kp_rounds goes
+// on: the two must never differ in what a pass is.  So everything of the pass that does not depend on how a
+// workgroup gets at its data is written once, here:
+//
+//   pair_wg_map, PairTile                   which (chain, tile) a workgroup is, and the tile's geometry
+//   round_state_open / round_state_commit   RoundState <-> the chain's committed record (also kp_round_commit)
+//   PassEmit                                a thread's deferred lobby: loads early, stores late
+//   PairWalk, walk_head, walk_general_hop,  the walk's running state, the carried anchor's head match, a hop
+//   walk_close                              that is not of the fast kind, the state behind the pass
+//   pass_apply                              section 2: the pass on the own tile
+//   head_first_fit                          the carried anchor's first fit in the tile, for the next pass
+//
+// The one systematic difference is how the walk reads what OTHER workgroups wrote: the previous launch did
+// (kp_round: plain loads) or this one (kp_rounds: past the vector L1) — a policy type, LdLaunch / LdPeer.
+// What a kernel owns: its staging and L2 pull (kp_round) or lookahead refresh and flag barrier (kp_rounds), its
+// fast path (kp_round's knows the second route level, kp_rounds's is tw_hops), what follows the publication,
+// the order of the sections and every barrier between them.
+// Nothing here reads threadIdx: kp_rounds hands in the index it launders once per iteration (TW_LAUNDER), and
+// what is derived from it must not be hoisted out of that loop.
 // ------------------------------------------------------------------------------------
 
 // Wave-wide: first queued index in [from, m) whose key fits akey (HBM keys + bitmap), or PK_NO.
@@ -1640,6 +1648,407 @@ static __device__ __forceinline__ uint32_t w_scan_fit(const uint32_t* key, const
     return PK_NO;
 }
 
+// Wave-wide, like w_scan_fit, on a bitmap other workgroups of this launch have written.
+static __device__ __forceinline__ uint32_t w_scan_fit_x(const uint32_t* key, const uint32_t* bits, uint32_t akey, uint32_t from, uint32_t m,
+                                                        uint32_t w, int lane)
+{
+    uint32_t klo, krng;
+    pk_bounds(akey, w, klo, krng);
+    // four 64-candidate steps per trip to memory, bitmap words and keys side by side (round 5: one step a trip, the key
+    // behind its bitmap word — 5.4k cycles for each of the ~50 hops a tick whose partner has just left, on every tile's walker)
+    for (uint32_t p = from; p < m; p += 256u) {
+        uint32_t bw[4], kv[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; ++u) {
+            const uint32_t c = p + 64u * u + (uint32_t)lane;
+            bw[u] = c < m ? xld(bits + (c >> 5)) : 0u;
+            kv[u] = c < m ? key[c] : 0xFFFFFFFFu;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; ++u) {
+            const uint32_t c = p + 64u * u + (uint32_t)lane;
+            const unsigned long long b = __ballot(((bw[u] >> (c & 31u)) & 1u) != 0u && pk_in(kv[u], klo, krng));
+            if (b) return p + 64u * u + (uint32_t)__ffsll(b) - 1u;
+        }
+    }
+    return PK_NO;
+}
+
+// How the walk reads REC, exit anchors, head partners and the pass-start bitmap of other tiles.
+struct LdLaunch {                    // the previous launch wrote them (kp_round)
+    static __device__ __forceinline__ uint32_t ld(const uint32_t* p) { return *p; }
+    static __device__ __forceinline__ uint32_t ld16(const uint16_t* p) { return *p; }
+    static __device__ __forceinline__ uint32_t scan_fit(const uint32_t* key, const uint32_t* bits, uint32_t akey, uint32_t from, uint32_t m,
+                                                        uint32_t w, int lane) { return w_scan_fit(key, bits, akey, from, m, w, lane); }
+};
+struct LdPeer {                      // workgroups of this launch did, in front of a flag barrier (kp_rounds)
+    static __device__ __forceinline__ uint32_t ld(const uint32_t* p) { return xld(p); }
+    static __device__ __forceinline__ uint32_t ld16(const uint16_t* p) { return xld16(p); }
+    static __device__ __forceinline__ uint32_t scan_fit(const uint32_t* key, const uint32_t* bits, uint32_t akey, uint32_t from, uint32_t m,
+                                                        uint32_t w, int lane) { return w_scan_fit_x(key, bits, akey, from, m, w, lane); }
+};
+
+// The workgroup's (rating group, tile) under the batch's map (PairParams.xseg), and its place among the chain's
+// workgroups of its XCD (xj of xn; PK_NO / 0 on the plain grid).  false: a slot nobody walks.
+static __device__ __forceinline__ bool pair_wg_map(const PairParams& P, uint32_t& g, uint32_t& t, uint32_t& xj, uint32_t& xn)
+{
+    g = blockIdx.y; t = blockIdx.x;
+    xj = PK_NO; xn = 0;
+    if (!P.xslots) return true;
+    const uint32_t x = blockIdx.x & 7u;
+    uint32_t sl = blockIdx.x >> 3;
+    bool found = false;
+#pragma unroll
+    for (uint32_t k = 0; k < PK_XSEG; ++k) {
+        const uint32_t c = P.xcnt[x][k];
+        if (!found && sl < c) {
+            const uint32_t sg = P.xseg[x][k];
+            g = sg & 0xFFu;
+            t = ((sg >> 8) & 0xFFu) + sl * (sg >> 16);
+            xj = sl; xn = c;
+            found = true;
+        }
+        if (!found) sl -= c;
+    }
+    return found;
+}
+
+// Tile t of rating group g in a chain of m index positions (m, buf: what the host saw, from the kernel arguments).
+template <uint32_t TP>
+struct PairTile {
+    uint32_t m, buf, ntiles;
+    uint32_t base, tl, hl;           // first index; length of the tile; of the tile and its lookahead tile
+    uint32_t own_words, hwords;      // bitmap words of tl / of hl
+    size_t qo, po;                   // the chain's offset in the q_* arrays / the group's in the pair arrays
+    const uint32_t* key;
+    const uint32_t* oidx;
+    uint16_t* gnx;                   // next[] of the tile
+    __device__ __forceinline__ PairTile(const PairParams& P, uint32_t g, uint32_t t, uint32_t m_, uint32_t buf_)
+    {
+        m = m_; buf = buf_;
+        ntiles = (m + TP - 1u) / TP;
+        qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        po = (size_t)g * P.pstride;
+        base = t * TP;
+        tl = dev_min_u32(TP, m - base);
+        hl = dev_min_u32(2u * TP, m - base);
+        own_words = (tl + 31u) >> 5;
+        hwords = (hl + 31u) >> 5;
+        key = P.key[buf] + po;
+        oidx = P.oidx[buf] + po;
+        gnx = P.nx16[buf] + po + base;
+    }
+};
+
+// The chain's committed record as the state a batch starts from / a batch's last state back into the record.
+static __device__ __forceinline__ RoundState round_state_open(const PairChain* pc)
+{
+    RoundState S;
+    S.live = 1; S.done = 0; S.want_compact = 0; S.rounds = pc->rounds; S.a_oi = PK_NO;
+    S.qlen = pc->qlen; S.passes = pc->passes; S.n_out = pc->n_out; S.has_anchor = pc->has_anchor;
+    S.a_key = pc->a_key; S.a_slot = pc->a_slot; S.a_cons = pc->a_cons; S.a_team = pc->a_team;
+    S.a_rating = pc->a_rating; S.pairs = pc->pairs; S.scanned = pc->scanned;
+    S.pos0 = pc->pos0; S.changed0 = pc->changed0; S.extra0 = pc->extra0;
+    return S;
+}
+static __device__ __forceinline__ void round_state_commit(PairChain* pc, const RoundState& S)
+{
+    pc->qlen = S.qlen; pc->passes = S.passes; pc->n_out = S.n_out; pc->has_anchor = S.has_anchor;
+    pc->a_key = S.a_key; pc->a_slot = S.a_slot; pc->a_cons = S.a_cons; pc->a_team = S.a_team;
+    pc->a_rating = S.a_rating; pc->pairs = S.pairs; pc->scanned = S.scanned; pc->rounds = S.rounds;
+    pc->want_compact = S.want_compact;
+    pc->pos0 = S.pos0; pc->changed0 = S.changed0; pc->extra0 = S.extra0;
+}
+
+// The deferred lobby of a thread (section 2): two dependent loads per player (oidx -> q_slot) and four stores,
+// none of which anything in the launch waits for.  pass_apply issues the first loads, load() the second ones
+// (behind the repair), store() the stores (at the end) — the workgroup does not stand at a barrier for them.
+struct PassEmit {
+    uint32_t em_off = PK_NO, em_ia = 0, em_iq = 0, em_score = 0, em_sa = 0, em_sq = 0;     // a step of the in-tile path
+    uint32_t hd_off = PK_NO, hd_iq = 0, hd_score = 0, hd_sq = 0, hd_sa = 0, hd_team = 0;   // the head match (thread 0)
+    uint32_t pass = 0;
+    bool loaded = false;
+    __device__ __forceinline__ void load(const PairParams& P, size_t qo)
+    {
+        if (loaded) return;
+        loaded = true;
+        if (em_off != PK_NO) { em_sa = P.q_slot[qo + em_ia]; em_sq = P.q_slot[qo + em_iq]; }
+        if (hd_off != PK_NO) hd_sq = P.q_slot[qo + hd_iq];
+    }
+    __device__ __forceinline__ void store(const PairParams& P, uint32_t g, size_t qo)
+    {
+        load(P, qo);
+        uint32_t* const eos = P.out_slots + (size_t)g * P.out_slot_stride;
+        if (em_off != PK_NO) {
+            eos[2u * em_off] = em_sa; eos[2u * em_off + 1u] = em_sq;
+            P.out_score[(size_t)g * P.out_rec_stride + em_off] = (float)(int32_t)em_score;
+            P.out_pass[(size_t)g * P.out_rec_stride + em_off] = pass;
+        }
+        if (hd_off != PK_NO) {
+            eos[2u * hd_off + hd_team] = hd_sa; eos[2u * hd_off + (1u - hd_team)] = hd_sq;
+            P.out_score[(size_t)g * P.out_rec_stride + hd_off] = (float)(int32_t)hd_score;
+            P.out_pass[(size_t)g * P.out_rec_stride + hd_off] = pass;
+        }
+        em_off = PK_NO; hd_off = PK_NO;
+    }
+};
+
+// The walk's running state (wave 0, everything wave uniform).
+struct PairWalk {
+    uint32_t tt, x;                  // the cursor: tile, position in it
+    uint32_t k;                      // lobbies of the pass so far
+    bool have_r;                     // rpre is the REC at the cursor
+    uint32_t rpre;
+    uint32_t my_entry, my_off, my_disp, my_kill, my_head, my_hoff;   // the own tile's share of the route (s_my[0..5])
+    uint32_t has_anchor, a_key, a_team;                              // the open lobby behind the cursor
+    uint32_t a_oi;                   // the seated anchor's index in the q_* arrays (slot, rating, cons are fetched off the walk)
+    bool quiescent;
+    __device__ __forceinline__ PairWalk(const RoundState& S, uint32_t a_oi_)
+        : tt(0), x(S.pos0), k(0), have_r(false), rpre(0), my_entry(PK_NO), my_off(0), my_disp(DISP_NONE), my_kill(PK_NO),
+          my_head(0), my_hoff(0), has_anchor(S.has_anchor), a_key(S.a_key), a_team(S.a_team), a_oi(a_oi_), quiescent(false) {}
+    __device__ __forceinline__ void publish(uint32_t* s_my) const
+    {
+        s_my[0] = my_entry; s_my[1] = my_off; s_my[2] = my_disp; s_my[3] = my_kill; s_my[4] = my_head; s_my[5] = my_hoff;
+        s_my[6] = 0; s_my[7] = 0;
+    }
+};
+
+// Head match: the carried anchor's partner is the first tile's prepared first fit that exists (hp: one word per
+// tile).  `early`: hp0 is the word of this lane's tile among the first 64, loaded ahead.
+template <uint32_t TP, class Ld>
+static __device__ __forceinline__ void walk_head(PairWalk& W, const PairTile<TP>& G, uint32_t t, const uint32_t* hp, uint32_t n_out, int lane,
+                                                 bool early = false, uint32_t hp0 = PK_NO)
+{
+    if (!W.has_anchor) return;
+    uint32_t j = PK_NO;
+    for (uint32_t tb = 0; tb < G.ntiles && j == PK_NO; tb += 64u) {
+        const uint32_t v = early && tb == 0u ? hp0 : (tb + (uint32_t)lane < G.ntiles ? Ld::ld(hp + tb + lane) : PK_NO);
+        const unsigned long long b = __ballot(v != PK_NO);
+        if (b) j = lane_get(v, __ffsll(b) - 1);
+    }
+    if (j == PK_NO) W.quiescent = true;              // a pass without a change
+    else {
+        if (j / TP == t) { W.my_kill = j - G.base; W.my_head = 1; W.my_hoff = n_out; }
+        W.k = 1; W.has_anchor = 0;
+        W.tt = (j + 1u) / TP; W.x = (j + 1u) % TP;
+    }
+}
+
+// One hop of the walk from (W.tt < ntiles, W.x) that the fast paths did not take: a clean exit, an exit anchor
+// without a partner inside the horizon, with a partner that left in the pass before (rescan), or without any
+// until the end of the queue (it stays seated).  tmr: kp_rounds' timers of the slow kinds (PairChain.pslow).
+template <uint32_t TP, class Ld>
+static __device__ __forceinline__ void walk_general_hop(PairWalk& W, const PairParams& P, const PairTile<TP>& G, uint32_t t,
+                                                        const uint32_t* rec, const uint16_t* exa, const uint32_t* bits_src,
+                                                        uint32_t n_out, int lane, bool tmr, PairChain* pc)
+{
+    const uint32_t m = G.m, ntiles = G.ntiles, w = P.window;
+    const uint32_t tlt = dev_min_u32(TP, m - W.tt * TP);
+    if (W.x >= tlt) { ++W.tt; W.x = 0; W.have_r = false; return; }
+    const uint32_t rr = W.have_r ? W.rpre : uni(Ld::ld(rec + (size_t)W.tt * TP + W.x));
+    W.have_r = false;
+    const uint32_t kind = rr >> 30, cnt = (rr >> 17) & 0x1FFFu, land = rr & 0x1FFFFu;
+    const uint32_t t0 = W.tt, x0 = W.x;
+    if (t0 == t) { W.my_entry = x0; W.my_off = n_out + W.k; }
+    uint32_t d = DISP_NONE;
+    W.k += cnt;
+    if (kind == REC_CLEAN) { ++W.tt; W.x = 0; }
+    else {
+        uint32_t q = PK_NO, a = t0 * TP + land;              // exit anchor (FAR / NONE kinds)
+        if (kind == REC_PARTNER) {
+            q = t0 * TP + land - 1u;
+            // partner still queued at the start of this pass?  (and, meanwhile, the next REC)
+            const uint32_t t2 = (q + 1u) / TP, x2 = (q + 1u) % TP;
+            const uint32_t bw = Ld::ld(bits_src + (q >> 5));
+            const bool in2 = t2 < ntiles && x2 < dev_min_u32(TP, m - t2 * TP);
+            if (in2) W.rpre = Ld::ld(rec + (size_t)t2 * TP + x2);
+            if ((uni(bw) >> (q & 31u)) & 1u) { W.have_r = in2; W.rpre = uni(W.rpre); }
+            else {
+                const long long ts0 = tmr ? clock64() : 0;
+                a = t0 * TP + Ld::ld16(exa + (size_t)t0 * TP + x0);
+                q = uni(Ld::scan_fit(G.key, bits_src, G.key[a], q + 1u, m, w, lane));
+                if (tmr) { atomicAdd(&pc->pslow[0], 1u); atomicAdd(&pc->pslow[1], (uint32_t)((clock64() - ts0) >> 4)); }
+            }
+        } else if (kind == REC_FAR) {
+            const long long ts0 = tmr ? clock64() : 0;
+            q = uni(Ld::scan_fit(G.key, bits_src, G.key[a], (t0 + 2u) * TP, m, w, lane));
+            if (tmr) { atomicAdd(&pc->pslow[2], 1u); atomicAdd(&pc->pslow[3], (uint32_t)((clock64() - ts0) >> 4)); }
+        }
+        if (q != PK_NO) {
+            d = q;
+            W.k += 1u;
+            if (q / TP == t) W.my_kill = q - G.base;
+            W.tt = (q + 1u) / TP; W.x = (q + 1u) % TP;
+        } else {
+            // nobody fits until the end of the queue: the anchor stays in the lobby.  Its key is what every tile
+            // needs before the pass ends (the next pass's head partner); slot, rating and role / region are fetched
+            // off the critical path through a_oi (kp_round: tile 0 patches the record when the kernel ends;
+            // kp_rounds: whoever emits the anchor, or the epilogue)
+            d = DISP_SEATED;
+            W.has_anchor = 1;
+            tw_sload2_v(G.key + a, G.oidx + a, W.a_key, W.a_oi);
+            W.a_team = 0;
+            W.tt = ntiles;
+        }
+    }
+    if (t0 == t) W.my_disp = d;
+}
+
+// The chain's state behind the pass the walk W has just finished from state S (one lane).  a_oi: what becomes of
+// RoundState.a_oi when the pass changed the lobby.
+static __device__ __forceinline__ RoundState walk_close(const RoundState& S, const PairWalk& W, uint32_t m, uint32_t a_oi)
+{
+    RoundState N = S;
+    N.rounds = S.rounds + 1u;
+    N.passes = S.passes + 1u;
+    N.pos0 = 0; N.changed0 = 0; N.extra0 = 0;
+    N.pairs = S.pairs + S.qlen + S.extra0; N.scanned = S.scanned + S.qlen + S.extra0;
+    if (W.quiescent) {
+        // nobody fits the carried anchor: a pass without a change ends the tick — unless the
+        // change of this pass was its very first attempt (cancel tick, the head joined the
+        // stale lobby): then the next pass is the one without a change
+        if (!S.changed0) { N.done = 1; N.live = 0; }
+    } else {
+        const uint32_t seats = W.k - S.has_anchor + W.has_anchor;        // players that opened a lobby
+        N.pairs -= seats;
+        N.qlen = S.qlen - (W.k + seats);
+        N.n_out = S.n_out + W.k;
+        N.has_anchor = W.has_anchor; N.a_key = W.a_key; N.a_team = W.a_team; N.a_oi = a_oi;
+        if ((W.k + seats == 0u && !S.changed0) || N.qlen == 0u) { N.done = 1; N.live = 0; }
+        else if (N.qlen < PL_MAX || N.qlen * 4u < m * 3u) N.want_compact = 1;
+    }
+    return N;
+}
+
+// Section 2, the pass on the own tile (every thread; s_my[0..5] hold the walk's verdict on it): wave 0 collects
+// the in-tile path, then everybody takes its players out of the bitmap and the keys and notes its lobby in E.
+// S: the chain's state the pass started from; a_oi: S's anchor's q_* index where its slot has not been fetched
+// (PK_NO: S.a_slot is valid).  The caller's barrier ends the section.
+template <uint32_t TP>
+static __device__ __forceinline__ void pass_apply(const PairParams& P, const PairTile<TP>& G, uint32_t g, PairChain* pc,
+                                                  const RoundState& S, uint32_t a_oi, uint32_t* s_key, const uint16_t* s_nx,
+                                                  const uint16_t* s_g, uint32_t* s_bits, uint16_t* s_path, uint32_t* s_my,
+                                                  PassEmit& E, int tid, int lane, int wave)
+{
+    const uint32_t base = G.base, tl = G.tl;
+    const uint32_t my_entry = s_my[0], my_off = s_my[1], d = s_my[2], my_kill = s_my[3];
+    uint32_t* const os = P.out_slots + (size_t)g * P.out_slot_stride;
+    E.pass = S.passes;
+    if (wave == 0) {
+        uint32_t n = 0;
+        if (my_entry != PK_NO) {
+            const uint32_t a = uni(l_succ(s_bits, my_entry, tl, lane));
+            if (a != PK_NO) {
+                uint32_t x = a;
+                for (;;) {
+#pragma unroll
+                    for (uint32_t k = 0; k < 8u; ++k) {
+                        s_path[n + k] = (uint16_t)x;
+                        x = lds_ld16(s_g + x);
+                    }
+                    n += 8u;
+                    if (uni(x) == TP) break;
+                }
+                const uint32_t pv = (uint32_t)lane < 8u ? (uint32_t)s_path[n - 8u + (uint32_t)lane] : TP;
+                const unsigned long long parked = __ballot(pv == TP);
+                n = n - 8u + (parked ? (uint32_t)__ffsll(parked) - 1u : 8u);
+            }
+        }
+        if (lane == 0) s_my[6] = n;
+    }
+    __syncthreads();
+    const uint32_t n = s_my[6];
+    if (tid == 0 && my_kill != PK_NO) {                    // a partner that an earlier tile's anchor (or the
+        const uint32_t kj = s_key[my_kill] & ~PK_DEAD;     // carried anchor) found in this tile
+        atomicAnd(&s_bits[my_kill >> 5], ~(1u << (my_kill & 31u)));
+        atomicOr(&s_key[my_kill], PK_DEAD);
+        if (s_my[4]) {                                     // the head match is emitted here
+            const uint32_t ra = pk_rating(S.a_key), rj = pk_rating(kj);
+            E.hd_off = s_my[5];
+            E.hd_iq = G.oidx[base + my_kill];
+            E.hd_score = ra > rj ? ra - rj : rj - ra;
+            E.hd_team = S.a_team;
+            E.hd_sa = a_oi != PK_NO ? P.q_slot[G.qo + a_oi] : S.a_slot;
+        }
+    }
+    for (uint32_t i = tid; i < n; i += PT_THREADS) {
+        const uint32_t a = s_path[i];
+        const uint32_t o = s_nx[a];
+        const bool internal = o != NX_NONE && o != NX_FAR && a + o < tl;
+        const uint32_t ka = s_key[a] & ~PK_DEAD;
+        atomicAnd(&s_bits[a >> 5], ~(1u << (a & 31u)));
+        atomicOr(&s_key[a], PK_DEAD);
+        uint32_t qabs = PK_NO, kq = 0;
+        if (internal) {
+            const uint32_t j = a + o;
+            kq = s_key[j] & ~PK_DEAD;
+            atomicAnd(&s_bits[j >> 5], ~(1u << (j & 31u)));
+            atomicOr(&s_key[j], PK_DEAD);
+            qabs = base + j;
+        } else {
+            if (i + 1u != n || d == DISP_NONE) atomicOr(&pc->err, MM_ERRF_SEAT_INVARIANT);
+            if (d != DISP_SEATED && d != DISP_NONE) { qabs = d; kq = G.key[qabs]; }
+        }
+        if (qabs != PK_NO) {
+            const uint32_t ra = pk_rating(ka), rq = pk_rating(kq);
+            const uint32_t sc = ra > rq ? ra - rq : rq - ra;
+            if (i < PT_THREADS) {                          // the lobby of this step: the first loads now (PassEmit)
+                E.em_off = my_off + i;
+                E.em_ia = G.oidx[base + a];
+                E.em_iq = G.oidx[qabs];
+                E.em_score = sc;
+            } else {                                       // more than 1024 lobbies in one tile and pass: right away
+                os[2u * (my_off + i)] = P.q_slot[G.qo + G.oidx[base + a]];
+                os[2u * (my_off + i) + 1u] = P.q_slot[G.qo + G.oidx[qabs]];
+                P.out_score[(size_t)g * P.out_rec_stride + my_off + i] = (float)(int32_t)sc;
+                P.out_pass[(size_t)g * P.out_rec_stride + my_off + i] = S.passes;
+            }
+        }
+    }
+    if (tid == 0) {
+        if (n) {
+            const uint32_t a = s_path[n - 1u], o = s_nx[a];
+            const bool internal = o != NX_NONE && o != NX_FAR && a + o < tl;
+            if (internal && d != DISP_NONE) atomicOr(&pc->err, MM_ERRF_SEAT_INVARIANT);
+        } else if (d != DISP_NONE) atomicOr(&pc->err, MM_ERRF_SEAT_INVARIANT);
+    }
+}
+
+// The carried anchor's first fit inside the tile (the next pass starts from the head): its minimum into *best_min,
+// which holds PK_NO beforehand and is complete behind the workgroup's next barrier.
+static __device__ __forceinline__ void head_first_fit(const uint32_t* s_key, uint32_t a_key, uint32_t w, uint32_t tl, int tid, int lane,
+                                                      uint32_t* best_min)
+{
+    uint32_t klo, krng;
+    pk_bounds(a_key, w, klo, krng);
+    uint32_t best = PK_NO;
+    for (uint32_t i = tid; i < tl; i += PT_THREADS)
+        if (best == PK_NO && pk_in(s_key[i], klo, krng)) best = i;
+    const unsigned long long b = __ballot(best != PK_NO);
+    if (b) {
+        // lanes hold increasing i within a stride, the first lane with a hit holds the wave's minimum
+        // only within its own stride: take the true minimum
+        uint32_t v = best;
+        for (int dd = 1; dd < 64; dd <<= 1) { const uint32_t o2 = (uint32_t)__shfl((int)v, lane ^ dd); v = o2 < v ? o2 : v; }
+        if (lane == 0) atomicMin(best_min, v);
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// kp_round: the three launches of a round fused into ONE.  Every tile's workgroup
+//   1. walks the route of pass p itself (wave 0; the same deterministic walk in every
+//      workgroup, so nobody waits for anybody),
+//   2. applies pass p to its own tile (in-tile chain, bitmap, emission),
+//   3. prepares its tile for pass p+1.
+// Everything a workgroup reads from another one (REC, exit anchors, the bitmap at the start
+// of the pass, head partners, the chain's round state) was written by the PREVIOUS launch
+// into the buffers of the other parity, so there is no intra-launch communication at all.
+// The price: a tile sees its lookahead tile as it was one pass ago.  That only ever shows
+// too many queued players (a superset), so an exit anchor may point at a partner that has
+// just left the queue; the walk checks the partner against the pass-start bitmap and rescans
+// if so (rare: the partner must have been matched in exactly the previous pass).
+// `first`: the launch that opens a batch only prepares (there is no route yet).
+// ------------------------------------------------------------------------------------
 template <uint32_t TP>
 __global__ __launch_bounds__(PT_THREADS) void kp_round(PairParams P, uint32_t r, uint32_t first)
 {
@@ -1654,70 +2063,36 @@ __global__ __launch_bounds__(PT_THREADS) void kp_round(PairParams P, uint32_t r,
     __shared__ uint16_t s_nw[PK_T / 32 + 2];
     __shared__ uint16_t s_path[PK_T / 2 + 72];
     __shared__ RoundState s_N;
-    __shared__ uint32_t s_my[8];                 // entry, offset, disposition, incoming kill, head flag, head offset, n, kills
+    __shared__ uint32_t s_my[8];                 // entry, offset, disposition, incoming kill, head flag, head offset, n, -
 
-    uint32_t g = blockIdx.y, t = blockIdx.x;
-    uint32_t xj = PK_NO, xn = 0;                          // my place among the chain's workgroups of this XCD, and how many they are
-    if (P.xslots) {
-        const uint32_t x = blockIdx.x & 7u;
-        uint32_t sl = blockIdx.x >> 3;
-        bool found = false;
-#pragma unroll
-        for (uint32_t k = 0; k < PK_XSEG; ++k) {
-            const uint32_t c = P.xcnt[x][k];
-            if (!found && sl < c) {
-                const uint32_t sg = P.xseg[x][k];
-                g = sg & 0xFFu;
-                t = ((sg >> 8) & 0xFFu) + sl * (sg >> 16);
-                xj = sl; xn = c;
-                found = true;
-            }
-            if (!found) sl -= c;
-        }
-        if (!found) return;
-    }
+    uint32_t g, t, xj, xn;                       // xj of xn: my place among the chain's workgroups of this XCD
+    if (!pair_wg_map(P, g, t, xj, xn)) return;
     PairChain* const pc = P.pchains + g;
-    const uint32_t m = P.bm[g], buf = P.bbuf[g];          // from the kernel arguments: no load in front of the tile's loads
-    if (m == 0u || t >= (m + PK_T - 1u) / PK_T) return;
+    const uint32_t bm = P.bm[g];                 // from the kernel arguments: no load in front of the tile's loads
+    if (bm == 0u || t >= (bm + PK_T - 1u) / PK_T) return;
+    const PairTile<TP> G(P, g, t, bm, P.bbuf[g]);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t cpar = r & 1u, npar = cpar ^ 1u;
-    const uint32_t w = P.window, ntiles = (m + PK_T - 1u) / PK_T;
-    const uint32_t c = P.mode * P.n_groups + g;
-    const size_t qo = (size_t)c * P.capacity, po = (size_t)g * P.pstride;
-    const uint32_t base = t * PK_T;
-    const uint32_t tl = dev_min_u32(PK_T, m - base);
-    const uint32_t hl = dev_min_u32(2u * PK_T, m - base);
-    const uint32_t* const key = P.key[buf] + po;
-    const uint32_t* const oidx = P.oidx[buf] + po;
-    uint16_t* const gnx = P.nx16[buf] + po + base;
-    const uint32_t* const bits_src = (first ? P.bits[buf] : P.bitsp[cpar]) + (size_t)g * P.bits_stride;
+    const uint32_t w = P.window;
+    const uint32_t* const bits_src = (first ? P.bits[G.buf] : P.bitsp[cpar]) + (size_t)g * P.bits_stride;
     uint32_t* const bits_dst = P.bitsp[npar] + (size_t)g * P.bits_stride;
-    const uint32_t own_words = (tl + 31u) >> 5;
 
-    RoundState S;
-    if (first) {
-        S.live = 1; S.done = 0; S.want_compact = 0; S.rounds = pc->rounds; S.a_oi = PK_NO;
-        S.qlen = pc->qlen; S.passes = pc->passes; S.n_out = pc->n_out; S.has_anchor = pc->has_anchor;
-        S.a_key = pc->a_key; S.a_slot = pc->a_slot; S.a_cons = pc->a_cons; S.a_team = pc->a_team;
-        S.a_rating = pc->a_rating; S.pairs = pc->pairs; S.scanned = pc->scanned;
-        S.pos0 = pc->pos0; S.changed0 = pc->changed0; S.extra0 = pc->extra0;
-    } else S = pc->rs[cpar];
+    const RoundState S = first ? round_state_open(pc) : pc->rs[cpar];
     // The tile's own state is asked for before anything of the round state is looked at (the two come from
     // HBM side by side instead of one after the other).
     long long tq = clock64();
     // the walk's first load (where the carried anchor finds its partner, one word per tile) is in flight while the
     // tile's own state comes in
     uint32_t hp0 = PK_NO;
-    if (!first && wave == 0 && (uint32_t)lane < ntiles) hp0 = P.headp[cpar][(size_t)g * P.max_tiles + (uint32_t)lane];
-    const uint32_t hwords = (hl + 31u) >> 5;
-    for (uint32_t i = tid; i < 2u * PK_T / 32u + 4u; i += PT_THREADS) s_bits[i] = i < hwords ? bits_src[(base >> 5) + i] : 0u;
-    copy_words_x4((uint32_t*)s_nx, (const uint32_t*)gnx, (tl + 1u) >> 1, tid, PT_THREADS);
-    if (!first) copy_words_x4((uint32_t*)s_g, (const uint32_t*)(P.g16 + po + base), (tl + 1u) >> 1, tid, PT_THREADS);
+    if (!first && wave == 0 && (uint32_t)lane < G.ntiles) hp0 = P.headp[cpar][(size_t)g * P.max_tiles + (uint32_t)lane];
+    for (uint32_t i = tid; i < 2u * PK_T / 32u + 4u; i += PT_THREADS) s_bits[i] = i < G.hwords ? bits_src[(G.base >> 5) + i] : 0u;
+    copy_words_x4((uint32_t*)s_nx, (const uint32_t*)G.gnx, (G.tl + 1u) >> 1, tid, PT_THREADS);
+    if (!first) copy_words_x4((uint32_t*)s_g, (const uint32_t*)(P.g16 + G.po + G.base), (G.tl + 1u) >> 1, tid, PT_THREADS);
     if (tid == 0) { s_cnt[1] = 0; s_cnt[2] = 0; s_cnt[3] = 0; s_cnt[4] = 0; }   // long list, list, cursor; staging waves done
     if ((uint32_t)tid < RP_MAXLONG) s_pc[RP_MAXLONG + tid] = PK_NO;      // repair_long's result slots
     __syncthreads();
     if (!S.live) {                               // ended earlier in this batch: keep both parities equal
-        for (uint32_t i = tid; i < own_words; i += PT_THREADS) bits_dst[(base >> 5) + i] = s_bits[i];
+        for (uint32_t i = tid; i < G.own_words; i += PT_THREADS) bits_dst[(G.base >> 5) + i] = s_bits[i];
         if (t == 0 && tid == 0) pc->rs[npar] = S;
         return;
     }
@@ -1730,27 +2105,10 @@ __global__ __launch_bounds__(PT_THREADS) void kp_round(PairParams P, uint32_t r,
     if (tid == 0) s_N = S;
     TMARK(0);
 
-    // deferred emission of this thread (kp_round section 2): lobby offset, the two players' q_* indices, score
-    uint32_t em_off = PK_NO, em_ia = 0, em_iq = 0, em_score = 0, hd_off = PK_NO, hd_iq = 0, hd_score = 0;
-    uint32_t em_sa = 0, em_sq = 0, hd_sq = 0;
+    PassEmit E;                                  // this thread's lobby of section 2
     uint32_t tst = 0;                            // diagnostics: candidates this wave tested (MM_PAIR_TUNE bit 13)
     uint32_t seat_oi = PK_NO, seat_slot = 0, seat_cons = 0;   // the anchor this pass leaves seated: its q_* index and values
     int32_t seat_rating = 0;
-    bool em_loaded = false;
-#define EMIT_LOAD() do { if (!em_loaded) { em_loaded = true;                                                   \
-        if (em_off != PK_NO) { em_sa = P.q_slot[qo + em_ia]; em_sq = P.q_slot[qo + em_iq]; }                  \
-        if (hd_off != PK_NO) hd_sq = P.q_slot[qo + hd_iq]; } } while (0)
-#define EMIT_STORE() do { EMIT_LOAD();                                                                         \
-        uint32_t* const eos = P.out_slots + (size_t)g * P.out_slot_stride;                                    \
-        if (em_off != PK_NO) {                                                                                \
-            eos[2u * em_off] = em_sa; eos[2u * em_off + 1u] = em_sq;                                          \
-            P.out_score[(size_t)g * P.out_rec_stride + em_off] = (float)(int32_t)em_score;                    \
-            P.out_pass[(size_t)g * P.out_rec_stride + em_off] = S.passes; }                                   \
-        if (hd_off != PK_NO) {                                                                                \
-            eos[2u * hd_off + S.a_team] = S.a_slot; eos[2u * hd_off + (1u - S.a_team)] = hd_sq;               \
-            P.out_score[(size_t)g * P.out_rec_stride + hd_off] = (float)(int32_t)hd_score;                    \
-            P.out_pass[(size_t)g * P.out_rec_stride + hd_off] = S.passes; }                                   \
-        em_off = PK_NO; hd_off = PK_NO; } while (0)
     if (!first) {
         // ================= 1. the route of pass p (MATCH_CHECK.md §4), wave 0 =================
         // meanwhile the other fifteen waves stage the keys (dead flags as of the start of the pass;
@@ -1771,8 +2129,8 @@ __global__ __launch_bounds__(PT_THREADS) void kp_round(PairParams P, uint32_t r,
             constexpr uint32_t PF_ENT = PK_T < 2816u ? PK_T : 2816u;                 // REC entries per tile
             constexpr uint32_t PF_Q = PF_ENT / 4u + PK_T / 128u;                     // 16-byte pieces per tile: REC + bitmap words
             // this workgroup's share: one of the chain's workgroups on this XCD
-            const uint32_t R = xn ? xn : (ntiles >> 3 ? ntiles >> 3 : 1u), myr = xn ? xj : (t >> 3) % R;
-            const uint4* const rec4 = (const uint4*)(P.rec2[cpar] + po);
+            const uint32_t R = xn ? xn : (G.ntiles >> 3 ? G.ntiles >> 3 : 1u), myr = xn ? xj : (t >> 3) % R;
+            const uint4* const rec4 = (const uint4*)(P.rec2[cpar] + G.po);
             const uint4* const bit4 = (const uint4*)bits_src;
 #pragma unroll
             for (uint32_t u = 0; u < PF_N; ++u) {
@@ -1780,15 +2138,15 @@ __global__ __launch_bounds__(PT_THREADS) void kp_round(PairParams P, uint32_t r,
                 const uint32_t tj = myr + (wk / PF_Q) * R, c = wk % PF_Q;
                 // (no more than this workgroup's fair share of the chain's tiles: with the chain on one XCD that is two or
                 // three tiles, not the seven the loads could cover — what another workgroup of the XCD pulls is in the L2 too)
-                if (tj < ntiles && wk / PF_Q < (ntiles + R - 1u) / R) {
+                if (tj < G.ntiles && wk / PF_Q < (G.ntiles + R - 1u) / R) {
                     if (c < PF_ENT / 4u) {
-                        if (tj * PK_T + c * 4u < m) pf[u] = rec4[(tj * PK_T) / 4u + c];
-                    } else if ((tj * PK_T) / 32u + (c - PF_ENT / 4u) * 4u < (m + 31u) / 32u) pf[u] = bit4[(tj * PK_T) / 128u + (c - PF_ENT / 4u)];
+                        if (tj * PK_T + c * 4u < G.m) pf[u] = rec4[(tj * PK_T) / 4u + c];
+                    } else if ((tj * PK_T) / 32u + (c - PF_ENT / 4u) * 4u < (G.m + 31u) / 32u) pf[u] = bit4[(tj * PK_T) / 128u + (c - PF_ENT / 4u)];
                 }
             }
         }
-        if (wave > PW_WAVES) {
-            prep_stage_keys<PK_T>(s_key, s_bits, key + base, hl, tid - 64 * (1 + PW_WAVES), PT_THREADS - 64 * (1 + PW_WAVES));
+        if (wave != 0) {
+            prep_stage_keys<PK_T>(s_key, s_bits, G.key + G.base, G.hl, tid - 64, PT_THREADS - 64);
 #pragma unroll
             for (uint32_t u = 0; u < PF_N; ++u) TW_SINK(pf[u].x);                    // the loads above are wanted in the cache only
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");        // this wave's keys are in LDS ...
@@ -1796,49 +2154,26 @@ __global__ __launch_bounds__(PT_THREADS) void kp_round(PairParams P, uint32_t r,
             if (lane == 0) atomicAdd(&s_cnt[4], 1u);                      // ... before it says so
         }
         if (wave != 0 && !(P.tune & 0x4000u)) {
-            // While wave 0 walks: the first repair sweep.  The keys are staged by waves PW_WAVES + 1 .. 15;
+            // While wave 0 walks: the first repair sweep.  The keys are staged by waves 1 .. 15;
             // everybody here waits for them (wave 0 cannot join a barrier now), then repairs the players whose
             // partner had left the queue when this pass began.  What the sweep writes stays valid through the
             // pass: it only replaces a departed partner by the next fit that is still queued NOW — if the pass
             // takes that one too, the second sweep sees it.  Anchors on this pass's path keep their next[]: an
             // in-tile partner is queued by construction, an exit anchor's is looked up by the walk itself.
-            while (lds_ld(&s_cnt[4]) < (uint32_t)(PT_THREADS / 64 - 1 - PW_WAVES)) __builtin_amdgcn_s_sleep(1);
+            while (lds_ld(&s_cnt[4]) < (uint32_t)(PT_THREADS / 64 - 1)) __builtin_amdgcn_s_sleep(1);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            repair_sweep<PK_T>(s_key, s_nx, s_pc, &s_cnt[1], s_pc + 2u * RP_MAXLONG + (uint32_t)wave * RP_TODO, bits_src + (base >> 5),
-                         tl, hl, base + hl == m, w, lane, (uint32_t)wave - 1u, PT_THREADS / 64u - 1u, tst);
+            repair_sweep<PK_T>(s_key, s_nx, s_pc, &s_cnt[1], s_pc + 2u * RP_MAXLONG + (uint32_t)wave * RP_TODO, bits_src + (G.base >> 5),
+                         G.tl, G.hl, G.base + G.hl == G.m, w, lane, (uint32_t)wave - 1u, PT_THREADS / 64u - 1u, tst);
         }
         if (wave == 0) {
             // the walk is the one serial piece of the round: it must not queue for issue slots behind the three
             // waves that share its SIMD and are staging / sweeping meanwhile
             __builtin_amdgcn_s_setprio(3);
-            const uint32_t* const rec = P.rec2[cpar] + po;
-            const uint16_t* const exa = P.exa[cpar] + po;
-            uint32_t qlen = S.qlen, n_out = S.n_out, has_anchor = S.has_anchor;
-            uint32_t a_key = S.a_key, a_slot = S.a_slot, a_cons = S.a_cons, a_team = S.a_team;
-            int32_t a_rating = S.a_rating;
-            unsigned long long pairs = S.pairs + qlen + S.extra0, scanned = S.scanned + qlen + S.extra0;
-            const uint32_t o_start = has_anchor;
-            uint32_t k = 0, tt = 0, x = S.pos0;
-            uint32_t my_entry = PK_NO, my_off = 0, my_disp = DISP_NONE, my_kill = PK_NO, my_head = 0, my_hoff = 0;
-            bool quiescent = false;
-            if (has_anchor) {
-                // head match: the first tile whose prepared local first fit exists
-                const uint32_t* const hp = P.headp[cpar] + (size_t)g * P.max_tiles;
-                uint32_t j = PK_NO;
-                for (uint32_t tb = 0; tb < ntiles && j == PK_NO; tb += 64u) {
-                    const uint32_t v = tb == 0u ? hp0 : (tb + (uint32_t)lane < ntiles ? hp[tb + lane] : PK_NO);
-                    const unsigned long long b = __ballot(v != PK_NO);
-                    if (b) j = lane_get(v, __ffsll(b) - 1);
-                }
-                if (j == PK_NO) quiescent = true;            // a pass without a change
-                else {
-                    if (j / PK_T == t) { my_kill = j - base; my_head = 1; my_hoff = n_out; }
-                    k = 1; has_anchor = 0;
-                    tt = (j + 1u) / PK_T; x = (j + 1u) % PK_T;
-                }
-            }
-            bool have_r = false;
-            uint32_t rpre = 0;
+            const uint32_t* const rec = P.rec2[cpar] + G.po;
+            const uint16_t* const exa = P.exa[cpar] + G.po;
+            const uint32_t m = G.m, base = G.base, n_out = S.n_out;
+            PairWalk W(S, PK_NO);
+            walk_head<TP, LdLaunch>(W, G, t, P.headp[cpar] + (size_t)g * P.max_tiles, n_out, lane, true, hp0);
             const long long tw0 = (P.tune & 0x2000u) ? clock64() : 0;
             uint32_t dbg_hops = 0, dbg_ghops = 0, dbg_gtry = 0, dbg_gstale = 0, gskip = PK_NO;
             bool to_group = false;
@@ -1847,7 +2182,7 @@ __global__ __launch_bounds__(PT_THREADS) void kp_round(PairParams P, uint32_t r,
             const bool grp_on = TP == PK_TMAX && P.grp != 0u;
             long long th0 = tw0;
             uint32_t dbg_early = 0, dbg_late = 0;
-            while (!quiescent && tt < ntiles) {
+            while (!W.quiescent && W.tt < G.ntiles) {
                 if (P.tune & 0x2000u) {
                     const long long now = clock64();
                     if (dbg_hops) { if (dbg_hops <= 4u) dbg_early += (uint32_t)(now - th0); else dbg_late += (uint32_t)(now - th0); }
@@ -1857,98 +2192,56 @@ __global__ __launch_bounds__(PT_THREADS) void kp_round(PairParams P, uint32_t r,
                 // Second level (long chains, kp_group): the cursor stands in the first tile of a group this tile
                 // does not belong to — one hop to where the walk goes on behind the group (or where, inside it, the
                 // general code has to look: then the entry says "here", and the hop below is the ordinary one).
-                if (grp_on && tt * PK_T + x != gskip) {
-                    const uint32_t gr = tt / PK_GS;
-                    if (gr != t / PK_GS && tt == gr * PK_GS) {
-                        const uint4* const ge = P.grec + (size_t)g * P.gstride + (size_t)gr * PK_T + x;
+                if (grp_on && W.tt * PK_T + W.x != gskip) {
+                    const uint32_t gr = W.tt / PK_GS;
+                    if (gr != t / PK_GS && W.tt == gr * PK_GS) {
+                        const uint4* const ge = P.grec + (size_t)g * P.gstride + (size_t)gr * PK_T + W.x;
                         uint32_t gp, gc, gq, gs;
                         tw_sload4_v((const uint32_t*)ge, gp, gc, gq, gs);
                         ++dbg_gtry;
                         if (gs != r) ++dbg_gstale;
-                        if (gs == r && gp != tt * PK_T + x) {
+                        if (gs == r && gp != W.tt * PK_T + W.x) {
                             ++dbg_ghops;
-                            k += gc;
-                            if (gq != PK_NO && gq / PK_T == t) my_kill = gq - base;
-                            tt = gp / PK_T;
-                            x = gp % PK_T;
-                            have_r = false;
+                            W.k += gc;
+                            if (gq != PK_NO && gq / PK_T == t) W.my_kill = gq - base;
+                            W.tt = gp / PK_T;
+                            W.x = gp % PK_T;
+                            W.have_r = false;
                             continue;
                         }
-                        gskip = tt * PK_T + x;       // not an entry of this round (or it says "here"): tile by tile from here
+                        gskip = W.tt * PK_T + W.x;   // not an entry of this round (or it says "here"): tile by tile from here
                     }
                 }
                 // Fast path — almost every hop: the tile's REC says "exit anchor with a partner" and the partner
                 // is still queued.  Everything is wave uniform and kept scalar; one round trip to memory per
                 // hop (the partner's bitmap word and the next REC together).  Anything else (a clean exit, no
                 // partner inside the horizon, a partner that left in the pass before) falls through to the
-                // general code below, which redoes the hop from the same state.
-                if (have_r) {
+                // general hop below, which redoes the hop from the same state.
+                if (W.have_r) {
                     // the loop carries the cursor's absolute position and the REC there in scalar registers, nothing else
-                    uint32_t p = tt * PK_T + x, rr = rpre;
+                    uint32_t p = W.tt * PK_T + W.x, rr = W.rpre;
                     while ((rr >> 30) == REC_PARTNER) {
                         const uint32_t tb = p & ~(PK_T - 1u);
                         // (the first tile of somebody else's group: back to the top, there is a hop over the whole group)
                         if (grp_on && (tb / PK_T) % PK_GS == 0u && tb / (PK_T * PK_GS) != t / PK_GS && p != gskip) { to_group = true; break; }
                         const uint32_t q = tb + (rr & 0x1FFFFu) - 1u, nxt = q + 1u;
-                        if (nxt >= m) break;                                          // the end of the queue: the general code
+                        if (nxt >= m) break;                                          // the end of the queue: the general hop
                         uint32_t bw, r2;
                         tw_sload2(bits_src + (q >> 5), rec + nxt, bw, r2);             // through the scalar cache: the shorter path
                         if (!((bw >> (q & 31u)) & 1u)) break;
-                        if (tb == base) { my_entry = p - base; my_off = n_out + k; my_disp = q; }
-                        k += ((rr >> 17) & 0x1FFFu) + 1u;
-                        if ((q & ~(PK_T - 1u)) == base) my_kill = q - base;
+                        if (tb == base) { W.my_entry = p - base; W.my_off = n_out + W.k; W.my_disp = q; }
+                        W.k += ((rr >> 17) & 0x1FFFu) + 1u;
+                        if ((q & ~(PK_T - 1u)) == base) W.my_kill = q - base;
                         p = nxt;
                         rr = r2;
                     }
-                    tt = p / PK_T;
-                    x = p % PK_T;
-                    rpre = rr;
+                    W.tt = p / PK_T;
+                    W.x = p % PK_T;
+                    W.rpre = rr;
                 }
-                if (tt >= ntiles) break;
+                if (W.tt >= G.ntiles) break;
                 if (to_group) { to_group = false; continue; }
-                const uint32_t tlt = dev_min_u32(PK_T, m - tt * PK_T);
-                if (x >= tlt) { ++tt; x = 0; have_r = false; continue; }
-                const uint32_t rr = have_r ? rpre : uni(rec[(size_t)tt * PK_T + x]);
-                have_r = false;
-                const uint32_t kind = rr >> 30, cnt = (rr >> 17) & 0x1FFFu, land = rr & 0x1FFFFu;
-                const uint32_t t0 = tt, x0 = x;
-                if (t0 == t) { my_entry = x0; my_off = n_out + k; }
-                uint32_t d = DISP_NONE;
-                k += cnt;
-                if (kind == REC_CLEAN) { ++tt; x = 0; }
-                else {
-                    uint32_t q = PK_NO, a = t0 * PK_T + land;              // exit anchor (FAR / NONE kinds)
-                    if (kind == REC_PARTNER) {
-                        q = t0 * PK_T + land - 1u;
-                        // partner still queued at the start of this pass?  (and, meanwhile, the next REC)
-                        const uint32_t t2 = (q + 1u) / PK_T, x2 = (q + 1u) % PK_T;
-                        const uint32_t bw = bits_src[q >> 5];
-                        const bool in2 = t2 < ntiles && x2 < dev_min_u32(PK_T, m - t2 * PK_T);
-                        if (in2) rpre = rec[(size_t)t2 * PK_T + x2];
-                        if ((uni(bw) >> (q & 31u)) & 1u) { have_r = in2; rpre = uni(rpre); }
-                        else {
-                            a = t0 * PK_T + (uint32_t)exa[(size_t)t0 * PK_T + x0];
-                            q = uni(w_scan_fit(key, bits_src, key[a], q + 1u, m, w, lane));
-                        }
-                    } else if (kind == REC_FAR) q = uni(w_scan_fit(key, bits_src, key[a], (t0 + 2u) * PK_T, m, w, lane));
-                    if (q != PK_NO) {
-                        d = q;
-                        k += 1u;
-                        if (q / PK_T == t) my_kill = q - base;
-                        tt = (q + 1u) / PK_T; x = (q + 1u) % PK_T;
-                    } else {
-                        // nobody fits until the end of the queue: the anchor stays in the lobby
-                        d = DISP_SEATED;
-                        has_anchor = 1;
-                        // its key is wanted by every tile before the launch ends (the next pass's head partner);
-                        // slot, rating and role / region only in the chain's record in HBM: tile 0 fetches them
-                        // off the critical path and patches the record when the kernel ends
-                        tw_sload2_v(key + a, oidx + a, a_key, seat_oi);
-                        a_team = 0;
-                        tt = ntiles;
-                    }
-                }
-                if (t0 == t) my_disp = d;
+                walk_general_hop<TP, LdLaunch>(W, P, G, t, rec, exa, bits_src, n_out, lane, false, pc);
             }
             __builtin_amdgcn_s_setprio(0);
             if ((P.tune & 0x2000u) && tmr) {
@@ -1958,122 +2251,16 @@ __global__ __launch_bounds__(PT_THREADS) void kp_round(PairParams P, uint32_t r,
                 atomicAdd(&pc->tm[14], dbg_late >> 4);
             }
             if (lane == 0 && t == 0u && dbg_gtry) { atomicAdd(&pc->ghops, dbg_ghops); atomicAdd(&pc->gtry, dbg_gtry); atomicAdd(&pc->gstale, dbg_gstale); }
+            seat_oi = W.a_oi;
             if (lane == 0) {
-                RoundState N = S;
-                N.rounds = S.rounds + 1u;
-                N.passes = S.passes + 1u;
-                N.pos0 = 0; N.changed0 = 0; N.extra0 = 0;
-                N.pairs = pairs; N.scanned = scanned;
-                if (quiescent) {
-                    // nobody fits the carried anchor: a pass without a change ends the tick — unless the
-                    // change of this pass was its very first attempt (cancel tick, the head joined the
-                    // stale lobby): then the next pass is the one without a change
-                    if (!S.changed0) { N.done = 1; N.live = 0; }
-                } else {
-                    const uint32_t seats = k - o_start + has_anchor;        // players that opened a lobby
-                    N.pairs = pairs - seats;
-                    N.qlen = qlen - (k + seats);
-                    N.n_out = n_out + k;
-                    N.has_anchor = has_anchor; N.a_key = a_key; N.a_slot = a_slot; N.a_cons = a_cons;
-                    N.a_team = a_team; N.a_rating = a_rating;
-                    if ((k + seats == 0u && !S.changed0) || N.qlen == 0u) { N.done = 1; N.live = 0; }
-                    else if (N.qlen < PL_MAX || N.qlen * 4u < m * 3u) N.want_compact = 1;
-                }
-                s_N = N;
-                s_my[0] = my_entry; s_my[1] = my_off; s_my[2] = my_disp; s_my[3] = my_kill; s_my[4] = my_head; s_my[5] = my_hoff;
-                s_my[6] = 0; s_my[7] = 0;
+                s_N = walk_close(S, W, m, S.a_oi);
+                W.publish(s_my);
             }
         }
         __syncthreads();
         TMARK(6);
         // ================= 2. pass p on the own tile =================
-        const uint32_t my_entry = s_my[0], my_off = s_my[1], d = s_my[2], my_kill = s_my[3];
-        uint32_t* const os = P.out_slots + (size_t)g * P.out_slot_stride;
-        if (wave == 0) {
-            uint32_t n = 0;
-            if (my_entry != PK_NO) {
-                const uint32_t a = uni(l_succ(s_bits, my_entry, tl, lane));
-                if (a != PK_NO) {
-                    uint32_t x = a;
-                    for (;;) {
-#pragma unroll
-                        for (uint32_t k = 0; k < 8u; ++k) {
-                            s_path[n + k] = (uint16_t)x;
-                            x = lds_ld16(s_g + x);
-                        }
-                        n += 8u;
-                        if (uni(x) == PK_T) break;
-                    }
-                    const uint32_t pv = (uint32_t)lane < 8u ? (uint32_t)s_path[n - 8u + (uint32_t)lane] : PK_T;
-                    const unsigned long long parked = __ballot(pv == PK_T);
-                    n = n - 8u + (parked ? (uint32_t)__ffsll(parked) - 1u : 8u);
-                }
-            }
-            if (lane == 0) s_my[6] = n;
-        }
-        __syncthreads();
-        const uint32_t n = s_my[6];
-        uint32_t kills = 0;
-        if (tid == 0 && my_kill != PK_NO) {                    // a partner that an earlier tile's anchor (or the
-            const uint32_t kj = s_key[my_kill] & ~PK_DEAD;     // carried anchor) found in this tile
-            atomicAnd(&s_bits[my_kill >> 5], ~(1u << (my_kill & 31u)));
-            atomicOr(&s_key[my_kill], PK_DEAD);
-            ++kills;
-            if (s_my[4]) {                                     // the head match is emitted here (stores: end of the kernel)
-                const uint32_t ra = pk_rating(S.a_key), rj = pk_rating(kj);
-                hd_off = s_my[5];
-                hd_iq = oidx[base + my_kill];
-                hd_score = ra > rj ? ra - rj : rj - ra;
-            }
-        }
-        for (uint32_t i = tid; i < n; i += PT_THREADS) {
-            const uint32_t a = s_path[i];
-            const uint32_t o = s_nx[a];
-            const bool internal = o != NX_NONE && o != NX_FAR && a + o < tl;
-            const uint32_t ka = s_key[a] & ~PK_DEAD;
-            atomicAnd(&s_bits[a >> 5], ~(1u << (a & 31u)));
-            atomicOr(&s_key[a], PK_DEAD);
-            ++kills;
-            uint32_t qabs = PK_NO, kq = 0;
-            if (internal) {
-                const uint32_t j = a + o;
-                kq = s_key[j] & ~PK_DEAD;
-                atomicAnd(&s_bits[j >> 5], ~(1u << (j & 31u)));
-                atomicOr(&s_key[j], PK_DEAD);
-                ++kills;
-                qabs = base + j;
-            } else {
-                if (i + 1u != n || d == DISP_NONE) atomicOr(&pc->err, MM_ERRF_SEAT_INVARIANT);
-                if (d != DISP_SEATED && d != DISP_NONE) { qabs = d; kq = key[qabs]; }
-            }
-            if (qabs != PK_NO) {
-                const uint32_t ra = pk_rating(ka), rq = pk_rating(kq);
-                const uint32_t sc = ra > rq ? ra - rq : rq - ra;
-                if (i < PT_THREADS) {
-                    // The lobby of this step: two dependent loads per player (oidx -> q_slot) and four stores,
-                    // none of which anything in this launch waits for.  Issue the first loads now, the second
-                    // ones after the repair, the stores at the end — the workgroup does not stand at the next
-                    // barrier for them.
-                    em_off = my_off + i;
-                    em_ia = oidx[base + a];
-                    em_iq = oidx[qabs];
-                    em_score = sc;
-                } else {                                       // more than 1024 lobbies in one tile and pass: right away
-                    os[2u * (my_off + i)] = P.q_slot[qo + oidx[base + a]];
-                    os[2u * (my_off + i) + 1u] = P.q_slot[qo + oidx[qabs]];
-                    P.out_score[(size_t)g * P.out_rec_stride + my_off + i] = (float)(int32_t)sc;
-                    P.out_pass[(size_t)g * P.out_rec_stride + my_off + i] = S.passes;
-                }
-            }
-        }
-        if (tid == 0) {
-            if (n) {
-                const uint32_t a = s_path[n - 1u], o = s_nx[a];
-                const bool internal = o != NX_NONE && o != NX_FAR && a + o < tl;
-                if (internal && d != DISP_NONE) atomicOr(&pc->err, MM_ERRF_SEAT_INVARIANT);
-            } else if (d != DISP_NONE) atomicOr(&pc->err, MM_ERRF_SEAT_INVARIANT);
-        }
-        (void)kills;
+        pass_apply<TP>(P, G, g, pc, S, PK_NO, s_key, s_nx, s_g, s_bits, s_path, s_my, E, tid, lane, wave);
         __syncthreads();
         TMARK(9);
     } else __syncthreads();
@@ -2084,58 +2271,41 @@ __global__ __launch_bounds__(PT_THREADS) void kp_round(PairParams P, uint32_t r,
     if (t == 0 && tid == 0) {
         pc->rs[npar] = s_N;
         if (seat_oi != PK_NO) {                  // loads now, the three stores at the end (SEAT_PATCH)
-            seat_slot = P.q_slot[qo + seat_oi];
-            seat_rating = P.q_rating[qo + seat_oi];
-            seat_cons = P.q_cons[qo + seat_oi];
+            seat_slot = P.q_slot[G.qo + seat_oi];
+            seat_rating = P.q_rating[G.qo + seat_oi];
+            seat_cons = P.q_cons[G.qo + seat_oi];
         }
     }
 #define SEAT_PATCH() do { if (t == 0 && tid == 0 && seat_oi != PK_NO) {                                          \
         pc->rs[npar].a_slot = seat_slot; pc->rs[npar].a_rating = seat_rating; pc->rs[npar].a_cons = seat_cons; } } while (0)
-    for (uint32_t i = tid; i < own_words; i += PT_THREADS) bits_dst[(base >> 5) + i] = s_bits[i];
-    if (!N.live) { EMIT_STORE(); SEAT_PATCH(); return; }
+    for (uint32_t i = tid; i < G.own_words; i += PT_THREADS) bits_dst[(G.base >> 5) + i] = s_bits[i];
+    if (!N.live) { E.store(P, g, G.qo); SEAT_PATCH(); return; }
 
     // ================= 3. the own tile for pass p + 1 =================
     if (first) {
-        prep_stage_keys<PK_T>(s_key, s_bits, key + base, hl, tid);
+        prep_stage_keys<PK_T>(s_key, s_bits, G.key + G.base, G.hl, tid);
         __syncthreads();
     }
-    prep_repair<PK_T>(s_key, s_nx, s_pc, &s_cnt[1], bits_src + (base >> 5), tl, hl, base + hl == m, w, tid, tst,
+    prep_repair<PK_T>(s_key, s_nx, s_pc, &s_cnt[1], bits_src + (G.base >> 5), G.tl, G.hl, G.base + G.hl == G.m, w, tid, tst,
                       tmr && !(P.tune & 0x2000u) ? pc->tm : nullptr);
-    EMIT_LOAD();                                 // the oidx loads of section 2 have long arrived
-    prep_tables<PK_T>(s_key, s_nx, s_bits, s_nw, s_pc, P.g16 + po + base, P.rec2[npar] + po + base, P.exa[npar] + po + base,
-                gnx, tl, tid, tmr ? pc->tm : nullptr);
+    E.load(P, G.qo);                             // the oidx loads of section 2 have long arrived
+    prep_tables<PK_T>(s_key, s_nx, s_bits, s_nw, s_pc, P.g16 + G.po + G.base, P.rec2[npar] + G.po + G.base, P.exa[npar] + G.po + G.base,
+                G.gnx, G.tl, tid, tmr ? pc->tm : nullptr);
     TMARK(3);
     __syncthreads();                             // every node of s_pc is final: the samples below read other threads' nodes
-    // the carried anchor's first fit inside this tile (the next pass starts from the head)
     if (tid == 0) s_cnt[0] = PK_NO;
     __syncthreads();
-    if (N.has_anchor) {
-        uint32_t klo, krng;
-        pk_bounds(N.a_key, w, klo, krng);
-        uint32_t best = PK_NO;
-        for (uint32_t i = tid; i < tl; i += PT_THREADS)
-            if (best == PK_NO && pk_in(s_key[i], klo, krng)) best = i;
-        const unsigned long long b = __ballot(best != PK_NO);
-        if (b) {
-            // lanes hold increasing i within a stride, the first lane with a hit holds the wave's minimum
-            // only within its own stride: take the true minimum
-            uint32_t v = best;
-            for (int dd = 1; dd < 64; dd <<= 1) { const uint32_t o2 = (uint32_t)__shfl((int)v, lane ^ dd); v = o2 < v ? o2 : v; }
-            if (lane == 0) atomicMin(&s_cnt[0], v);
-        }
-    }
+    if (N.has_anchor) head_first_fit(s_key, N.a_key, w, G.tl, tid, lane, &s_cnt[0]);
     __syncthreads();
-    if (tid == 0) P.headp[npar][(size_t)g * P.max_tiles + t] = s_cnt[0] == PK_NO ? PK_NO : base + s_cnt[0];
-    EMIT_STORE();
+    if (tid == 0) P.headp[npar][(size_t)g * P.max_tiles + t] = s_cnt[0] == PK_NO ? PK_NO : G.base + s_cnt[0];
+    E.store(P, g, G.qo);
     SEAT_PATCH();
     if ((P.tune & 0x2000u) && lane == 0) {          // + the carried anchor's scan of the tile (one test per position)
-        const unsigned long long all = (unsigned long long)tst + (wave == 0 && N.has_anchor ? tl : 0u);
+        const unsigned long long all = (unsigned long long)tst + (wave == 0 && N.has_anchor ? G.tl : 0u);
         if (all) atomicAdd(&pc->tested, all);
     }
     TMARK(4);
 #undef TMARK
-#undef EMIT_LOAD
-#undef EMIT_STORE
 #undef SEAT_PATCH
 }
 
@@ -2188,32 +2358,6 @@ struct RoundsRes {
     uint32_t tm[16];                 // diagnostics (tile 1)
 };
 
-// Wave-wide, like w_scan_fit, on a bitmap other workgroups of this launch have written.
-static __device__ __forceinline__ uint32_t w_scan_fit_x(const uint32_t* key, const uint32_t* bits, uint32_t akey, uint32_t from, uint32_t m,
-                                                        uint32_t w, int lane)
-{
-    uint32_t klo, krng;
-    pk_bounds(akey, w, klo, krng);
-    // four 64-candidate steps per trip to memory, bitmap words and keys side by side (round 5: one step a trip, the key
-    // behind its bitmap word — 5.4k cycles for each of the ~50 hops a tick whose partner has just left, on every tile's walker)
-    for (uint32_t p = from; p < m; p += 256u) {
-        uint32_t bw[4], kv[4];
-#pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) {
-            const uint32_t c = p + 64u * u + (uint32_t)lane;
-            bw[u] = c < m ? xld(bits + (c >> 5)) : 0u;
-            kv[u] = c < m ? key[c] : 0xFFFFFFFFu;
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) {
-            const uint32_t c = p + 64u * u + (uint32_t)lane;
-            const unsigned long long b = __ballot(((bw[u] >> (c & 31u)) & 1u) != 0u && pk_in(kv[u], klo, krng));
-            if (b) return p + 64u * u + (uint32_t)__ffsll(b) - 1u;
-        }
-    }
-    return PK_NO;
-}
-
 template <uint32_t TP>
 __global__ __launch_bounds__(PT_THREADS) void kp_rounds(PairParams P, uint32_t it_begin, uint32_t it_end, uint32_t K)
 {
@@ -2230,39 +2374,15 @@ __global__ __launch_bounds__(PT_THREADS) void kp_rounds(PairParams P, uint32_t i
     uint16_t* const s_path = L.path;
     uint32_t* const s_my = L.my;
 
-    uint32_t g = blockIdx.y, t = blockIdx.x;
-    if (P.xslots) {
-        const uint32_t x = blockIdx.x & 7u;
-        uint32_t sl = blockIdx.x >> 3;
-        bool found = false;
-#pragma unroll
-        for (uint32_t k = 0; k < PK_XSEG; ++k) {
-            const uint32_t c = P.xcnt[x][k];
-            if (!found && sl < c) {
-                const uint32_t sg = P.xseg[x][k];
-                g = sg & 0xFFu;
-                t = ((sg >> 8) & 0xFFu) + sl * (sg >> 16);
-                found = true;
-            }
-            if (!found) sl -= c;
-        }
-        if (!found) return;
-    }
+    uint32_t g, t, xj, xn;
+    if (!pair_wg_map(P, g, t, xj, xn)) return;
     PairChain* const pc = P.pchains + g;
-    const uint32_t m = P.bm[g], buf = P.bbuf[g];
-    if (m == 0u || t >= (m + PK_T - 1u) / PK_T) return;
+    const uint32_t bm = P.bm[g];
+    if (bm == 0u || t >= (bm + PK_T - 1u) / PK_T) return;
+    const PairTile<TP> G(P, g, t, bm, P.bbuf[g]);
     const int tid_o = threadIdx.x;
-    const uint32_t w = P.window, ntiles = (m + PK_T - 1u) / PK_T;
-    const uint32_t c = P.mode * P.n_groups + g;
-    const size_t qo = (size_t)c * P.capacity, po = (size_t)g * P.pstride;
-    const uint32_t base = t * PK_T;
-    const uint32_t tl = dev_min_u32(PK_T, m - base);
-    const uint32_t hl = dev_min_u32(2u * PK_T, m - base);
-    const uint32_t* const key = P.key[buf] + po;
-    const uint32_t* const oidx = P.oidx[buf] + po;
-    uint16_t* const gnx = P.nx16[buf] + po + base;
-    uint32_t* const bits_com = P.bits[buf] + (size_t)g * P.bits_stride;      // the committed bitmap
-    const uint32_t own_words = (tl + 31u) >> 5, hwords = (hl + 31u) >> 5;
+    const uint32_t w = P.window;
+    uint32_t* const bits_com = P.bits[G.buf] + (size_t)g * P.bits_stride;      // the committed bitmap
     unsigned long long* const bar = P.pbar + g;
     long long tq = clock64();
 #define TMARK(K_) do { if (tmr) { const long long now = clock64(); L.tm[K_] += (uint32_t)(now - tq); tq = now; } } while (0)
@@ -2272,24 +2392,19 @@ __global__ __launch_bounds__(PT_THREADS) void kp_rounds(PairParams P, uint32_t i
         const int tid = tid_o;
         MM_RESIDENT_FRESH(L);
         if (tid == 0) {
-            RoundState S;
-            S.live = 1; S.done = 0; S.want_compact = 0; S.rounds = pc->rounds;
-            S.qlen = pc->qlen; S.passes = pc->passes; S.n_out = pc->n_out; S.has_anchor = pc->has_anchor;
-            S.a_key = pc->a_key; S.a_slot = pc->a_slot; S.a_cons = pc->a_cons; S.a_team = pc->a_team;
-            S.a_rating = pc->a_rating; S.pairs = pc->pairs; S.scanned = pc->scanned;
-            S.pos0 = pc->pos0; S.changed0 = pc->changed0; S.extra0 = pc->extra0; S.a_oi = PK_NO;
+            const RoundState S = round_state_open(pc);
             L.S = S;
             L.N = S;
             L.ctl[0] = 0; L.ctl[1] = 0; L.ctl[2] = 0;
             for (int k = 0; k < 16; ++k) L.tm[k] = 0;
         }
-        for (uint32_t i = tid; i < 2u * PK_T / 32u + 4u; i += PT_THREADS) s_bits[i] = i < hwords ? bits_com[(base >> 5) + i] : 0u;
-        copy_words_x4((uint32_t*)s_nx, (const uint32_t*)gnx, (tl + 1u) >> 1, tid, PT_THREADS);
+        for (uint32_t i = tid; i < 2u * PK_T / 32u + 4u; i += PT_THREADS) s_bits[i] = i < G.hwords ? bits_com[(G.base >> 5) + i] : 0u;
+        copy_words_x4((uint32_t*)s_nx, (const uint32_t*)G.gnx, (G.tl + 1u) >> 1, tid, PT_THREADS);
         if (tid < 8) s_g[PK_T + tid] = (uint16_t)PK_T;
         if (tid == 0) { s_cnt[1] = 0; s_cnt[2] = 0; s_cnt[3] = 0; s_cnt[4] = 0; }   // long list, list, cursor (prep_repair)
         if ((uint32_t)tid < RP_MAXLONG) s_pc[RP_MAXLONG + tid] = PK_NO;              // repair_long's result slots
         __syncthreads();
-        prep_stage_keys<PK_T>(s_key, s_bits, key + base, hl, tid);
+        prep_stage_keys<PK_T>(s_key, s_bits, G.key + G.base, G.hl, tid);
         __syncthreads();
     } else if (L.ctl[0]) return;                 // (shim launches: this chain has been committed already)
 
@@ -2308,30 +2423,13 @@ __global__ __launch_bounds__(PT_THREADS) void kp_rounds(PairParams P, uint32_t i
         const uint32_t cpar = it & 1u, npar = cpar ^ 1u;
         const uint32_t* const bits_src = P.bitsp[cpar] + (size_t)g * P.bits_stride;
         uint32_t* const bits_dst = P.bitsp[npar] + (size_t)g * P.bits_stride;
-        // deferred emission of this thread (as in kp_round, section 2)
-        uint32_t em_off = PK_NO, em_ia = 0, em_iq = 0, em_score = 0, hd_off = PK_NO, hd_iq = 0, hd_score = 0;
-        uint32_t em_sa = 0, em_sq = 0, hd_sq = 0, hd_sa = 0, hd_team = 0, em_pass = 0;
-        bool em_loaded = false;
-#define EMIT_LOAD() do { if (!em_loaded) { em_loaded = true;                                                   \
-        if (em_off != PK_NO) { em_sa = P.q_slot[qo + em_ia]; em_sq = P.q_slot[qo + em_iq]; }                  \
-        if (hd_off != PK_NO) hd_sq = P.q_slot[qo + hd_iq]; } } while (0)
-#define EMIT_STORE() do { EMIT_LOAD();                                                                         \
-        uint32_t* const eos = P.out_slots + (size_t)g * P.out_slot_stride;                                    \
-        if (em_off != PK_NO) {                                                                                \
-            eos[2u * em_off] = em_sa; eos[2u * em_off + 1u] = em_sq;                                          \
-            P.out_score[(size_t)g * P.out_rec_stride + em_off] = (float)(int32_t)em_score;                    \
-            P.out_pass[(size_t)g * P.out_rec_stride + em_off] = em_pass; }                                    \
-        if (hd_off != PK_NO) {                                                                                \
-            eos[2u * hd_off + hd_team] = hd_sa; eos[2u * hd_off + (1u - hd_team)] = hd_sq;                    \
-            P.out_score[(size_t)g * P.out_rec_stride + hd_off] = (float)(int32_t)hd_score;                    \
-            P.out_pass[(size_t)g * P.out_rec_stride + hd_off] = em_pass; }                                    \
-        em_off = PK_NO; hd_off = PK_NO; } while (0)
+        PassEmit E;                              // this thread's lobby of section 2
 
         if (it > 0u) {
             // ================= 0. everybody's tables of iteration it - 1 are out =================
             if (tid == 0) {
                 uint32_t verdict = 0;
-                const unsigned long long need = (unsigned long long)ntiles * it;
+                const unsigned long long need = (unsigned long long)G.ntiles * it;
                 const long long t0 = wall_clock64();
                 const long long limit = it == 1u ? (long long)P.ptimeout0 : (long long)P.ptimeout1;
                 for (;;) {
@@ -2366,14 +2464,13 @@ __global__ __launch_bounds__(PT_THREADS) void kp_rounds(PairParams P, uint32_t i
             TMARK(0);
             if (tid == 0 && (P.tune & 0x10000u)) dw0 = clock64();             // (diagnostics: this tile's pass begins)
             const RoundState S = L.S;
-            em_pass = S.passes;
             // ================= 1. the route of the pass (wave 0) beside the first repair sweep =================
             if (wave != 0) {
                 // The lookahead tile as its workgroup left it: who is gone there since the last look gets the dead flag.  Only
                 // the sweep needs that, not the walk: the fifteen waves do it among themselves (a counter in LDS is their
                 // rendezvous; wave 0 is on its way already).
-                for (uint32_t i = PK_T / 32u + (uint32_t)tid - 64u; i < hwords; i += PT_THREADS - 64u) {
-                    const uint32_t nw_ = xld(bits_src + (base >> 5) + i);
+                for (uint32_t i = PK_T / 32u + (uint32_t)tid - 64u; i < G.hwords; i += PT_THREADS - 64u) {
+                    const uint32_t nw_ = xld(bits_src + (G.base >> 5) + i);
                     uint32_t gone = s_bits[i] & ~nw_;
                     s_bits[i] = nw_;
                     while (gone) {
@@ -2391,230 +2488,65 @@ __global__ __launch_bounds__(PT_THREADS) void kp_rounds(PairParams P, uint32_t i
                 // (no sweep in the batch's last iteration: what it puts on the long list is only finished by the prepare step,
                 // and there is none behind the last pass — the next batch's first prepare finds the same departures)
                 if (it != K && !(P.tune & 0x4000u))
-                    repair_sweep<PK_T>(s_key, s_nx, s_pc, &s_cnt[1], s_pc + 2u * RP_MAXLONG + (uint32_t)wave * RP_TODO, bits_src + (base >> 5),
-                                       tl, hl, base + hl == m, w, lane, (uint32_t)wave - 1u, PT_THREADS / 64u - 1u, tst);
+                    repair_sweep<PK_T>(s_key, s_nx, s_pc, &s_cnt[1], s_pc + 2u * RP_MAXLONG + (uint32_t)wave * RP_TODO, bits_src + (G.base >> 5),
+                                       G.tl, G.hl, G.base + G.hl == G.m, w, lane, (uint32_t)wave - 1u, PT_THREADS / 64u - 1u, tst);
             }
             if (wave == 0) {
                 __builtin_amdgcn_s_setprio(3);
-                const uint32_t* const rec = P.rec2[cpar] + po;
-                const uint16_t* const exa = P.exa[cpar] + po;
-                uint32_t qlen = S.qlen, n_out = S.n_out, has_anchor = S.has_anchor;
-                uint32_t a_key = S.a_key, a_slot = S.a_slot, a_cons = S.a_cons, a_team = S.a_team, a_oi = S.a_oi;
-                int32_t a_rating = S.a_rating;
-                unsigned long long pairs = S.pairs + qlen + S.extra0, scanned = S.scanned + qlen + S.extra0;
-                const uint32_t o_start = has_anchor;
-                uint32_t k = 0, tt = 0, x = S.pos0;
-                uint32_t my_entry = PK_NO, my_off = 0, my_disp = DISP_NONE, my_kill = PK_NO, my_head = 0, my_hoff = 0;
-                bool quiescent = false;
-                if (has_anchor) {
-                    // head match: the first tile whose prepared local first fit exists
-                    const uint32_t* const hp = P.headp[cpar] + (size_t)g * P.max_tiles;
-                    uint32_t j = PK_NO;
-                    for (uint32_t tb = 0; tb < ntiles && j == PK_NO; tb += 64u) {
-                        const uint32_t v = tb + (uint32_t)lane < ntiles ? xld(hp + tb + lane) : PK_NO;
-                        const unsigned long long b = __ballot(v != PK_NO);
-                        if (b) j = lane_get(v, __ffsll(b) - 1);
-                    }
-                    if (j == PK_NO) quiescent = true;            // a pass without a change
-                    else {
-                        if (j / PK_T == t) { my_kill = j - base; my_head = 1; my_hoff = n_out; }
-                        k = 1; has_anchor = 0;
-                        tt = (j + 1u) / PK_T; x = (j + 1u) % PK_T;
-                    }
-                }
-                bool have_r = false;
-                uint32_t rpre = 0;
+                const uint32_t* const rec = P.rec2[cpar] + G.po;
+                const uint16_t* const exa = P.exa[cpar] + G.po;
+                const uint32_t m = G.m, base = G.base, n_out = S.n_out;
+                PairWalk W(S, S.a_oi);
+                walk_head<TP, LdPeer>(W, G, t, P.headp[cpar] + (size_t)g * P.max_tiles, n_out, lane);
                 uint32_t dbg_hops = 0;
                 const long long tw0 = tmr ? clock64() : 0;
-                while (!quiescent && tt < ntiles) {
+                while (!W.quiescent && W.tt < G.ntiles) {
                     ++dbg_hops;
                     // Fast path (kp_round's, minus the second route level): exit anchor with a partner that is still
                     // queued — one round trip through the scalar cache per hop
-                    if (have_r) {
-                        uint32_t p = tt * PK_T + x, rr = rpre;
+                    if (W.have_r) {
+                        uint32_t p = W.tt * PK_T + W.x, rr = W.rpre;
                         // a hop whose partner lies in front of the own tile, or whose anchor lies behind it, concerns nobody here:
                         // the tight loop (mm_gfx950.h); the hops in between keep the own tile's books
                         const uint32_t p_in = p;
                         const long long th0 = tmr ? clock64() : 0;
-                        tw_hops(tw_sptr(bits_src), tw_sptr(rec), m, ~(PK_T - 1u), base, p, rr, k);
+                        tw_hops(tw_sptr(bits_src), tw_sptr(rec), m, ~(PK_T - 1u), base, p, rr, W.k);
                         while ((rr >> 30) == REC_PARTNER) {
                             const uint32_t tb = p & ~(PK_T - 1u);
                             if (tb > base) break;
                             const uint32_t q = tb + (rr & 0x1FFFFu) - 1u, nxt = q + 1u;
-                            if (nxt >= m) break;                                          // the end of the queue: the general code
+                            if (nxt >= m) break;                                          // the end of the queue: the general hop
                             uint32_t bw, r2;
                             tw_sload2(bits_src + (q >> 5), rec + nxt, bw, r2);
                             if (!((bw >> (q & 31u)) & 1u)) break;
-                            if (tb == base) { my_entry = p - base; my_off = n_out + k; my_disp = q; }
-                            k += ((rr >> 17) & 0x1FFFu) + 1u;
-                            if ((q & ~(PK_T - 1u)) == base) my_kill = q - base;
+                            if (tb == base) { W.my_entry = p - base; W.my_off = n_out + W.k; W.my_disp = q; }
+                            W.k += ((rr >> 17) & 0x1FFFu) + 1u;
+                            if ((q & ~(PK_T - 1u)) == base) W.my_kill = q - base;
                             p = nxt;
                             rr = r2;
                         }
-                        tw_hops(tw_sptr(bits_src), tw_sptr(rec), m, ~(PK_T - 1u), 0xFFFFFFFFu, p, rr, k);
+                        tw_hops(tw_sptr(bits_src), tw_sptr(rec), m, ~(PK_T - 1u), 0xFFFFFFFFu, p, rr, W.k);
                         dbg_hops += p / PK_T - p_in / PK_T;                            // (diagnostics: a fast hop advances a tile)
                         if (tmr) L.tm[3] += (uint32_t)(clock64() - th0);               // ... and the fast hops' cycles
-                        tt = p / PK_T;
-                        x = p % PK_T;
-                        rpre = rr;
+                        W.tt = p / PK_T;
+                        W.x = p % PK_T;
+                        W.rpre = rr;
                     }
-                    if (tt >= ntiles) break;
-                    const uint32_t tlt = dev_min_u32(PK_T, m - tt * PK_T);
-                    if (x >= tlt) { ++tt; x = 0; have_r = false; continue; }
-                    const uint32_t rr = have_r ? rpre : uni(xld(rec + (size_t)tt * PK_T + x));
-                    have_r = false;
-                    const uint32_t kind = rr >> 30, cnt = (rr >> 17) & 0x1FFFu, land = rr & 0x1FFFFu;
-                    const uint32_t t0 = tt, x0 = x;
-                    if (t0 == t) { my_entry = x0; my_off = n_out + k; }
-                    uint32_t d = DISP_NONE;
-                    k += cnt;
-                    if (kind == REC_CLEAN) { ++tt; x = 0; }
-                    else {
-                        uint32_t q = PK_NO, a = t0 * PK_T + land;              // exit anchor (FAR / NONE kinds)
-                        if (kind == REC_PARTNER) {
-                            q = t0 * PK_T + land - 1u;
-                            // partner still queued at the start of this pass?  (and, meanwhile, the next REC)
-                            const uint32_t t2 = (q + 1u) / PK_T, x2 = (q + 1u) % PK_T;
-                            const uint32_t bw = xld(bits_src + (q >> 5));
-                            const bool in2 = t2 < ntiles && x2 < dev_min_u32(PK_T, m - t2 * PK_T);
-                            if (in2) rpre = xld(rec + (size_t)t2 * PK_T + x2);
-                            if ((uni(bw) >> (q & 31u)) & 1u) { have_r = in2; rpre = uni(rpre); }
-                            else {
-                                const long long ts0 = tmr ? clock64() : 0;
-                                a = t0 * PK_T + xld16(exa + (size_t)t0 * PK_T + x0);
-                                q = uni(w_scan_fit_x(key, bits_src, key[a], q + 1u, m, w, lane));
-                                if (tmr) { atomicAdd(&pc->pslow[0], 1u); atomicAdd(&pc->pslow[1], (uint32_t)((clock64() - ts0) >> 4)); }
-                            }
-                        } else if (kind == REC_FAR) {
-                            const long long ts0 = tmr ? clock64() : 0;
-                            q = uni(w_scan_fit_x(key, bits_src, key[a], (t0 + 2u) * PK_T, m, w, lane));
-                            if (tmr) { atomicAdd(&pc->pslow[2], 1u); atomicAdd(&pc->pslow[3], (uint32_t)((clock64() - ts0) >> 4)); }
-                        }
-                        if (q != PK_NO) {
-                            d = q;
-                            k += 1u;
-                            if (q / PK_T == t) my_kill = q - base;
-                            tt = (q + 1u) / PK_T; x = (q + 1u) % PK_T;
-                        } else {
-                            // nobody fits until the end of the queue: the anchor stays in the lobby.  Its key is what every
-                            // tile needs (the next pass's head partner); slot, rating and role / region are fetched by
-                            // whoever emits it, or by the epilogue (a_oi)
-                            d = DISP_SEATED;
-                            has_anchor = 1;
-                            tw_sload2_v(key + a, oidx + a, a_key, a_oi);
-                            a_team = 0;
-                            tt = ntiles;
-                        }
-                    }
-                    if (t0 == t) my_disp = d;
+                    if (W.tt >= G.ntiles) break;
+                    walk_general_hop<TP, LdPeer>(W, P, G, t, rec, exa, bits_src, n_out, lane, tmr, pc);
                 }
                 __builtin_amdgcn_s_setprio(0);
                 if (tmr) { L.tm[13] += (uint32_t)((clock64() - tw0) >> 4); L.tm[15] += dbg_hops; }
                 if (lane == 0) {
-                    RoundState N = S;
-                    N.rounds = S.rounds + 1u;
-                    N.passes = S.passes + 1u;
-                    N.pos0 = 0; N.changed0 = 0; N.extra0 = 0;
-                    N.pairs = pairs; N.scanned = scanned;
-                    if (quiescent) {
-                        if (!S.changed0) { N.done = 1; N.live = 0; }
-                    } else {
-                        const uint32_t seats = k - o_start + has_anchor;        // players that opened a lobby
-                        N.pairs = pairs - seats;
-                        N.qlen = qlen - (k + seats);
-                        N.n_out = n_out + k;
-                        N.has_anchor = has_anchor; N.a_key = a_key; N.a_slot = a_slot; N.a_cons = a_cons;
-                        N.a_team = a_team; N.a_rating = a_rating; N.a_oi = has_anchor ? a_oi : PK_NO;
-                        if ((k + seats == 0u && !S.changed0) || N.qlen == 0u) { N.done = 1; N.live = 0; }
-                        else if (N.qlen < PL_MAX || N.qlen * 4u < m * 3u) N.want_compact = 1;
-                    }
-                    L.N = N;
-                    s_my[0] = my_entry; s_my[1] = my_off; s_my[2] = my_disp; s_my[3] = my_kill; s_my[4] = my_head; s_my[5] = my_hoff;
-                    s_my[6] = 0; s_my[7] = 0;
+                    L.N = walk_close(S, W, m, W.has_anchor ? W.a_oi : PK_NO);
+                    W.publish(s_my);
                 }
             }
             __syncthreads();
             TMARK(6);
             // ================= 2. the pass on the own tile =================
-            const uint32_t my_entry = s_my[0], my_off = s_my[1], d = s_my[2], my_kill = s_my[3];
-            uint32_t* const os = P.out_slots + (size_t)g * P.out_slot_stride;
-            if (wave == 0) {
-                uint32_t n = 0;
-                if (my_entry != PK_NO) {
-                    const uint32_t a = uni(l_succ(s_bits, my_entry, tl, lane));
-                    if (a != PK_NO) {
-                        uint32_t x = a;
-                        for (;;) {
-#pragma unroll
-                            for (uint32_t k = 0; k < 8u; ++k) {
-                                s_path[n + k] = (uint16_t)x;
-                                x = lds_ld16(s_g + x);
-                            }
-                            n += 8u;
-                            if (uni(x) == PK_T) break;
-                        }
-                        const uint32_t pv = (uint32_t)lane < 8u ? (uint32_t)s_path[n - 8u + (uint32_t)lane] : PK_T;
-                        const unsigned long long parked = __ballot(pv == PK_T);
-                        n = n - 8u + (parked ? (uint32_t)__ffsll(parked) - 1u : 8u);
-                    }
-                }
-                if (lane == 0) s_my[6] = n;
-            }
-            __syncthreads();
-            const uint32_t n = s_my[6];
-            if (tid == 0 && my_kill != PK_NO) {                    // a partner that an earlier tile's anchor (or the
-                const uint32_t kj = s_key[my_kill] & ~PK_DEAD;     // carried anchor) found in this tile
-                atomicAnd(&s_bits[my_kill >> 5], ~(1u << (my_kill & 31u)));
-                atomicOr(&s_key[my_kill], PK_DEAD);
-                if (s_my[4]) {                                     // the head match is emitted here (stores: end of the iteration)
-                    const uint32_t ra = pk_rating(S.a_key), rj = pk_rating(kj);
-                    hd_off = s_my[5];
-                    hd_iq = oidx[base + my_kill];
-                    hd_score = ra > rj ? ra - rj : rj - ra;
-                    hd_team = S.a_team;
-                    hd_sa = S.a_oi != PK_NO ? P.q_slot[qo + S.a_oi] : S.a_slot;
-                }
-            }
-            for (uint32_t i = tid; i < n; i += PT_THREADS) {
-                const uint32_t a = s_path[i];
-                const uint32_t o = s_nx[a];
-                const bool internal = o != NX_NONE && o != NX_FAR && a + o < tl;
-                const uint32_t ka = s_key[a] & ~PK_DEAD;
-                atomicAnd(&s_bits[a >> 5], ~(1u << (a & 31u)));
-                atomicOr(&s_key[a], PK_DEAD);
-                uint32_t qabs = PK_NO, kq = 0;
-                if (internal) {
-                    const uint32_t j = a + o;
-                    kq = s_key[j] & ~PK_DEAD;
-                    atomicAnd(&s_bits[j >> 5], ~(1u << (j & 31u)));
-                    atomicOr(&s_key[j], PK_DEAD);
-                    qabs = base + j;
-                } else {
-                    if (i + 1u != n || d == DISP_NONE) atomicOr(&pc->err, MM_ERRF_SEAT_INVARIANT);
-                    if (d != DISP_SEATED && d != DISP_NONE) { qabs = d; kq = key[qabs]; }
-                }
-                if (qabs != PK_NO) {
-                    const uint32_t ra = pk_rating(ka), rq = pk_rating(kq);
-                    const uint32_t sc = ra > rq ? ra - rq : rq - ra;
-                    if (i < PT_THREADS) {
-                        em_off = my_off + i;
-                        em_ia = oidx[base + a];
-                        em_iq = oidx[qabs];
-                        em_score = sc;
-                    } else {                                       // more than 1024 lobbies in one tile and pass: right away
-                        os[2u * (my_off + i)] = P.q_slot[qo + oidx[base + a]];
-                        os[2u * (my_off + i) + 1u] = P.q_slot[qo + oidx[qabs]];
-                        P.out_score[(size_t)g * P.out_rec_stride + my_off + i] = (float)(int32_t)sc;
-                        P.out_pass[(size_t)g * P.out_rec_stride + my_off + i] = em_pass;
-                    }
-                }
-            }
+            pass_apply<TP>(P, G, g, pc, S, S.a_oi, s_key, s_nx, s_g, s_bits, s_path, s_my, E, tid, lane, wave);
             if (tid == 0) {
-                if (n) {
-                    const uint32_t a = s_path[n - 1u], o = s_nx[a];
-                    const bool internal = o != NX_NONE && o != NX_FAR && a + o < tl;
-                    if (internal && d != DISP_NONE) atomicOr(&pc->err, MM_ERRF_SEAT_INVARIANT);
-                } else if (d != DISP_NONE) atomicOr(&pc->err, MM_ERRF_SEAT_INVARIANT);
                 L.S = L.N;                       // the pass is in the tile: from here on the chain's state is the new one
                 L.ctl[2] += 1u;
             }
@@ -2624,39 +2556,26 @@ __global__ __launch_bounds__(PT_THREADS) void kp_rounds(PairParams P, uint32_t i
         // what everybody needs of the state behind the pass
         struct { uint32_t live, has_anchor, a_key; } N;
         N.live = L.S.live; N.has_anchor = L.S.has_anchor; N.a_key = L.S.a_key;
-        if (!N.live || it == K) { EMIT_STORE(); ended = true; break; }       // the chain's tick is over / the batch is: no tables for nobody
+        if (!N.live || it == K) { E.store(P, g, G.qo); ended = true; break; }       // the chain's tick is over / the batch is: no tables for nobody
         if (it > 0u && L.S.qlen <= P.pyq[g]) {
             // every workgroup of the chain sees the same queue length behind the same pass: they all leave here, and the
             // other chains are asked to (they find the word at their next barrier)
             if (t == 0u && tid == 0) __hip_atomic_store(P.pyield, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            EMIT_STORE(); ended = true; break;
+            E.store(P, g, G.qo); ended = true; break;
         }
 
         // ================= 3. the own tile for the next pass =================
-        for (uint32_t i = tid; i < own_words; i += PT_THREADS) bits_dst[(base >> 5) + i] = s_bits[i];
+        for (uint32_t i = tid; i < G.own_words; i += PT_THREADS) bits_dst[(G.base >> 5) + i] = s_bits[i];
         if (tid == 0) { s_cnt[0] = PK_NO; s_cnt[4] = 0; }                    // (the head scan's minimum; the next pass's rendezvous)
-        prep_repair<PK_T>(s_key, s_nx, s_pc, &s_cnt[1], bits_src + (base >> 5), tl, hl, base + hl == m, w, tid, tst,
+        prep_repair<PK_T>(s_key, s_nx, s_pc, &s_cnt[1], bits_src + (G.base >> 5), G.tl, G.hl, G.base + G.hl == G.m, w, tid, tst,
                           tmr ? L.tm : nullptr);
-        EMIT_LOAD();
-        // the carried anchor's first fit inside this tile (the next pass starts from the head); the minimum is complete
-        // behind the barriers inside prep_tables
-        if (N.has_anchor) {
-            uint32_t klo, krng;
-            pk_bounds(N.a_key, w, klo, krng);
-            uint32_t best = PK_NO;
-            for (uint32_t i = tid; i < tl; i += PT_THREADS)
-                if (best == PK_NO && pk_in(s_key[i], klo, krng)) best = i;
-            const unsigned long long b = __ballot(best != PK_NO);
-            if (b) {
-                uint32_t v = best;
-                for (int dd = 1; dd < 64; dd <<= 1) { const uint32_t o2 = (uint32_t)__shfl((int)v, lane ^ dd); v = o2 < v ? o2 : v; }
-                if (lane == 0) atomicMin(&s_cnt[0], v);
-            }
-        }
-        prep_tables<PK_T>(s_key, s_nx, s_bits, s_nw, s_pc, s_g, P.rec2[npar] + po + base, P.exa[npar] + po + base,
-                          nullptr, tl, tid, tmr ? L.tm : nullptr);
+        E.load(P, G.qo);
+        // (the head scan's minimum is complete behind the barriers inside prep_tables)
+        if (N.has_anchor) head_first_fit(s_key, N.a_key, w, G.tl, tid, lane, &s_cnt[0]);
+        prep_tables<PK_T>(s_key, s_nx, s_bits, s_nw, s_pc, s_g, P.rec2[npar] + G.po + G.base, P.exa[npar] + G.po + G.base,
+                          nullptr, G.tl, tid, tmr ? L.tm : nullptr);
         if (tmr) tq = clock64();
-        if (tid == 0) P.headp[npar][(size_t)g * P.max_tiles + t] = s_cnt[0] == PK_NO ? PK_NO : base + s_cnt[0];
+        if (tid == 0) P.headp[npar][(size_t)g * P.max_tiles + t] = s_cnt[0] == PK_NO ? PK_NO : G.base + s_cnt[0];
         {
             // Read back what the tile has just published, a word per 64 bytes of REC and of the bitmap: a STORE does not leave
             // its line in the L2 (whoever loads it next goes to memory: 460-480 cycles a dependent load, whichever XCD he is on),
@@ -2665,9 +2584,9 @@ __global__ __launch_bounds__(PT_THREADS) void kp_rounds(PairParams P, uint32_t i
             // that: a new launch starts by invalidating the L2.  (Stores and loads may pass each other on the way: the line
             // ends up resident and current either way, the L2 is where this XCD's stores are performed.)
             uint32_t acc = 0;
-            const uint32_t* const rb = P.rec2[npar] + po + base;
-            for (uint32_t i = (uint32_t)tid * 16u; i < tl; i += PT_THREADS * 16u) acc ^= xld(rb + i);
-            for (uint32_t i = (uint32_t)tid * 16u; i < own_words; i += PT_THREADS * 16u) acc ^= xld(bits_dst + (base >> 5) + i);
+            const uint32_t* const rb = P.rec2[npar] + G.po + G.base;
+            for (uint32_t i = (uint32_t)tid * 16u; i < G.tl; i += PT_THREADS * 16u) acc ^= xld(rb + i);
+            for (uint32_t i = (uint32_t)tid * 16u; i < G.own_words; i += PT_THREADS * 16u) acc ^= xld(bits_dst + (G.base >> 5) + i);
             TW_SINK(acc);
         }
         // ---- the tables are out: arrive ----
@@ -2694,36 +2613,31 @@ __global__ __launch_bounds__(PT_THREADS) void kp_rounds(PairParams P, uint32_t i
                 }
             } else atomicAdd(bar, add);
         }
-        EMIT_STORE();                            // nobody in this launch waits for the lobbies: behind the arrival
+        E.store(P, g, G.qo);                     // nobody in this launch waits for the lobbies: behind the arrival
         TMARK(4);
     }
-#undef EMIT_LOAD
-#undef EMIT_STORE
     if (!ended && !stop) return;                 // (shim launches: the resident state goes on in the next launch)
 
     // ---- epilogue: the chain's state back into its committed form (what kp_round_commit / kp_round_stage do) ----
     const int tid = tid_o, lane = tid & 63;
     const bool tmr = t == 1u && tid == 0;
     __syncthreads();
-    for (uint32_t i = tid; i < own_words; i += PT_THREADS) bits_com[(base >> 5) + i] = s_bits[i];
-    for (uint32_t i = tid; i < tl; i += PT_THREADS)             // (a chain that ended in mid-sweep: "on the long list" is no value to keep)
+    for (uint32_t i = tid; i < G.own_words; i += PT_THREADS) bits_com[(G.base >> 5) + i] = s_bits[i];
+    for (uint32_t i = tid; i < G.tl; i += PT_THREADS)           // (a chain that ended in mid-sweep: "on the long list" is no value to keep)
         if (s_nx[i] == NX_PEND) s_nx[i] = (uint16_t)NX_INV;
     __syncthreads();
     {
-        uint4* const nx4 = (uint4*)gnx;
-        for (uint32_t i = tid; i < (tl + 7u) >> 3; i += PT_THREADS) nx4[i] = ((const uint4*)s_nx)[i];
+        uint4* const nx4 = (uint4*)G.gnx;
+        for (uint32_t i = tid; i < (G.tl + 7u) >> 3; i += PT_THREADS) nx4[i] = ((const uint4*)s_nx)[i];
     }
     if (tid == 0) L.ctl[0] = 1;
     if (t == 0 && tid == 0) {
-        const RoundState S = L.S;
-        pc->qlen = S.qlen; pc->passes = S.passes; pc->n_out = S.n_out; pc->has_anchor = S.has_anchor;
-        pc->a_key = S.a_key; pc->a_team = S.a_team;
-        if (S.has_anchor && S.a_oi != PK_NO) {
-            pc->a_slot = P.q_slot[qo + S.a_oi]; pc->a_rating = P.q_rating[qo + S.a_oi]; pc->a_cons = P.q_cons[qo + S.a_oi];
-        } else { pc->a_slot = S.a_slot; pc->a_rating = S.a_rating; pc->a_cons = S.a_cons; }
-        pc->pairs = S.pairs; pc->scanned = S.scanned; pc->rounds = S.rounds;
-        pc->want_compact = S.want_compact | ((!S.done && P.pyq[g] && S.qlen <= P.pyq[g]) ? 1u : 0u);   // (the yield is for a compaction)
-        pc->pos0 = S.pos0; pc->changed0 = S.changed0; pc->extra0 = S.extra0;
+        RoundState S = L.S;
+        if (S.has_anchor && S.a_oi != PK_NO) {   // the seated anchor's values, not fetched on the way
+            S.a_slot = P.q_slot[G.qo + S.a_oi]; S.a_rating = P.q_rating[G.qo + S.a_oi]; S.a_cons = P.q_cons[G.qo + S.a_oi];
+        }
+        if (!S.done && P.pyq[g] && S.qlen <= P.pyq[g]) S.want_compact = 1u;      // (the yield is for a compaction)
+        round_state_commit(pc, S);
         if (S.done) pc->stage = PS_DONE;
         pc->pfail = stop;
         pc->ppass += L.ctl[2];
@@ -2871,11 +2785,7 @@ __global__ __launch_bounds__(256) void kp_round_commit(PairParams P, uint32_t r_
     __syncthreads();
     if (t == 0 && tid == 0) {
         const RoundState S = pc->rs[cpar];
-        pc->qlen = S.qlen; pc->passes = S.passes; pc->n_out = S.n_out; pc->has_anchor = S.has_anchor;
-        pc->a_key = S.a_key; pc->a_slot = S.a_slot; pc->a_cons = S.a_cons; pc->a_team = S.a_team;
-        pc->a_rating = S.a_rating; pc->pairs = S.pairs; pc->scanned = S.scanned; pc->rounds = S.rounds;
-        pc->want_compact = S.want_compact;
-        pc->pos0 = S.pos0; pc->changed0 = S.changed0; pc->extra0 = S.extra0;
+        round_state_commit(pc, S);
     }
 }
 

@@ -8,7 +8,7 @@ from fractions import Fraction
 import numpy as np
 
 from microservice_matchmaking_amd._abi import NO_SLOT, cons_make
-from microservice_matchmaking_amd.config import make_config
+from microservice_matchmaking_amd.config import make_config, mode_1v1
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mode_r_cases.json")
 
@@ -131,6 +131,29 @@ def assert_same_state(ea, eb, cfg, tag=""):
             sa, ta = ea.lobby_state(mode, g)
             sb, tb = eb.lobby_state(mode, g)
             assert np.array_equal(sa, sb) and np.array_equal(ta, tb), (tag, "lobby", mode, g, sa, sb)
+
+
+def run_full_tile_one_pass(engine_cls, oracle_cls, tag):
+    """More than 1024 lobbies in one tile and pass — the immediate emission of the pair walk's pass_apply
+    (mm_pair.inc, `i >= PT_THREADS`: a thread defers one lobby, the tile's further ones are stored right away).
+    One 1v1 mode, one region, the window as wide as the rating span: every player fits its neighbour, so the first
+    pass pairs the whole queue.  One rating group of 20 000 players is the smallest chain that is tiled at all
+    (kp_late takes the ones below 16 384): three tiles of 8192 positions, and a full tile emits 4096 lobbies in that
+    pass.  The tile length is pinned to the largest (mm_tuning.pair_tile_fixed): left to itself the host walks a chain
+    of 20 000 in ten tiles of 2048, which hold 1024 lobbies at most and never reach the branch (one of 4096 needs a
+    chain of more than 40 x 2048 players).  Equality with the oracle, all 10 000 lobbies and a tick of at most two
+    passes together say that one pass put more than 1024 lobbies into a tile."""
+    n = 20000
+    cfg = make_config([mode_1v1(window=1500, region_filter=True)], capacity=1 << 15)
+    rating = np.random.default_rng(41).integers(0, 1400, size=n).astype(np.int32)      # the first rating group: 0 .. 1499
+    cons = cons_make(np.zeros(n, np.int64), 0, 0, 0)
+    with engine_cls(cfg, {"pair_tile_fixed": 1}) as e, oracle_cls(cfg) as o:
+        assert np.array_equal(e.enqueue(rating, cons), o.enqueue(rating, cons))
+        me, mo = e.tick(0), o.tick(0)
+        assert_same_tick(me, mo, tag)
+        assert_same_state(e, o, cfg, tag)
+        assert len(me) == n // 2, (tag, len(me))
+        assert me.stats["passes_max"] <= 2, (tag, me.stats["passes_max"])
 
 
 def random_scenario(rng, cfg, ea, eb, n_rounds=4, batch=200, cancel_frac=0.05, n_regions=3,

@@ -6,7 +6,7 @@ counters (pairs, scanned, passes, pool sizes) and lobby/queue state; scores with
 import numpy as np
 import pytest
 
-from helpers import assert_same_state, assert_same_tick, load_golden, random_scenario, run_golden_case
+from helpers import assert_same_state, assert_same_tick, load_golden, random_scenario, run_full_tile_one_pass, run_golden_case
 from microservice_matchmaking_amd import cons_make, make_config, mode_1v1, mode_team
 from microservice_matchmaking_amd.synth import ROLE_WEIGHTS_5V5, make_pool
 
@@ -610,6 +610,16 @@ def test_gpu_pair_rounds_stop_and_go_on(gpu_cls, oracle_cls, monkeypatch, env):
                     assert ps["degraded"] == 1 and ps["pair_stops_timeout"] >= 1 and ps["pair_round_launches"] > 0, ps
                 else:
                     assert ps["degraded"] == 1 and ps["pair_persist_off"] == 1 and ps["pair_rounds_launches"] == 0, ps
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env", [{}, {"MM_PAIR_PERSIST": "0"}], ids=["kp_rounds", "kp_round"])
+def test_gpu_pair_more_than_1024_lobbies_in_a_tile_and_pass(gpu_cls, oracle_cls, monkeypatch, env):
+    """pass_apply's immediate emission (a full tile of 8192 positions emits 4096 lobbies in one pass), in both kernels
+    that share it: helpers.run_full_tile_one_pass."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    run_full_tile_one_pass(gpu_cls, oracle_cls, "full tile, one pass %s" % env)
 
 
 @pytest.mark.gpu
