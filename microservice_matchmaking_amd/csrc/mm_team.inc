@@ -41,6 +41,9 @@
 //             ONE launch: a chaser takes F[a] as soon as the flag of a's chunk is up, so the chase runs
 //             beside kt_f instead of behind it
 //   the last passes (a handful of lobbies each)         kt_late, once: one persistent workgroup per chain
+// Written once for the pass kernels' chaser (tc_chaser) and kt_late's: the close of a pass (pass_close), a player's leaving the
+// queue (tq_leave), the tail of an emission (emit_members), lobby_clear, lobby_needs.  The stored lobby's fill from the head of
+// the queue and the lobby left open stand twice, in tc_chaser and in kt_late's head_fill / open_lobby_close (see there).
 //   (Rounds 2-5 could also run kt_f | kt_chase | kt_emit one behind the other — MM_TEAM_LIVE=0 / MM_TEAM_FUSED=0; taken out in round 6.)
 // What workgroups of one launch tell each other goes through agent-scope atomics (pub_st / pub_ld);
 // the one that waits always has the lower index, i.e. is dispatched first.
@@ -152,7 +155,7 @@ struct TwScratch {       // one wave's lobby under construction (LDS)
     uint32_t pos[MM_MAX_LOBBY], spos[MM_MAX_LOBBY];
     int32_t rat[MM_MAX_LOBBY];
     uint32_t con[MM_MAX_LOBBY], slo[MM_MAX_LOBBY];
-    uint32_t sqx[MM_MAX_LOBBY];                              // where the player stands in its role's sub-queue (tw_sort_load -> tw_kill)
+    uint32_t sqx[MM_MAX_LOBBY];                              // where the player stands in its role's sub-queue (tw_sort_load -> tq_kill)
 };
 
 // What workgroups of ONE launch tell each other (kt_chase's chaser -> its emitter workgroups; kt_fc's kt_f chunks
@@ -1080,17 +1083,45 @@ static __device__ __forceinline__ uint32_t tw_replay(LobbyDev& lb, const TwScrat
     return err;
 }
 
-// S's players leave the queue
-template <int HAVE_SQX = 1>           // S.sqx is tw_sort_load's (else the entry is looked up here: a trip more)
-static __device__ __forceinline__ void tw_kill(const TeamParams& P, uint32_t g, const TwScratch& S, uint32_t n, int lane)
+// A player leaves the queue.  WHAT: the records of the queue that the caller keeps current with this call —
+//   TQ_BITS   its bit in `bits`, the chaser's bitmap: bits[1] in memory (the pass kernels) or kt_late's copy in LDS
+//   TQ_CHUNK  its role's population of its chunk
+//   TQ_TOMB   its entry `sqx` of the role sub-queue (tw_sort_load's S.sqx; TQ_SQI: looked up here, a trip more) becomes a tombstone, a key no
+//             interval holds, and stays where it is until kt_build runs again.  kt_late writes none: its bitmap skips the entries, the next tick rebuilds.
+enum { TQ_BITS = 1, TQ_CHUNK = 2, TQ_TOMB = 4, TQ_ALL = 7, TQ_SQI = 8 };
+static __device__ __forceinline__ uint32_t* tq_chunk(const TeamParams& P, uint32_t g, uint32_t role, uint32_t pos)
 {
-    if ((uint32_t)lane < n) {
-        const uint32_t pos = S.spos[lane], role = (S.con[lane] >> 16) & 7u;
-        atomicAnd(&P.bits[1][(size_t)g * P.bits_stride + (pos >> 5)], ~(1u << (pos & 31u)));
-        atomicSub(&P.chunk[((size_t)g * MM_MAX_ROLES + role) * P.chunk_stride + pos / TT_CH], 1u);
-        // its entry in the role sub-queue stays where it is until kt_build runs again: a key no interval holds
-        P.sqk[(size_t)g * P.pstride + (HAVE_SQX ? S.sqx[lane] : P.sqi[(size_t)g * P.pstride + pos])] = 0xFFFFFFFFu;
+    return &P.chunk[((size_t)g * MM_MAX_ROLES + role) * P.chunk_stride + pos / TT_CH];
+}
+template <int WHAT>
+static __device__ __forceinline__ void tq_leave(const TeamParams& P, uint32_t g, uint32_t* bits, uint32_t pos, uint32_t cons, uint32_t sqx)
+{
+    if (WHAT & TQ_BITS) atomicAnd(&bits[pos >> 5], ~(1u << (pos & 31u)));
+    if (WHAT & TQ_CHUNK) atomicSub(tq_chunk(P, g, (cons >> 16) & 7u, pos), 1u);
+    if (WHAT & TQ_TOMB) P.sqk[(size_t)g * P.pstride + ((WHAT & TQ_SQI) ? P.sqi[(size_t)g * P.pstride + pos] : sqx)] = 0xFFFFFFFFu;
+}
+// ... S's players, a lane each
+template <int WHAT>
+static __device__ __forceinline__ void tq_kill(const TeamParams& P, uint32_t g, uint32_t* bits, const TwScratch& S, uint32_t n, int lane)
+{
+    if ((uint32_t)lane < n) tq_leave<WHAT>(P, g, bits, S.spos[lane], S.con[lane], (WHAT & TQ_SQI) ? 0u : S.sqx[lane]);
+}
+
+// the lobby record is empty again
+static __device__ __forceinline__ void lobby_clear(LobbyDev& lb, int lane)
+{
+    if (lane == 0) {
+        lb.n = 0;
+        for (uint32_t t = 0; t < MM_MAX_TEAMS; ++t) lb.cnt[t] = 0;
     }
+}
+
+// seats per role of the lobby an anchor of role `arole` opens, a nibble each: teams * quota[r], less the anchor's own
+static __device__ __forceinline__ uint32_t lobby_needs(const ModeDev& M, uint32_t arole)
+{
+    uint32_t needs = 0;
+    for (uint32_t r = 0; r < M.n_roles; ++r) needs |= (M.teams * M.quota[r] - (r == arole ? 1u : 0u)) << (4u * r);
+    return needs;
 }
 
 static __device__ __forceinline__ void tw_lobby_copy(uint32_t* dst, const uint32_t* src, int lane)
@@ -1210,6 +1241,21 @@ static __device__ __forceinline__ void tl_write_lobby(const TeamParams& P, uint3
     P.out_pass[(size_t)g * P.out_rec_stride + idx] = pass;
 }
 
+// The tail of an emission, for the members in S.pos[0..nf) and an empty `lb`: their records in queue order, the seats replayed
+// (the team choice needs the order), the lobby written at out index `idx`, the players taken out of the queue (WHAT, bits: tq_leave).
+template <int WHAT>
+static __device__ __forceinline__ uint32_t emit_members(const TeamParams& P, uint32_t g, LobbyDev& lb, TwScratch& S, uint32_t nf,
+                                                        uint32_t idx, uint32_t pass, uint32_t err, uint32_t* bits, int lane)
+{
+    tw_sort_load(S, nf, P, g, lane);
+    err |= tw_replay(lb, S, nf, P.M, lane);
+    if (lb.n != P.M.L) err |= MM_ERRF_SEAT_INVARIANT;
+    // is_filled: emit in team order (search/worker.ex:313-319)
+    if (lane == 0 && !err) tl_write_lobby(P, g, lb, idx, pass);
+    tq_kill<WHAT>(P, g, bits, S, nf, lane);
+    return err;
+}
+
 // One lobby a pass emits (kt_emit's unit of work, and the emitter waves' behind kt_chase): the anchor `a`, its members
 // from kt_f's record (or looked up when kt_chase went by its own look-up), the seats replayed in queue order (the team
 // choice needs the order), the lobby written at out index `idx`, the players taken out of the queue.
@@ -1225,11 +1271,8 @@ static __device__ __forceinline__ uint32_t te_emit_one(const TeamParams& P, uint
     const bool looked = (a & TV_LOOKED) != 0u;                // the chaser did not have kt_f's F for this anchor: neither do we
     a &= ~TV_LOOKED;
     wave_sync();
-    if (lane == 0) {
-        lb.n = 0;
-        for (uint32_t t = 0; t < MM_MAX_TEAMS; ++t) lb.cnt[t] = 0;
-        S.pos[0] = a;
-    }
+    lobby_clear(lb, lane);
+    if (lane == 0) S.pos[0] = a;
     const uint32_t LM = M.L - 1u;
     const bool mine = (uint32_t)lane >= 1u && (uint32_t)lane <= LM;
     uint32_t Fa, fpa, dm = 0;                                 // all of the record in one trip
@@ -1248,14 +1291,14 @@ static __device__ __forceinline__ uint32_t te_emit_one(const TeamParams& P, uint
         if (mine) S.pos[lane] = a + dm;
         nf = M.L;
     }
-    uint32_t lo = 0, rng = 0, arole = 0, st = 0;
+    uint32_t lo = 0, rng = 0, needs = 0, st = 0;
     if (!rec) {
         pk_bounds(P.tkey[po + a], P.window, lo, rng);
-        arole = (P.q_cons[qo + a] >> 16) & 7u;
+        needs = lobby_needs(M, (P.q_cons[qo + a] >> 16) & 7u);
         st = tw_starts(P, g, a, m, lane);
     }
     for (uint32_t r = 0; r < nr && !rec; ++r) {
-        const uint32_t need = M.teams * M.quota[r] - (r == arole ? 1u : 0u);
+        const uint32_t need = (needs >> (4u * r)) & 15u;
         const uint32_t j0 = lane_get(st, (int)r);
         if (!need) continue;
         const uint32_t got = tw_collect(P.sqk + po + tc->off[r], P.sqp + po + tc->off[r], j0, tc->len[r], need,
@@ -1263,13 +1306,7 @@ static __device__ __forceinline__ uint32_t te_emit_one(const TeamParams& P, uint
         nf += got;
         if (got < need) err |= MM_ERRF_SEAT_INVARIANT;
     }
-    tw_sort_load(S, nf, P, g, lane);
-    err |= tw_replay(lb, S, nf, M, lane);
-    if (lb.n != M.L) err |= MM_ERRF_SEAT_INVARIANT;
-    // is_filled: emit in team order (search/worker.ex:313-319)
-    if (lane == 0 && !err) tl_write_lobby(P, g, lb, idx, pass);
-    tw_kill(P, g, S, nf, lane);
-    return err;
+    return emit_members<TQ_ALL>(P, g, lb, S, nf, idx, pass, err, P.bits[1] + (size_t)g * P.bits_stride, lane);
 }
 
 
@@ -1520,6 +1557,127 @@ static __device__ __forceinline__ uint32_t tcf_load(const TeamParams& P, uint32_
     return tw_sload(P.fv + (size_t)g * P.pstride + a);
 }
 
+// ------------------------------------------------------------------------------------
+// A pass of a chain around its chase.  pass_close — the pass's counters, the first-pass rules of a cancel tick, `done` — is
+// one body for tc_chaser (kt_chase, kt_fc, kt_f's head-fill column) and kt_late's wave 0.  head_fill (the stored lobby meets
+// the queue from its head) and open_lobby_close (the lobby that stays open) are kt_late's; tc_chaser keeps its own text of
+// both: built on head_fill alone kt_fc's pass was 1.9 us slower, with the view in its chase loop more; and kt_late with its own
+// text inline again runs 1 % slower than with these two functions (profiles/team_pass_refactor_check.txt, 4a, 4c).  A rule changed in one
+// is changed in the other; what they share beneath — lobby_clear, lobby_needs, tq_kill, lsum_seat — is written once.
+// ------------------------------------------------------------------------------------
+struct PassTally { uint32_t nvis, head, n_open, gone, err; bool changed, over; };       // what one pass did; over: the chase has nothing left to do
+struct PassCounts { uint32_t qlen, passes, n_out; unsigned long long pairs, scanned; };  // the chain's running counts (TeamChain's)
+
+// How kt_late's chaser sees the queue: the bitmap in LDS, current (a pass only takes players out behind the cursor); look-ups by
+// the chaser alone, all roles abreast, the entries of players that left skipped by the bitmap; no tombstones.
+struct QvLate {
+    enum { KILL = TQ_BITS | TQ_CHUNK };
+    const TeamParams& P;
+    const uint32_t g;
+    uint32_t* const bits;
+    const uint32_t (&rlen)[MM_MAX_ROLES];                     // the sub-queues of the last kt_build: fixed for the launch
+    const uint32_t (&roff)[MM_MAX_ROLES];
+    uint32_t (&d_sc)[MM_MAX_ROLES];                           // MM_PAIR_DEBUG: sub-queue entries scanned per role
+    __device__ __forceinline__ uint32_t succ(uint32_t from, uint32_t m, int lane) const { return uni(l_succ(bits, from, m, lane)); }
+    __device__ __forceinline__ uint32_t lookup(uint32_t st, uint32_t needs, uint32_t lo, uint32_t rng, uint32_t* out, uint32_t nout, int lane,
+                                               uint32_t* dry)
+    {
+        return tl_collect_all<1, 2, 8>(P, rlen, roff, (size_t)g * P.pstride, bits, st, needs, lo, rng, out, nout, lane, dry, d_sc);
+    }
+};
+static_assert(PK_NO == TT_NONE, "l_succ's and tw_succ's `nobody` are one value");
+
+// The stored lobby meets the queue from its head (LobbyState.get_state, lobby_state.ex:61-104).
+// Normally one window: the anchor in the first team.  After a cancel emptied the lower
+// teams, the first player seated there becomes the anchor (MATCH_CHECK.md section 2.1) and
+// the players behind it are judged by ITS window: collect with the current anchor, seat
+// in queue order until the anchor moves, collect again from there.
+// If the lobby fills it is emitted right here (out index *n_out, pass *pass: read only then) and `lb` is empty from then on.
+// Returns where the chase begins (TT_NONE: nobody is queued behind); T.over: everybody was popped against the lobby and it
+// is still open — the pass is over.
+// A seated player leaves the queue at once, on lane 0 (tc_chaser's own fill: together when the fill is over, for the tombstones' trip).
+static __device__ __forceinline__ uint32_t head_fill(QvLate& V, TeamChain* tc, LobbySum& L, LobbyDev& lb, TwScratch& S, uint32_t m,
+                                                     const uint32_t* n_out, const uint32_t* pass, PassTally& T, int lane)
+{
+    const TeamParams& P = V.P;
+    const ModeDev& M = P.M;
+    const uint32_t g = V.g;
+    uint32_t nseat = 0, from = 0;
+    bool moved = true;
+    for (uint32_t stage = 0; stage < MM_MAX_TEAMS && moved && L.n < M.L; ++stage) {
+        moved = false;
+        uint32_t lo, rng;
+        pk_bounds(pk_pack(L.ar, L.ac, tc->rmin, P.eqmask), P.window, lo, rng);
+        const uint32_t st = from ? tw_starts(P, g, from - 1u, m, lane) : 0u;
+        wave_sync();
+        uint32_t dry = 0;
+        const uint32_t nf = V.lookup(st, L.free, lo, rng, S.pos, 0u, lane, &dry);
+        tw_sort_load(S, nf, P, g, lane);
+        const uint32_t at0 = L.at;
+        uint32_t k = 0;
+        while (k < nf && !moved) {
+            if (lsum_seat(L, lb, M, S.rat[k], S.con[k], S.slo[k], lane) < 0) T.err |= MM_ERRF_SEAT_INVARIANT;
+            if (lane == 0) tq_leave<QvLate::KILL>(P, g, V.bits, S.spos[k], S.con[k], 0u);   // the open lobby holds the player from here on
+            ++nseat;
+            ++k;
+            if (L.at != at0) moved = true;
+        }
+        wave_sync();
+        if (k) from = S.spos[k - 1u] + 1u;
+        if (moved && lane == 0) tc->dbg[7] += 1u;
+    }
+    wave_sync();
+    T.gone += nseat;
+    T.changed = nseat > 0u;
+    T.over = L.n != M.L;
+    if (T.over) return TT_NONE;
+    // filled by the player at from - 1 (lb holds it, seated in queue order)
+    if (*n_out >= P.out_cap) T.err |= MM_ERRF_OUT_OVERFLOW;
+    else if (lane == 0) tl_write_lobby(P, g, lb, *n_out, *pass);
+    wave_sync();
+    lobby_clear(lb, lane);
+    wave_sync();
+    lsum_load(L, lb, M);
+    T.head = 1;
+    T.changed = true;
+    return V.succ(from, m, lane);
+}
+
+// The lobby the anchor S.pos[0] opens stays open: it and everybody it takes (S, in queue order) are seated, nobody else
+// is queued behind — the pass is over.
+static __device__ __forceinline__ void open_lobby_close(const QvLate& V, LobbyDev& lb, const TwScratch& S, uint32_t nf, PassTally& T, int lane)
+{
+    T.err |= tw_replay(lb, S, nf, V.P.M, lane);
+    tq_kill<QvLate::KILL>(V.P, V.g, V.bits, S, nf, lane);
+    T.n_open = 1;
+    T.changed = true;
+    T.gone += nf;
+    T.over = true;
+}
+
+// The end of a pass: the chain's counts move on by what the pass did.  On the first pass of a cancel tick the head was
+// popped against the stale lobby in kt_init; if that rejected it, it sat the pass out and is back in the queue for the next
+// (lane 0 puts it back into `bits`, the chaser's current bitmap; team_walk keeps such a tick from kt_late to this day — a
+// head that sat out is not in the first pass's sub-queues — but the rule is the same one).  Returns `done`.
+static __device__ __forceinline__ bool pass_close(const TeamParams& P, uint32_t g, const TeamChain* tc, uint32_t* bits, PassTally& T,
+                                                  PassCounts& C, int lane)
+{
+    const uint32_t left = C.qlen - T.gone - T.nvis * P.M.L;
+    const bool first = C.passes == 0u;
+    const uint32_t popped = C.qlen + (first ? tc->extra0 : 0u);
+    if (first && tc->changed0) T.changed = true;
+    if (first && tc->sitout && lane == 0) {
+        atomicOr(&bits[0], 1u);
+        atomicAdd(tq_chunk(P, g, tc->head_role, 0u), 1u);
+    }
+    C.n_out += T.head + T.nvis;
+    C.pairs += (unsigned long long)(popped - (T.nvis + T.n_open));
+    C.scanned += (unsigned long long)popped;
+    C.qlen = left;
+    C.passes += 1u;
+    return !(T.changed || T.nvis) || left == 0u || T.err;
+}
+
 // The chaser of chain g (one wave).  USE_F2: the passes that have F o F (kt_f2) — its own instantiation, so that the
 // plain chase stays as tight as it was.  LIVE: kt_f's chunks run in the same launch (kt_fc).
 // PHASE 0: a whole pass.  1: only the stored lobby's fill from the head of the queue (in kt_f's launch, beside its chunks: it needs
@@ -1543,7 +1701,8 @@ static __device__ __forceinline__ void tc_chaser(const TeamParams& P, const uint
     const uint32_t c = P.mode * P.n_groups + g;
     ChainDev* const ch = P.chains + c;
     const size_t qo = (size_t)c * P.capacity, po = (size_t)g * P.pstride;
-    const uint32_t m = tc->m, qlen = tc->qlen, nr = M.n_roles;
+    const uint32_t m = tc->m, qlen = tc->qlen;
+    uint32_t* const bits1 = P.bits[1] + (size_t)g * P.bits_stride;   // the current bitmap
     // the bitmap of the start of the pass: kt_f's copy — or, LIVE, the current one: what this pass takes out lies
     // behind the cursor, and the chaser only ever asks for positions from the cursor on
     const uint32_t* const b0 = P.bits[(LIVE || PHASE == 1) ? 1 : 0] + (size_t)g * P.bits_stride;
@@ -1610,17 +1769,14 @@ static __device__ __forceinline__ void tc_chaser(const TeamParams& P, const uint
         // the players it took leave the queue, whether it filled or not
         if ((uint32_t)lane < nseat) { S.spos[lane] = s_hf[lane]; S.con[lane] = s_hfc[lane]; }
         wave_sync();
-        tw_kill<0>(P, g, S, nseat, lane);
+        tq_kill<TQ_ALL | TQ_SQI>(P, g, bits1, S, nseat, lane);
         if (L.n == M.L) {
             // filled by the player at from - 1: emitted right here (s_lb holds it, seated in queue order); the
             // lobby is empty from here on
             if (tc->n_out >= P.out_cap) err |= MM_ERRF_OUT_OVERFLOW;
             else if (lane == 0) tl_write_lobby(P, g, s_lb, tc->n_out, tc->passes);
             wave_sync();
-            if (lane == 0) {
-                s_lb.n = 0;
-                for (uint32_t t = 0; t < MM_MAX_TEAMS; ++t) s_lb.cnt[t] = 0;
-            }
+            lobby_clear(s_lb, lane);
             wave_sync();
             lsum_load(L, s_lb, M);
             head = 1;
@@ -1684,13 +1840,12 @@ static __device__ __forceinline__ void tc_chaser(const TeamParams& P, const uint
 #define TLMARK(K) do { if (LIVE && P.debug) { const long long now = clock64(); t_lk[K] += now - tl0; tl0 = now; } } while (0)
         uint32_t lo, rng;
         pk_bounds(P.tkey[po + a], P.window, lo, rng);
-        const uint32_t arole = (P.q_cons[qo + a] >> 16) & 7u;
+        const uint32_t needs = lobby_needs(M, (P.q_cons[qo + a] >> 16) & 7u);
         const uint32_t st = tw_starts(P, g, a, m, lane);
         wave_sync();
         if (lane == 0) S.pos[0] = a;
         TLMARK(0);
-        uint32_t needs = 0, dry = 0;
-        for (uint32_t r = 0; r < nr; ++r) needs |= (M.teams * M.quota[r] - (r == arole ? 1u : 0u)) << (4u * r);
+        uint32_t dry = 0;
         // (eight 64-entry steps a trip: the role that runs dry — every pass ends on one — is read to its end)
         const uint32_t nf = 1u + tlk_lookup(P, g, v_off, v_len, K, kseq, st, needs, lo, rng, S.pos, 1u, lane, &dry, d_look);
         if (dry >> 31) err |= MM_ERRF_SYNC_TIMEOUT;
@@ -1706,7 +1861,7 @@ static __device__ __forceinline__ void tc_chaser(const TeamParams& P, const uint
         }
         // it stays open: `a` and everybody it takes are seated, nobody else is queued behind
         err |= tw_replay(s_lb, S, nf, M, lane);
-        tw_kill(P, g, S, nf, lane);
+        tq_kill<TQ_ALL>(P, g, bits1, S, nf, lane);
         TLMARK(3);
 #undef TLMARK
         n_open = 1;
@@ -1719,25 +1874,20 @@ static __device__ __forceinline__ void tc_chaser(const TeamParams& P, const uint
     if (lane == 0) {
         const uint32_t base = tc->n_out, n_new = head + nvis;
         if (base + n_new > P.out_cap) err |= MM_ERRF_OUT_OVERFLOW;
-        const uint32_t left = qlen - gone - nvis * M.L;
-        // first pass of a cancel tick: the head was popped against the stale lobby in kt_init
-        const bool first = tc->passes == 0u;
-        const uint32_t popped = qlen + (first ? tc->extra0 : 0u);
-        if (first && tc->changed0) changed = true;
-        if (first && tc->sitout) {            // it was rejected: back into the queue for the next pass
-            atomicOr(&P.bits[1][(size_t)g * P.bits_stride], 1u);
-            atomicAdd(&P.chunk[((size_t)g * MM_MAX_ROLES + tc->head_role) * P.chunk_stride], 1u);
-        }
+        PassTally T = {nvis, head, n_open, gone, err, changed, over};
+        PassCounts C = {qlen, tc->passes, base, tc->pairs, tc->scanned};
+        const uint32_t pass = C.passes;
+        const bool done = pass_close(P, g, tc, bits1, T, C, lane);
         tc->out_base = base;
-        tc->n_out = base + n_new;
+        tc->n_out = C.n_out;
         tc->n_vis = (err & MM_ERRF_OUT_OVERFLOW) ? 0u : nvis;
         tc->head = (err & MM_ERRF_OUT_OVERFLOW) ? 0u : head;
-        tc->cur_pass = tc->passes;
-        tc->pairs += (unsigned long long)(popped - (nvis + n_open));
-        tc->scanned += (unsigned long long)popped;
-        tc->qlen = left;
-        tc->passes += 1u;
-        if (!(changed || nvis) || left == 0u || err) tc->done = 1;
+        tc->cur_pass = pass;
+        tc->pairs = C.pairs;
+        tc->scanned = C.scanned;
+        tc->qlen = C.qlen;
+        tc->passes = C.passes;
+        if (done) tc->done = 1;
         if (err) atomicOr(&tc->err, err);          // (the emitters of this launch report theirs the same way)
         if (d_late) tc->flags_late += d_late;
         tc->cp[LIVE ? 1 : 0] += 1u;
@@ -1897,8 +2047,6 @@ __global__ __launch_bounds__(TT_CH) MM_WAVES_PER_SIMD(KT_FC_WPS) void kt_fc(Team
     Roles& R = *reinterpret_cast<Roles*>(&s_tmp[0][0]);
     LobbyDev* const s_lbw = R.lbw;
     TwScratch* const s_Sw = R.Sw;
-    uint32_t* const s_hf = R.hf;
-    uint32_t* const s_hfc = R.hfc;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // Order of the workgroups: the chasers, kt_f's chunks, the emitters.  The chasers wait for chunks and the emitters
     // for the chasers; nobody who waits may keep the one he waits for off the chip, so only the chasers — one workgroup
@@ -1922,7 +2070,7 @@ __global__ __launch_bounds__(TT_CH) MM_WAVES_PER_SIMD(KT_FC_WPS) void kt_fc(Team
         if (threadIdx.x < MM_MAX_ROLES) R.look.ack[threadIdx.x] = 0;
         __syncthreads();
         if (wave == 0) {
-            tc_chaser<0, 1>(P, k, lane, s_lbw[0], s_Sw[0], s_hf, s_hfc, R.look);
+            tc_chaser<0, 1>(P, k, lane, s_lbw[0], s_Sw[0], R.hf, R.hfc, R.look);
             if (lane == 0) lds_st(&R.look.seq, TLK_EXIT);      // the helper waves may go
         } else if ((uint32_t)wave < P.M.n_roles) tlk_helper(P, k, R.look, (uint32_t)wave, lane);   // the chaser's look-ups, a role each
         return;
@@ -1953,7 +2101,8 @@ __global__ __launch_bounds__(TT_CH) MM_WAVES_PER_SIMD(KT_FC_WPS) void kt_fc(Team
 // writes tombstones here: the chain is walked to its end in this launch and the next tick rebuilds).
 // Waves 1.. take the lobbies from an LDS ring: the players' records, the seats replayed in queue order
 // (the team choice needs the order: lsum_seat, as kt_emit), the lobby written, the chunk populations.
-// The pass bookkeeping is kt_chase's, line by line.  The bitmap goes back to HBM once, at the end.
+// What a pass does around the chase: head_fill and open_lobby_close (tc_chaser's rules over the LDS bitmap, QvLate) and
+// pass_close, the one tc_chaser calls.  The bitmap goes back to HBM once, at the end.
 // Exactness: a pass only takes players out BEHIND the cursor (a lobby's members all lie before the next
 // anchor), so the current bitmap is, for everything the pass still looks at, the bitmap of its start.
 // ------------------------------------------------------------------------------------
@@ -1964,16 +2113,6 @@ __global__ __launch_bounds__(TT_CH) MM_WAVES_PER_SIMD(KT_FC_WPS) void kt_fc(Team
 #define TL_BITS_MAX (1u << 20)       // positions of a chain whose bitmap fits the workgroup's LDS (128 KB)
 #endif
 struct TlJob { uint32_t seq, n, idx, pass, pos[MM_MAX_LOBBY]; };
-
-// S's players leave the queue: the LDS bitmap now (the chaser's view), the chunk populations in HBM
-static __device__ __forceinline__ void tl_kill(const TeamParams& P, uint32_t g, uint32_t* bits, const TwScratch& S, uint32_t n, int lane)
-{
-    if ((uint32_t)lane < n) {
-        const uint32_t pos = S.spos[lane], role = (S.con[lane] >> 16) & 7u;
-        atomicAnd(&bits[pos >> 5], ~(1u << (pos & 31u)));
-        atomicSub(&P.chunk[((size_t)g * MM_MAX_ROLES + role) * P.chunk_stride + pos / TT_CH], 1u);
-    }
-}
 
 __global__ __launch_bounds__(TL_THREADS) void kt_late(TeamParams P)
 {
@@ -2003,85 +2142,34 @@ __global__ __launch_bounds__(TL_THREADS) void kt_late(TeamParams P)
     TwScratch& S = s_Sw[wave];
 
     if (wave == 0) {
-        // ---------------- the chaser: kt_chase's pass, again and again ----------------
+        // ---------------- the chaser: pass after pass (head_fill, the chase below, open_lobby_close, pass_close) ----------------
         tw_lobby_copy((uint32_t*)&s_lb, (const uint32_t*)&ch->lobby, lane);
         LobbySum L;
         lsum_load(L, s_lb, M);
-        uint32_t qlen = tc->qlen, passes = tc->passes, n_out = tc->n_out, err = 0, rk = 0;
-        const uint32_t passes0 = passes, n_out0 = n_out;
+        PassCounts C = {tc->qlen, tc->passes, tc->n_out, tc->pairs, tc->scanned};   // in registers across the passes, stored once
+        const uint32_t passes0 = C.passes, n_out0 = C.n_out;
+        uint32_t err = 0, rk = 0;
         uint32_t rlen[MM_MAX_ROLES], roff[MM_MAX_ROLES];       // the sub-queues of the last kt_build: fixed for this launch
 #pragma unroll
         for (uint32_t r = 0; r < MM_MAX_ROLES; ++r) { rlen[r] = r < nr ? tc->len[r] : 0u; roff[r] = r < nr ? tc->off[r] : 0u; }
-        unsigned long long pairs = tc->pairs, scanned = tc->scanned;
-        bool done = qlen == 0u, bailed = false;
+        bool done = C.qlen == 0u, bailed = false;
         // MM_PAIR_DEBUG: what the chaser did and where its time went (TeamChain.lt)
         uint32_t d_rec = 0, d_look = 0, d_open = 0, d_fill = 0, d_sc[MM_MAX_ROLES] = {0, 0, 0, 0, 0, 0, 0, 0};
         long long c_rec = 0, c_look = 0, c_fill = 0, c_ring = 0;
         const long long c_all0 = clock64();
-        if (P.debug && lane == 0) tc->lt[15] = passes;
+        if (P.debug && lane == 0) tc->lt[15] = C.passes;
+        QvLate V = {P, g, s_bits, rlen, roff, d_sc};
         while (!done) {
-            uint32_t nvis = 0, head = 0, n_open = 0, gone = 0;
-            bool changed = false, over = false;
+            PassTally T = {0u, 0u, 0u, 0u, err, false, false};
             uint32_t a = TT_NONE;
             if (L.n > 0u) {
-                // the stored lobby meets the queue from its head (kt_chase: stage by stage while the anchor moves)
-                const long long c0 = clock64();
+                const long long c0 = clock64();                 // (MM_PAIR_DEBUG, lt[12]: the fill with its emission on the spot)
                 ++d_fill;
-                uint32_t nseat = 0, from = 0;
-                bool moved = true;
-                for (uint32_t stage = 0; stage < MM_MAX_TEAMS && moved && L.n < M.L; ++stage) {
-                    moved = false;
-                    uint32_t lo, rng;
-                    pk_bounds(pk_pack(L.ar, L.ac, tc->rmin, P.eqmask), P.window, lo, rng);
-                    const uint32_t st = from ? tw_starts(P, g, from - 1u, m, lane) : 0u;
-                    wave_sync();
-                    uint32_t dry = 0;
-                    const uint32_t nf = tl_collect_all<1, 2, 8>(P, rlen, roff, po, s_bits, st, L.free, lo, rng, S.pos, 0u, lane, &dry, d_sc);
-                    tw_sort_load(S, nf, P, g, lane);
-                    const uint32_t at0 = L.at;
-                    uint32_t k = 0;
-                    while (k < nf && !moved) {
-                        if (lsum_seat(L, s_lb, M, S.rat[k], S.con[k], S.slo[k], lane) < 0) err |= MM_ERRF_SEAT_INVARIANT;
-                        // the player is seated: it leaves the queue (the open lobby holds it from here on)
-                        if (lane == 0) {
-                            const uint32_t pos = S.spos[k], role = (S.con[k] >> 16) & 7u;
-                            atomicAnd(&s_bits[pos >> 5], ~(1u << (pos & 31u)));
-                            atomicSub(&P.chunk[((size_t)g * MM_MAX_ROLES + role) * P.chunk_stride + pos / TT_CH], 1u);
-                        }
-                        ++nseat;
-                        ++k;
-                        if (L.at != at0) moved = true;
-                    }
-                    wave_sync();
-                    if (k) from = S.spos[k - 1u] + 1u;
-                    if (moved && lane == 0) tc->dbg[7] += 1u;
-                }
-                wave_sync();
+                a = head_fill(V, tc, L, s_lb, S, m, &C.n_out, &C.passes, T, lane);
                 c_fill += clock64() - c0;
-                gone += nseat;
-                changed = nseat > 0u;
-                if (L.n == M.L) {
-                    // filled by the player at from - 1: emitted right here (s_lb holds it, seated in queue order)
-                    if (n_out >= P.out_cap) err |= MM_ERRF_OUT_OVERFLOW;
-                    else if (lane == 0) tl_write_lobby(P, g, s_lb, n_out, passes);
-                    wave_sync();
-                    if (lane == 0) {
-                        s_lb.n = 0;
-                        for (uint32_t t = 0; t < MM_MAX_TEAMS; ++t) s_lb.cnt[t] = 0;
-                    }
-                    wave_sync();
-                    lsum_load(L, s_lb, M);
-                    head = 1;
-                    changed = true;
-                    a = uni(l_succ(s_bits, from, m, lane));
-                    if (a == PK_NO) a = TT_NONE;
-                } else over = true;      // everybody was popped against it and it is still open: the pass is over
-            } else {
-                a = uni(l_succ(s_bits, 0u, m, lane));
-                if (a == PK_NO) a = TT_NONE;
-            }
+            } else a = V.succ(0u, m, lane);
 
-            while (!over && a != TT_NONE) {
+            while (!T.over && a != TT_NONE) {
                 // Everything that depends on `a` alone is asked for in ONE trip: its record (lane 0 F, lane 1 the last
                 // member, lanes 2.. the members' distances) and — wanted only when the record turns out stale — its key
                 // and what places it in the role sub-queues (tw_starts: the 64-block's entries and roles, the ranks
@@ -2123,32 +2211,25 @@ __global__ __launch_bounds__(TL_THREADS) void kt_late(TeamParams P)
                     const uint32_t brole = inB ? (bcn >> 16) & 7u : 0u;
                     const uint32_t arole = (lane_get(bcn, (int)(a & 63u)) >> 16) & 7u;
                     const unsigned long long le = (2ull << (a & 63u)) - 1ull;
-                    uint32_t st = 0, needs = 0;
+                    uint32_t st = 0;
                     for (uint32_t r = 0; r < nr; ++r) {
                         const unsigned long long mk = __ballot(inB && brole == r);
                         const uint32_t base = lane_get(bbs, (int)r);
                         if ((uint32_t)lane == r) st = base + (uint32_t)__popcll(mk & le);
-                        needs |= (M.teams * M.quota[r] - (r == arole ? 1u : 0u)) << (4u * r);
                     }
                     wave_sync();
                     if (lane == 0) S.pos[0] = a;
                     uint32_t dry = 0;
-                    nf += tl_collect_all<1, 2, 8>(P, rlen, roff, po, s_bits, st, needs, lo, rng, S.pos, 1u, lane, &dry, d_sc);
+                    nf += V.lookup(st, lobby_needs(M, arole), lo, rng, S.pos, 1u, lane, &dry);
                     const bool ok = dry == 0u;
                     wave_sync();
                     c_look += clock64() - c2;
                     if (!ok) {
                         ++d_open;
-                        // it stays open: `a` and everybody it takes are seated, nobody else is queued behind
                         tw_sort_load(S, nf, P, g, lane);
-                        err |= tw_replay(s_lb, S, nf, M, lane);
-                        tl_kill(P, g, s_bits, S, nf, lane);
+                        open_lobby_close(V, s_lb, S, nf, T, lane);
                         wave_sync();
-                        lsum_load(L, s_lb, M);
-                        n_open = 1;
-                        changed = true;
-                        gone += nf;
-                        over = true;
+                        lsum_load(L, s_lb, M);                   // (the next pass begins with it)
                         break;
                     }
                     uint32_t mx = (uint32_t)lane < nf ? S.pos[lane] : 0u;
@@ -2156,7 +2237,7 @@ __global__ __launch_bounds__(TL_THREADS) void kt_late(TeamParams P)
                     last = mx;
                 }
                 // the lobby fills: an emitter wave seats and writes it; its players are behind the cursor from here on
-                if (n_out + head + nvis >= P.out_cap) { err |= MM_ERRF_OUT_OVERFLOW; over = true; break; }
+                if (C.n_out + T.head + T.nvis >= P.out_cap) { T.err |= MM_ERRF_OUT_OVERFLOW; T.over = true; break; }
                 wave_sync();
                 {
                     TlJob& J = s_ring[rk % TL_RING];
@@ -2167,60 +2248,45 @@ __global__ __launch_bounds__(TL_THREADS) void kt_late(TeamParams P)
                     if ((uint32_t)lane < nf) {
                         const uint32_t pos = S.pos[lane];
                         J.pos[lane] = pos;
-                        atomicAnd(&s_bits[pos >> 5], ~(1u << (pos & 31u)));
+                        tq_leave<TQ_BITS>(P, g, s_bits, pos, 0u, 0u);      // (the chunk populations: the emitter, which has the roles)
                     }
-                    if (lane == 0) { J.n = nf; J.idx = n_out + head + nvis; J.pass = passes; }
+                    if (lane == 0) { J.n = nf; J.idx = C.n_out + T.head + T.nvis; J.pass = C.passes; }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                     wave_lockstep();
                     if (lane == 0) lds_st(&J.seq, rk + 1u);
                     ++rk;
                 }
-                ++nvis;
-                a = uni(l_succ(s_bits, last + 1u, m, lane));
-                if (a == PK_NO) a = TT_NONE;
+                ++T.nvis;
+                a = V.succ(last + 1u, m, lane);
             }
 
-            // ---- the pass's counters: kt_chase's, line by line ----
-            const uint32_t left = qlen - gone - nvis * M.L;
-            const bool first = passes == 0u;
-            const uint32_t popped = qlen + (first ? tc->extra0 : 0u);
-            if (first && tc->changed0) changed = true;
-            if (first && tc->sitout) {            // the head was rejected by the stale lobby: back into the queue
-                if (lane == 0) {
-                    atomicOr(&s_bits[0], 1u);
-                    atomicAdd(&P.chunk[((size_t)g * MM_MAX_ROLES + tc->head_role) * P.chunk_stride], 1u);
-                }
-                wave_sync();
-            }
-            n_out += head + nvis;
-            pairs += (unsigned long long)(popped - (nvis + n_open));
-            scanned += (unsigned long long)popped;
-            qlen = left;
-            passes += 1u;
-            if (!(changed || nvis) || left == 0u || err) done = true;
+            const uint32_t n_new = T.head + T.nvis;
+            done = pass_close(P, g, tc, s_bits, T, C, lane);
+            wave_sync();                                      // (the head's bit, if pass_close put it back)
+            err = T.err;
             // a pass that seats many lobbies after all (a newcomer unblocked a cascade): back to the pass kernels,
             // which look lobbies up for everybody at once — the host rebuilds the sub-queues first (no tombstones here)
-            else if (head + nvis > P.late_bail) { bailed = true; break; }
+            if (!done && n_new > P.late_bail) { bailed = true; break; }
         }
         if (lane == 0) { lds_st(&s_produced, rk); lds_st(&s_fin, 1u); }
         tw_lobby_copy((uint32_t*)&ch->lobby, (const uint32_t*)&s_lb, lane);
         if (lane == 0) {
-            tc->n_out = n_out;
+            tc->n_out = C.n_out;
             tc->n_vis = 0;
             tc->head = 0;
-            tc->out_base = n_out;
-            tc->cur_pass = passes;
-            tc->pairs = pairs;
-            tc->scanned = scanned;
-            tc->qlen = qlen;
-            tc->passes = passes;
+            tc->out_base = C.n_out;
+            tc->cur_pass = C.passes;
+            tc->pairs = C.pairs;
+            tc->scanned = C.scanned;
+            tc->qlen = C.qlen;
+            tc->passes = C.passes;
             tc->done = bailed ? 0u : 1u;
-            tc->cp[2] += passes - passes0;
-            tc->cp[5] += n_out - n_out0;
+            tc->cp[2] += C.passes - passes0;
+            tc->cp[5] += C.n_out - n_out0;
             tc->cp[7] += d_look + d_fill;
             if (err) atomicOr(&s_err, err);
             if (P.debug) {
-                tc->lt[0] = passes - tc->lt[15]; tc->lt[1] = d_rec; tc->lt[2] = d_look; tc->lt[3] = d_open; tc->lt[4] = d_fill;
+                tc->lt[0] = C.passes - tc->lt[15]; tc->lt[1] = d_rec; tc->lt[2] = d_look; tc->lt[3] = d_open; tc->lt[4] = d_fill;
 #pragma unroll
                 for (uint32_t r = 0; r < 5u; ++r) tc->lt[5u + r] = d_sc[r];      // (unrolled: the counters stay in registers)
                 tc->lt[10] = (uint32_t)(c_rec >> 4); tc->lt[11] = (uint32_t)(c_look >> 4); tc->lt[12] = (uint32_t)(c_fill >> 4);
@@ -2228,7 +2294,7 @@ __global__ __launch_bounds__(TL_THREADS) void kt_late(TeamParams P)
             }
         }
     } else {
-        // ---------------- emitters: one lobby per ticket (kt_emit's work for a lobby on record) ----------------
+        // ---------------- emitters: one lobby per ticket (emit_members, as te_emit_one for a lobby on record) ----------------
         uint32_t err = 0;
         for (;;) {
             uint32_t t = 0;
@@ -2247,18 +2313,8 @@ __global__ __launch_bounds__(TL_THREADS) void kt_late(TeamParams P)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             wave_lockstep();
             if (lane == 0) lds_st(&J.seq, t + TL_RING);          // the slot is free again
-            if (lane == 0) {
-                s_lb.n = 0;
-                for (uint32_t tt = 0; tt < MM_MAX_TEAMS; ++tt) s_lb.cnt[tt] = 0;
-            }
-            tw_sort_load(S, nf, P, g, lane);
-            err |= tw_replay(s_lb, S, nf, M, lane);
-            if (s_lb.n != M.L) err |= MM_ERRF_SEAT_INVARIANT;
-            if (lane == 0 && !err) tl_write_lobby(P, g, s_lb, idx, pass);
-            if ((uint32_t)lane < nf) {
-                const uint32_t pos = S.spos[lane], role = (S.con[lane] >> 16) & 7u;
-                atomicSub(&P.chunk[((size_t)g * MM_MAX_ROLES + role) * P.chunk_stride + pos / TT_CH], 1u);
-            }
+            lobby_clear(s_lb, lane);
+            err = emit_members<TQ_CHUNK>(P, g, s_lb, S, nf, idx, pass, err, nullptr, lane);   // (the chaser took them out of the bitmap)
             wave_sync();
         }
         if (err && lane == 0) atomicOr(&s_err, err);

@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 from emu_engine import EmuEngine, EmuEngineSmall
-from helpers import assert_same_state, assert_same_tick, random_scenario
+from helpers import (ANCHOR_MOVES_PRODUCT, ANCHOR_MOVES_PRODUCT_IDS, assert_path_counts, assert_same_state, assert_same_tick, random_scenario,
+                     run_anchor_moves_to_the_emptied_first_team)
 from microservice_matchmaking_amd._abi import cons_make
 from microservice_matchmaking_amd.config import make_config, mode_1v1, mode_team
 
@@ -111,34 +112,36 @@ def test_team_anchor_moves_to_the_emptied_first_team(oracle_cls):
     tick's head meets the stale lobby (anchor A: rejected, it sits out the pass), the filter
     leaves team 2: [B] with B the anchor.  D fits B and is seated in the empty team 1, which makes
     D the anchor: E (fits D, not B) is taken, F (fits B, not D) is not; G completes the lobby a
-    tick later."""
-    cfg = make_config([mode_team(2, 2, 100, (2,))], capacity=4096)
-    others = 1000 + 5 * np.arange(70)                    # one rating group, nobody near 500
-    with EmuEngineSmall(cfg) as a, oracle_cls(cfg) as b:
-        def both(fn):
-            ra, rb = fn(a), fn(b)
-            return ra, rb
-        r1 = np.concatenate([[500, 510, 520], others]).astype(np.int32)
-        sa, sb = both(lambda e: e.enqueue(r1, cons_make(np.zeros(r1.size))))
-        assert np.array_equal(sa, sb)
-        ma, mb = both(lambda e: e.tick(0))
-        assert_same_tick(ma, mb, "tick 1")
-        assert_same_state(a, b, cfg, "tick 1")
-        slots, teams = a.lobby_state(0, 0)
-        assert slots.tolist() == [int(sa[0]), int(sa[2]), int(sa[1])] and teams.tolist() == [0, 0, 1]
-        both(lambda e: e.cancel(np.asarray([sa[0], sa[2]], np.uint32)))
-        r2 = np.asarray([600, 690, 450], np.int32)       # D, E, F
-        s2, _ = both(lambda e: e.enqueue(r2, cons_make(np.zeros(3))))
-        ma, mb = both(lambda e: e.tick(0))
-        assert_same_tick(ma, mb, "tick 2")
-        assert_same_state(a, b, cfg, "tick 2")
-        slots, teams = a.lobby_state(0, 0)
-        assert slots.tolist() == [int(s2[0]), int(sa[1]), int(s2[1])] and teams.tolist() == [0, 1, 1]
-        s3, _ = both(lambda e: e.enqueue(np.asarray([650], np.int32), cons_make(np.zeros(1))))
-        ma, mb = both(lambda e: e.tick(0))
-        assert_same_tick(ma, mb, "tick 3")
-        assert len(ma) >= 1 and ma.slots[0].tolist() == [int(s2[0]), int(s3[0]), int(sa[1]), int(s2[1])]
-        assert_same_state(a, b, cfg, "tick 3")
+    tick later.  (The scenario and its assertions: helpers.run_anchor_moves_to_the_emptied_first_team.)"""
+    run_anchor_moves_to_the_emptied_first_team(None, EmuEngineSmall, oracle_cls)
+
+
+@pytest.mark.parametrize("tuning,want", [
+    ({}, {2: {"crit_team_f_passes": 2, "crit_team_late_passes": 0},
+          3: {"team_late_launches": 1, "crit_team_late_passes": 3, "crit_team_f_passes": 0}}),
+    ({"team_f2": 0}, {2: {"crit_team_fc_passes": 2}}),
+    ({"team_f2": 1000, "team_split": 0}, {2: {"crit_team_f_passes": 2}}),      # the fill in the chase's own launch
+    ({"team_late": 0}, {3: {"crit_team_f_passes": 3}}),
+], ids=["default", "f2=0", "f2=1000-split=0", "late=0"])
+def test_one_pass_body_in_every_kernel_small_geometry(oracle_cls, tuning, want):
+    """What a pass does around its chase (mm_team.inc: tc_chaser's fill and kt_late's head_fill, the lobby left open,
+    pass_close, the kills) in every kernel that carries it, on the smallest scenario that runs it all at once — a stale
+    lobby, a head that sits out, an anchor that moves to the emptied team mid-fill, a lobby left open, then a stored lobby
+    that the head of the queue fills and that is emitted on the spot: tick 2's fill in kt_f's head-fill column (default), in
+    kt_fc, in kt_chase's own launch; tick 3's in kt_late (default) or in the pass kernels.  The path counters say which
+    kernel it was.  The anchor moves in tick 2 only, which a head that sat out keeps from kt_late: the restart of kt_late's
+    head_fill is not run here."""
+    stats, _ = run_anchor_moves_to_the_emptied_first_team(tuning, EmuEngineSmall, oracle_cls)
+    assert_path_counts(stats, want)
+
+
+@pytest.mark.parametrize("tuning,want", ANCHOR_MOVES_PRODUCT, ids=ANCHOR_MOVES_PRODUCT_IDS)
+def test_one_pass_body_in_every_kernel_product_geometry(oracle_cls, tuning, want):
+    """The same scenario at the product's geometry (TT_MIN = 4096: 4100 bystanders), as the device runs it
+    (test_gpu_parity.py has the twin); tick 3 emits 678 lobbies."""
+    stats, ma = run_anchor_moves_to_the_emptied_first_team(tuning, EmuEngine, oracle_cls, bystanders=4100, capacity=8192)
+    assert len(ma) == 678
+    assert_path_counts(stats, want)
 
 
 def test_team_extreme_ratings_fall_back(oracle_cls):

@@ -6,7 +6,8 @@ counters (pairs, scanned, passes, pool sizes) and lobby/queue state; scores with
 import numpy as np
 import pytest
 
-from helpers import assert_same_state, assert_same_tick, load_golden, random_scenario, run_full_tile_one_pass, run_golden_case
+from helpers import (ANCHOR_MOVES_PRODUCT, ANCHOR_MOVES_PRODUCT_IDS, assert_path_counts, assert_same_state, assert_same_tick, load_golden,
+                     random_scenario, run_anchor_moves_to_the_emptied_first_team, run_full_tile_one_pass, run_golden_case)
 from microservice_matchmaking_amd import cons_make, make_config, mode_1v1, mode_team
 from microservice_matchmaking_amd.synth import ROLE_WEIGHTS_5V5, make_pool
 
@@ -564,6 +565,18 @@ def test_gpu_team_late_kernel_forced(gpu_cls, oracle_cls, monkeypatch, late, lat
             assert_same_state(a, b, cfg, "kt_late forced tick %d" % tick)
             live = np.setdiff1d(live, ma.slots.ravel())
 
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tuning,want", ANCHOR_MOVES_PRODUCT, ids=ANCHOR_MOVES_PRODUCT_IDS)
+def test_gpu_team_one_pass_body_in_every_kernel(gpu_cls, oracle_cls, tuning, want):
+    """What a pass does around its chase (tc_chaser's fill and kt_late's head_fill, pass_close, the kills) in every kernel:
+    a stale lobby, a head that sits out, an anchor that moves to the emptied team mid-fill, a lobby left open, then a
+    stored lobby that the head of the queue fills (helpers.run_anchor_moves_to_the_emptied_first_team; the shim's twin is
+    tests/test_emu_team.py's).  The path counters say which kernel ran which pass."""
+    stats, ma = run_anchor_moves_to_the_emptied_first_team(tuning, gpu_cls, oracle_cls, bystanders=4100, capacity=8192,
+                                                           score_tol=SCORE_TOL)
+    assert len(ma) == 678
+    assert_path_counts(stats, want)
 
 
 @pytest.mark.gpu
