@@ -98,9 +98,11 @@ typedef struct mm_wait_group {
 } mm_wait_group;
 
 /* Sets the engine's clock.  The unit is the owner's (milliseconds of a monotonic clock is the
- * intended one); ages are computed modulo 2^32, which is exact while nobody waits 2^31 units.
- * The clock does not go backwards: MM_ERR_RANGE (and nothing changes) when
- * (int32_t)(now - current) < 0.  The FIRST call switches the feature on: stamp[capacity] is
+ * intended one); ages are (uint32_t)(clock - stamp), exact for every wait below 2^32 units: an age
+ * of 2^32 - 2 lands in histogram bucket 32 and is older than max_age = 2^32 - 3.  Only a single step
+ * is limited: the clock does not go backwards, MM_ERR_RANGE (and nothing changes) when
+ * (int32_t)(now - current) < 0, so one call advances it by 2^31 - 1 at the most (and a stamp handed
+ * to mm_enqueue_stamped is at most 2^31 - 1 behind the clock).  The FIRST call switches the feature on: stamp[capacity] is
  * allocated, every player already waiting is stamped `now`, and from then on mm_enqueue and
  * mm_enqueue_device stamp every accepted player with the clock's value at the call.
  * Reference: none (the deliveries of lib/search/worker.ex:352-358 carry no arrival time). */
