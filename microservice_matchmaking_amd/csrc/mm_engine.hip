@@ -935,7 +935,13 @@ __global__ __launch_bounds__(256) void k_wait_matched(PackArgs A, const uint32_t
     const uint32_t sl = out_slots[(size_t)g * A.out_slot_stride + (size_t)(i - A.pre[g] * A.L)];
     wait[i] = sl < capacity ? now - stamp[sl] : 0u;
 }
+// The three thresholds of matches_finish (tests/emu/results_check builds them small)
+#ifndef MM_PACK_MAX
 #define MM_PACK_MAX 8192u           // lobbies of a tick up to which its match list is packed on the device
+#endif
+#ifndef MM_MAIN_COPY_MAX
+#define MM_MAIN_COPY_MAX 8192u      // lobbies up to which a tick's tail that leaves as copy commands takes the engine's stream (beyond: the copy stream)
+#endif
 
 // The TAIL of a big tick's match list — what the last kernels of the walk emitted, after the last early send — straight
 // into the engine's pinned host buffers, each lobby at its final place (the buffers are device-accessible: hipHostMalloc).
@@ -962,7 +968,9 @@ __global__ __launch_bounds__(256) void k_results_tail(TailArgs A, const uint32_t
     h_score[at] = out_score[(size_t)g * A.out_rec_stride + j];
     h_pass[at] = out_pass[(size_t)g * A.out_rec_stride + j];
 }
+#ifndef MM_TAIL_MAX
 #define MM_TAIL_MAX (1u << 20)       // lobbies up to which a tick's tail leaves through k_results_tail (beyond: copy commands)
+#endif
 
 // A look of the host at the chains' records in the middle of a tick (pair path: after every batch of passes; team path:
 // every 16 passes) is a D2H copy of 3 KB and a stream synchronisation.  The alternative built in round 5 (VERDICT r04,
@@ -1016,6 +1024,44 @@ struct WaitLists {
         slot.clear(); group.clear(); age.clear(); new_slot.clear();
         rating.clear(); cons.clear(); stamp.clear();
     }
+};
+
+// The match list of a tick on the host, group-major emission order.  It travels while the walk is
+// still running: at every look the host takes at the chains, the lobbies emitted since the last look go out on a stream
+// of their own (emission lists only grow).  Group g's lobbies live at h_r*[r_base[g] ..) — r_base from the most a group
+// can emit (its players at the start of the tick), so a lobby's place is known before the tick is over; r_cnt / r_pre
+// index them for mm_matches.  Only the matches_* functions touch a field (engine_init, mm_clock_set and
+// mm_engine_destroy make and free the stream, the event and the buffers).  What they keep:
+//   1. r_marked[g] <= r_sent[g] <= the group's n_out, for every group, at every moment of a tick;
+//   2. a matched player's slot is set FREE in h_state exactly once: by matches_mark, which only moves r_marked up;
+//   3. a region of the pinned buffers is read only after the copy that fills it has been waited for: r_marked follows
+//      r_sent behind ev_copy (matches_absorb) or behind the tick's last synchronisation (matches_close);
+//   4. emission index i of the tick, r_pre[g] <= i < r_pre[g + 1], is stored at r_base[g] + (i - r_pre[g]) (matches_read).
+enum MatchRoute {              // how the end of a tick's list reaches the host (matches_finish)
+    MR_NONE,                   // nothing was left to send
+    MR_PACKED,                 // k_pack_results and three copies on the engine's stream: a small tick that sent nothing early
+    MR_TAIL,                   // k_results_tail on the engine's stream
+    MR_COPY_MAIN,              // copy commands on the engine's stream
+    MR_COPY_STREAM             // copy commands on the copy stream, behind ev_copy (the only route of a look mid-walk)
+};
+static inline bool route_on_engine_stream(MatchRoute r) { return r == MR_PACKED || r == MR_TAIL || r == MR_COPY_MAIN; }
+struct MatchList {
+    std::vector<uint32_t> r_released;   // the slots the liveness filter released in the tick
+    uint32_t* h_rslots;        // pinned: the last tick's lobbies (slots, score, pass), emission order
+    float* h_rscore;
+    uint32_t* h_rpass;
+    uint32_t r_n, r_L;
+    hipStream_t copy_stream;
+    hipEvent_t ev_copy;
+    bool ev_copy_pending;
+    uint32_t r_base[MM_MAX_GROUPS], r_cnt[MM_MAX_GROUPS], r_pre[MM_MAX_GROUPS + 1];
+    uint32_t r_sent[MM_MAX_GROUPS];     // lobbies of the running tick already on their way / arrived
+    uint32_t r_marked[MM_MAX_GROUPS];   // ... whose players' slots are FREE in h_state already
+    bool r_based;
+    MatchRoute route;          // the route matches_finish took: matches_close marks what came on the engine's stream
+    uint32_t* h_mwait;         // pinned, as large as d_wt_matched: mm_matches_wait, emission order, r_L words a lobby
+    uint32_t mw_n;             // lobbies of the last tick h_mwait covers (0: the clock was off at that tick)
+    void drop() { r_n = 0; mw_n = 0; }   // no list: mm_matches and mm_matches_wait answer MM_ERR_RANGE for all but an empty window
 };
 
 struct mm_engine {
@@ -1100,22 +1146,7 @@ struct mm_engine {
     std::vector<uint8_t> h_state;
     uint32_t next_slot;
     uint32_t cancel_pending;
-    std::vector<uint32_t> r_released;
-    uint32_t* h_rslots;        // pinned: the last tick's lobbies (slots, score, pass), emission order
-    float* h_rscore;
-    uint32_t* h_rpass;
-    uint32_t r_n, r_L;
-    // The match list travels while the walk is still running: at every look the host takes at the chains, the
-    // lobbies emitted since the last look go out on a stream of their own (emission lists only grow).  Group g's
-    // lobbies live at h_r*[r_base[g] ..) — r_base from the most a group can emit (its players at the start of the
-    // tick), so a lobby's place is known before the tick is over; r_cnt / r_pre index them for mm_matches.
-    hipStream_t copy_stream;
-    hipEvent_t ev_copy;
-    bool ev_copy_pending;
-    uint32_t r_base[MM_MAX_GROUPS], r_cnt[MM_MAX_GROUPS], r_pre[MM_MAX_GROUPS + 1];
-    uint32_t r_sent[MM_MAX_GROUPS];     // lobbies of the running tick already on their way / arrived
-    uint32_t r_marked[MM_MAX_GROUPS];   // ... whose players' slots are FREE in h_state already
-    bool r_based;
+    MatchList ml;              // the last tick's lobbies on the host (mm_matches, mm_matches_wait)
     bool poisoned;             // a tick failed half way: everything but reset / restore / destroy answers MM_ERR_STATE
     uint32_t ticks_seen;       // mm_ticks of this engine so far (tn.fail_tick)
     // the clock (include/mm_wait.h): nothing below is allocated, and no kernel of it runs, before the first mm_clock_set
@@ -1129,8 +1160,6 @@ struct mm_engine {
     WaitLists x;               // the last marking call's list (mm_expired, mm_moved, mm_moved_rows)
     uint32_t* d_mv_cols;       // [4][capacity] mm_move's rows: rating | constraint word | stamp | new slot (allocated at the first mm_move)
     uint8_t* d_mv_group;       // [capacity] ... and their rating groups, the column k_bucket_* take
-    uint32_t* h_mwait;         // pinned, as large as d_wt_matched: mm_matches_wait, emission order, r_L words a lobby
-    uint32_t mw_n;             // lobbies of the last tick h_mwait covers (0: the clock was off at that tick)
     // mm_locate (include/mm_wait.h): nothing below is allocated, and no kernel of it runs, before the first mm_locate
     uint32_t* d_loc_tag;       // [capacity] query + 1 of a queried slot while a call runs; all zero between calls
     uint32_t* d_loc_rows;      // [wait_max_chunks][WT_ROWS] + 1: d_wt_rows' layout, a buffer of the call's own (the clock may be off)
@@ -1424,9 +1453,9 @@ extern "C" void mm_engine_destroy(mm_engine* e)
         if (e->ev_nx[i]) (void)hipEventDestroy(e->ev_nx[i]);
     for (uint32_t i = 0; i < MM_MAX_GROUPS; ++i)
         if (e->ev_grp[i]) (void)hipEventDestroy(e->ev_grp[i]);
-    if (e->ev_copy_pending) (void)hipEventSynchronize(e->ev_copy);     // (nothing of this engine is left on the shared stream)
-    if (e->copy_stream) { e->copy_stream = nullptr; copy_stream_release(e->cfg.device); }
-    if (e->ev_copy) (void)hipEventDestroy(e->ev_copy);
+    if (e->ml.ev_copy_pending) (void)hipEventSynchronize(e->ml.ev_copy);     // (nothing of this engine is left on the shared stream)
+    if (e->ml.copy_stream) { e->ml.copy_stream = nullptr; copy_stream_release(e->cfg.device); }
+    if (e->ml.ev_copy) (void)hipEventDestroy(e->ml.ev_copy);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1574,8 +1603,8 @@ static int engine_init(mm_engine* e)
     for (int i = 0; i < 4; ++i) HIPCHK(e, hipEventCreate(&e->ev[i]));
     for (int i = 0; i < 2; ++i) HIPCHK(e, hipEventCreate(&e->ev_nx[i]));
     for (uint32_t i = 0; i < cfg->n_groups; ++i) HIPCHK(e, hipEventCreate(&e->ev_grp[i]));
-    if (copy_stream_acquire(cfg->device, &e->copy_stream)) { e->copy_stream = nullptr; return MM_ERR_HIP; }
-    HIPCHK(e, hipEventCreate(&e->ev_copy));
+    if (copy_stream_acquire(cfg->device, &e->ml.copy_stream)) { e->ml.copy_stream = nullptr; return MM_ERR_HIP; }
+    HIPCHK(e, hipEventCreate(&e->ml.ev_copy));
     MMTRY(dev_alloc(e, e->d_q_rating, e->n_chains * cap * sizeof(int32_t)));
     MMTRY(dev_alloc(e, e->d_q_cons, e->n_chains * cap * sizeof(uint32_t)));
     MMTRY(dev_alloc(e, e->d_q_slot, e->n_chains * cap * sizeof(uint32_t)));
@@ -1621,9 +1650,9 @@ static int engine_init(mm_engine* e)
         MMTRY(pin_alloc(e, e->h_pchains, cfg->n_groups * sizeof(PairChain)));
         // a tick emits at most (cap + lobby) / 2 lobbies per group, cap + lobbies-in-progress players overall
         // (+ one lobby of slack per group: a group's region is sized by the players it holds when the tick begins)
-        MMTRY(pin_alloc(e, e->h_rslots, (cap + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(uint32_t)));
-        MMTRY(pin_alloc(e, e->h_rscore, (cap / 2 + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(float)));
-        MMTRY(pin_alloc(e, e->h_rpass, (cap / 2 + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(uint32_t)));
+        MMTRY(pin_alloc(e, e->ml.h_rslots, (cap + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(uint32_t)));
+        MMTRY(pin_alloc(e, e->ml.h_rscore, (cap / 2 + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(float)));
+        MMTRY(pin_alloc(e, e->ml.h_rpass, (cap / 2 + (size_t)3 * MM_MAX_LOBBY * cfg->n_groups + 64) * sizeof(uint32_t)));
         HIPCHK(e, hipMemsetAsync(e->d_pchains, 0, cfg->n_groups * sizeof(PairChain), e->stream));
         e->tk_chunk_stride = (uint32_t)(e->pk_stride / TT_CH + 2);
         MMTRY(dev_alloc(e, e->d_tchains, cfg->n_groups * sizeof(TeamChain)));
@@ -1694,7 +1723,7 @@ extern "C" int mm_engine_create_ex(const mm_config* cfg, const mm_tuning* tuning
         e->cfg = *cfg;
         e->tn = tn;
         e->n_chains = cfg->n_modes * cfg->n_groups;
-        e->r_L = 2;
+        e->ml.r_L = 2;
         e->ps.mode = 0xFFFFFFFFu;
         const int rc = guarded([&]() -> int { return engine_init(e); });
         if (rc) { mm_engine_destroy(e); return rc; }
@@ -1711,8 +1740,7 @@ extern "C" int mm_reset(mm_engine* e)
         std::fill(e->h_state.begin(), e->h_state.end(), (uint8_t)MM_ST_FREE);
         e->next_slot = 0;
         e->cancel_pending = 0;
-        e->r_n = 0;
-        e->mw_n = 0;
+        e->ml.drop();
         e->x.clear();                                      // (the clock itself goes on: include/mm_wait.h)
         e->live_upper = 0;
         std::fill(e->tk_last_len.begin(), e->tk_last_len.end(), 0u);
@@ -1987,94 +2015,259 @@ extern "C" int mm_cancel(mm_engine* e, uint32_t n, const uint32_t* slot)
 #ifndef MM_RESULTS_MIN_TEAM
 #define MM_RESULTS_MIN_TEAM 4096u
 #endif
-// r_base: where group g's lobbies live in h_r*.  `before[g]`: the players the group holds as the tick begins (queue +
-// stored lobby + cancelled entries): it cannot emit more than before / L lobbies.
-static void results_set_bases(mm_engine* e, const uint32_t* before, uint32_t L)
+// What a tick's chains say when its walk is over (h_chains), gathered in one loop over them (tick_totals).
+struct TickTotals {
+    uint32_t total, after, before, pmax, err;   // lobbies | players after, before | the most passes of a chain | the chains' error flags
+    unsigned long long pairs, scanned;
+    uint32_t n_out[MM_MAX_GROUPS], had[MM_MAX_GROUPS], left[MM_MAX_GROUPS];   // per group: lobbies | players before | queue + stored lobby after
+};
+
+// A tick begins: nothing sent, nothing placed; a copy event a failed tick left pending is drained.
+static void matches_open(mm_engine* e, uint32_t L)
 {
-    uint32_t run = 0;
-    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) {
-        e->r_base[g] = run;
-        run += before[g] / L + 1u;
-    }
-    e->r_based = true;
+    MatchList& m = e->ml;
+    m.r_n = 0; m.mw_n = 0; m.r_L = L;
+    if (m.ev_copy_pending) { (void)hipEventSynchronize(m.ev_copy); m.ev_copy_pending = false; }   // (a tick that failed half way)
+    m.r_based = false; m.route = MR_NONE;
+    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) { m.r_sent[g] = 0; m.r_marked[g] = 0; m.r_cnt[g] = 0; }
 }
 
-// the players of lobbies [from, to) of group g are matched: their slots are FREE again (ActiveUser.remove_user for
-// the matched players, game-lobby/worker.ex:73-103)
-static void results_mark(mm_engine* e, uint32_t g, uint32_t to, uint32_t L)
+// The first look of a tick at its chains sizes the groups' regions (r_base); later calls change nothing.  `before[g]`:
+// the players the group holds as the tick begins (queue + stored lobby + cancelled entries): it cannot emit more than
+// before / L lobbies.
+static void matches_place(mm_engine* e, const uint32_t* before)
 {
-    const uint32_t from = e->r_marked[g];
+    MatchList& m = e->ml;
+    if (m.r_based) return;
+    uint32_t run = 0;
+    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) {
+        m.r_base[g] = run;
+        run += before[g] / m.r_L + 1u;
+    }
+    m.r_based = true;
+}
+
+// the players of lobbies [r_marked[g], to) of group g are matched: their slots are FREE again (ActiveUser.remove_user for
+// the matched players, game-lobby/worker.ex:73-103)
+static void matches_mark(mm_engine* e, uint32_t g, uint32_t to)
+{
+    MatchList& m = e->ml;
+    const uint32_t from = m.r_marked[g], L = m.r_L;
     if (to <= from) return;
-    const uint32_t* const sl = e->h_rslots + (size_t)(e->r_base[g] + from) * L;
-    for (size_t i = 0, n = (size_t)(to - from) * L; i < n; ++i) e->h_state[sl[i]] = MM_ST_FREE;
-    e->r_marked[g] = to;
+    const uint32_t* const sl = m.h_rslots + (size_t)(m.r_base[g] + from) * L;
+    uint8_t* const state = e->h_state.data();
+    for (size_t i = 0, n = (size_t)(to - from) * L; i < n; ++i) state[sl[i]] = MM_ST_FREE;
+    m.r_marked[g] = to;
 }
 
 // what arrived with the last batch of copies: release the slots (host work while the device walks on)
-static int results_absorb(mm_engine* e, uint32_t L)
+static int matches_absorb(mm_engine* e)
 {
-    if (!e->ev_copy_pending) return MM_OK;
-    HIPCHK(e, hipEventSynchronize(e->ev_copy));
-    e->ev_copy_pending = false;
-    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) results_mark(e, g, e->r_sent[g], L);
+    MatchList& m = e->ml;
+    if (!m.ev_copy_pending) return MM_OK;
+    HIPCHK(e, hipEventSynchronize(m.ev_copy));
+    m.ev_copy_pending = false;
+    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) matches_mark(e, g, m.r_sent[g]);
     return MM_OK;
 }
 
-// lobbies [r_sent[g], n_out[g]) of every group go out on the copy stream.  The emission lists only grow and every
+// lobbies [r_sent[g], n_out[g]) of every group leave as copy commands on `st`.  The emission lists only grow and every
 // kernel that wrote entries below n_out has finished (the caller has just synchronised the engine stream).
-static int results_send(mm_engine* e, const uint32_t* n_out, uint32_t L, uint32_t min_new, bool* on_main = nullptr)
+static int matches_copy(mm_engine* e, const uint32_t* n_out, hipStream_t st)
+{
+    MatchList& m = e->ml;
+    const uint32_t L = m.r_L;
+    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) {
+        const uint32_t a = m.r_sent[g], b = n_out[g];
+        if (b <= a) continue;
+        const size_t at = (size_t)m.r_base[g] + a;
+        HIPCHK(e, hipMemcpyAsync(&m.h_rslots[at * L], e->d_out_slots + (size_t)g * e->out_slot_stride + (size_t)a * L,
+                                 (size_t)(b - a) * L * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipMemcpyAsync(&m.h_rscore[at], e->d_out_score + (size_t)g * e->out_rec_stride + a, (size_t)(b - a) * sizeof(float),
+                                 hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipMemcpyAsync(&m.h_rpass[at], e->d_out_pass + (size_t)g * e->out_rec_stride + a, (size_t)(b - a) * sizeof(uint32_t),
+                                 hipMemcpyDeviceToHost, st));
+        m.r_sent[g] = b;
+    }
+    if (st == e->stream) return MM_OK;                   // (matches_close marks them, after the tick's last synchronisation)
+    HIPCHK(e, hipEventRecord(m.ev_copy, m.copy_stream));
+    m.ev_copy_pending = true;
+    return MM_OK;
+}
+
+// ... as ONE launch of k_results_tail on the engine's stream
+static int matches_tail(mm_engine* e, const uint32_t* n_out)
+{
+    MatchList& m = e->ml;
+    TailArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_groups = e->cfg.n_groups; A.L = m.r_L; A.out_slot_stride = e->out_slot_stride; A.out_rec_stride = e->out_rec_stride;
+    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) {
+        const uint32_t a = m.r_sent[g], b = n_out[g] > a ? n_out[g] : a;
+        A.from[g] = a; A.base[g] = m.r_base[g]; A.pre[g + 1u] = A.pre[g] + (b - a);
+        m.r_sent[g] = b;
+    }
+    A.total = A.pre[e->cfg.n_groups];
+    if (!A.total) return MM_OK;
+    hipLaunchKernelGGL(k_results_tail, dim3((A.total + 255u) / 256u), dim3(256), 0, e->stream, A, e->d_out_slots, e->d_out_score,
+                       e->d_out_pass, m.h_rslots, m.h_rscore, m.h_rpass);
+    HIPCHK(e, hipGetLastError());
+    return MM_OK;
+}
+
+// The tick's lobbies as k_pack_results and k_wait_matched address them: group g's at its prefix.
+static PackArgs pack_args(const mm_engine* e, const TickTotals& T)
+{
+    PackArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_groups = e->cfg.n_groups; A.L = e->ml.r_L; A.total = T.total; A.out_slot_stride = e->out_slot_stride; A.out_rec_stride = e->out_rec_stride;
+    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) A.pre[g + 1u] = A.pre[g] + T.n_out[g];
+    return A;
+}
+
+// ... the whole list of a small tick in one packed piece, tight layout (group g at its prefix): k_pack_results and three copies
+static int matches_pack(mm_engine* e, const TickTotals& T)
+{
+    MatchList& m = e->ml;
+    const uint32_t L = m.r_L, total = T.total;
+    const PackArgs A = pack_args(e, T);
+    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) { m.r_base[g] = A.pre[g]; m.r_sent[g] = T.n_out[g]; }
+    m.r_based = true;
+    hipLaunchKernelGGL(k_pack_results, dim3((total + 255u) / 256u), dim3(256), 0, e->stream, A, e->d_out_slots, e->d_out_score,
+                       e->d_out_pass, e->d_pack);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(m.h_rslots, e->d_pack, (size_t)total * L * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(m.h_rscore, e->d_pack + (size_t)total * L, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(m.h_rpass, e->d_pack + (size_t)total * (L + 1u), (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    return MM_OK;
+}
+
+static uint32_t matches_fresh(const mm_engine* e, const uint32_t* n_out)
 {
     uint32_t fresh = 0;
-    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) fresh += n_out[g] > e->r_sent[g] ? n_out[g] - e->r_sent[g] : 0u;
-    if (on_main) *on_main = false;
-    if (fresh < min_new) return MM_OK;
-    MMTRY(results_absorb(e, L));                       // one batch of copies in flight at a time
-    // the end of a tick with little left to send (every tick of a stream): on the engine's own stream, behind the
-    // walk — the caller synchronises that stream anyway, and a second stream's event would be one more round trip
-    if (on_main != nullptr && fresh <= MM_TAIL_MAX && e->tn.results_tail) {
-        TailArgs A;
-        memset(&A, 0, sizeof(A));
-        A.n_groups = e->cfg.n_groups; A.L = L; A.out_slot_stride = e->out_slot_stride; A.out_rec_stride = e->out_rec_stride;
-        for (uint32_t g = 0; g < e->cfg.n_groups; ++g) {
-            const uint32_t a = e->r_sent[g], b = n_out[g] > a ? n_out[g] : a;
-            A.from[g] = a; A.base[g] = e->r_base[g]; A.pre[g + 1u] = A.pre[g] + (b - a);
-            e->r_sent[g] = b;
-        }
-        A.total = A.pre[e->cfg.n_groups];
-        if (A.total) {
-            hipLaunchKernelGGL(k_results_tail, dim3((A.total + 255u) / 256u), dim3(256), 0, e->stream, A, e->d_out_slots, e->d_out_score,
-                               e->d_out_pass, e->h_rslots, e->h_rscore, e->h_rpass);
-            HIPCHK(e, hipGetLastError());
-        }
-        *on_main = true;                                 // the caller marks the slots after its own synchronisation
-        return MM_OK;
+    for (uint32_t g = 0; g < e->cfg.n_groups; ++g) fresh += n_out[g] > e->ml.r_sent[g] ? n_out[g] - e->ml.r_sent[g] : 0u;
+    return fresh;
+}
+
+// In the middle of the walk, host work while the device runs a batch: what the last look's copies brought (slots
+// released), then the lobbies of this look behind them on the copy stream (n_out; nullptr: none yet) if they are worth
+// a batch of copies (`min_new`, with results_early).  One batch of copies is in flight at a time.
+static int matches_ship(mm_engine* e, const uint32_t* n_out, uint32_t min_new)
+{
+    MMTRY(matches_absorb(e));
+    if (!n_out || !e->tn.results_early || matches_fresh(e, n_out) < min_new) return MM_OK;
+    return matches_copy(e, n_out, e->ml.copy_stream);
+}
+
+// THE choice of a route for the end of a tick's list: `fresh` of its `total` lobbies have not left yet.
+static MatchRoute matches_route(bool based, uint32_t total, uint32_t fresh, const mm_tuning& tn)
+{
+    if (!based && total > 0u && total <= MM_PACK_MAX) return MR_PACKED;   // no look was taken and the tick is small (every tick of a stream)
+    if (fresh == 0u) return MR_NONE;
+    // little left to send: on the engine's own stream, behind the walk — the caller synchronises that stream anyway, and a
+    // second stream's event would be one more round trip
+    if (fresh <= MM_TAIL_MAX && tn.results_tail) return MR_TAIL;
+    return fresh <= MM_MAIN_COPY_MAX ? MR_COPY_MAIN : MR_COPY_STREAM;
+}
+
+// The end of a tick, its walk synchronised and its counts final (T).  Most of the list left for the host while the walk
+// was still running (matches_ship at every look at the chains); what the last kernels emitted follows now.  A count that
+// cannot be answers MM_ERR_INTERNAL before anything is sent.  What arrives on the engine's stream is marked by
+// matches_close, after the caller's synchronisation (ml.route says so).
+static int matches_finish(mm_engine* e, const TickTotals& T)
+{
+    MatchList& m = e->ml;
+    const uint32_t G = e->cfg.n_groups, L = m.r_L;
+    if ((size_t)T.total * L > (size_t)e->cfg.capacity + (size_t)MM_MAX_LOBBY * G) return MM_ERR_INTERNAL;
+    uint32_t tight[MM_MAX_GROUPS];
+    for (uint32_t g = 0; g < G; ++g) {
+        if (m.r_based && (T.n_out[g] < m.r_sent[g] || (unsigned long long)T.n_out[g] * L > (unsigned long long)T.had[g] + L))
+            return MM_ERR_INTERNAL;
+        tight[g] = T.n_out[g] * L;                           // (a tick without a look: the counts are final)
     }
-    const bool main_st = on_main != nullptr && fresh <= 8192u;
-    hipStream_t const st = main_st ? e->stream : e->copy_stream;
+    m.route = matches_route(m.r_based, T.total, matches_fresh(e, T.n_out), e->tn);
+    if (m.route != MR_PACKED) matches_place(e, tight);
+    if (m.route != MR_PACKED && m.route != MR_NONE) MMTRY(matches_absorb(e));   // one batch of copies in flight at a time
+    switch (m.route) {
+    case MR_NONE: return MM_OK;
+    case MR_PACKED: return matches_pack(e, T);
+    case MR_TAIL: return matches_tail(e, T.n_out);
+    case MR_COPY_MAIN: return matches_copy(e, T.n_out, e->stream);
+    case MR_COPY_STREAM: return matches_copy(e, T.n_out, m.copy_stream);
+    }
+    return MM_ERR_INTERNAL;
+}
+
+// ... behind it on the engine's stream: the slots the liveness filter released (h_counters[0] of them), and
+// mm_matches_wait — the waits of the matched, while their stamps are still theirs (the emission logs are final).  Queued
+// BEHIND the match list's tail, so the list reaches the host as early as without the clock; the copies go into memory
+// the tick's last synchronisation covers.  Then the host's part for what the copy stream has brought meanwhile.
+static int matches_extras(mm_engine* e, const TickTotals& T, uint32_t* n_released)
+{
+    MatchList& m = e->ml;
+    const uint32_t nrel = *n_released = e->h_counters[0];
+    m.r_released.resize(nrel);
+    if (nrel)
+        HIPCHK(e, hipMemcpyAsync(m.r_released.data(), e->d_released, nrel * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    if (e->clock_on && T.total > 0u) {
+        const PackArgs A = pack_args(e, T);
+        const uint32_t words = T.total * m.r_L;
+        hipLaunchKernelGGL(k_wait_matched, dim3((words + 255u) / 256u), dim3(256), 0, e->stream, A, e->d_out_slots, e->d_stamp,
+                           e->cfg.capacity, e->clock_now, e->d_wt_matched);
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipMemcpyAsync(m.h_mwait, e->d_wt_matched, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    }
+    return matches_absorb(e);
+}
+
+// After the tick's last synchronisation: what came on the engine's stream is marked, the released slots are FREE, and
+// the list is there for mm_matches (r_cnt, r_pre, r_n).
+static void matches_close(mm_engine* e, const TickTotals& T)
+{
+    MatchList& m = e->ml;
+    if (route_on_engine_stream(m.route))
+        for (uint32_t g = 0; g < e->cfg.n_groups; ++g) matches_mark(e, g, m.r_sent[g]);
+    uint8_t* const state = e->h_state.data();
+    const uint32_t* const rel = m.r_released.data();
+    for (size_t i = 0, n = m.r_released.size(); i < n; ++i) state[rel[i]] = MM_ST_FREE;
+    m.r_pre[0] = 0;
     for (uint32_t g = 0; g < e->cfg.n_groups; ++g) {
-        const uint32_t a = e->r_sent[g], b = n_out[g];
-        if (b <= a) continue;
-        const size_t at = (size_t)e->r_base[g] + a;
-        HIPCHK(e, hipMemcpyAsync(&e->h_rslots[at * L], e->d_out_slots + (size_t)g * e->out_slot_stride + (size_t)a * L,
-                                 (size_t)(b - a) * L * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipMemcpyAsync(&e->h_rscore[at], e->d_out_score + (size_t)g * e->out_rec_stride + a, (size_t)(b - a) * sizeof(float),
-                                 hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipMemcpyAsync(&e->h_rpass[at], e->d_out_pass + (size_t)g * e->out_rec_stride + a, (size_t)(b - a) * sizeof(uint32_t),
-                                 hipMemcpyDeviceToHost, st));
-        e->r_sent[g] = b;
+        m.r_cnt[g] = T.n_out[g];
+        m.r_pre[g + 1u] = m.r_pre[g] + T.n_out[g];
     }
-    if (main_st) { *on_main = true; return MM_OK; }      // the caller marks the slots after its own synchronisation
-    HIPCHK(e, hipEventRecord(e->ev_copy, e->copy_stream));
-    e->ev_copy_pending = true;
+    m.r_n = T.total;
+    m.mw_n = e->clock_on ? T.total : 0u;
+}
+
+// mm_matches: lobbies [first, first + count) of the last tick, emission order
+static int matches_read(const mm_engine* e, uint32_t first, uint32_t count, uint32_t* slots, float* score, uint32_t* group, uint32_t* pass)
+{
+    const MatchList& m = e->ml;
+    if (first > m.r_n || count > m.r_n - first) return MM_ERR_RANGE;
+    // emission index i of the tick = lobby i - r_pre[g] of group g, stored at r_base[g] + that
+    const uint32_t L = m.r_L;
+    // (Round 5, measured and taken out: the 10 MB of a big tick's list copied by four threads in 256 KB pieces —
+    // 10.01-10.28 ms a step with one thread, 10.03-10.26 with four, profiles/r05_ab_pair_micro.txt.)
+    for (uint32_t g = 0; count && g < e->cfg.n_groups; ++g) {
+        const uint32_t lo = m.r_pre[g] > first ? m.r_pre[g] : first;
+        const uint32_t hi = m.r_pre[g + 1u] < first + count ? m.r_pre[g + 1u] : first + count;
+        if (hi <= lo) continue;
+        const size_t src = (size_t)m.r_base[g] + (lo - m.r_pre[g]), dst = lo - first, n = hi - lo;
+        if (slots) memcpy(slots + dst * L, &m.h_rslots[src * L], n * L * sizeof(uint32_t));
+        if (score) memcpy(score + dst, &m.h_rscore[src], n * sizeof(float));
+        if (pass) memcpy(pass + dst, &m.h_rpass[src], n * sizeof(uint32_t));
+        if (group) std::fill_n(group + dst, n, g);
+    }
     return MM_OK;
 }
 
-// Host work while the device runs a batch: what the last look's copies brought (slots released), then the lobbies of
-// this look behind them (n_out; nullptr: none yet) if they are worth a batch of copies (`min_new`, with results_early).
-static int results_ship(mm_engine* e, const uint32_t* n_out, uint32_t L, uint32_t min_new)
+// mm_matches_wait: the waits of those lobbies' players, L words a lobby
+static int matches_read_wait(const mm_engine* e, uint32_t first, uint32_t count, uint32_t* wait)
 {
-    MMTRY(results_absorb(e, L));
-    return n_out ? results_send(e, n_out, L, e->tn.results_early ? min_new : 0xFFFFFFFFu) : MM_OK;
+    const MatchList& m = e->ml;
+    if (first > m.mw_n || count > m.mw_n - first) return MM_ERR_RANGE;
+    if (count && wait) memcpy(wait, &m.h_mwait[(size_t)first * m.r_L], (size_t)count * m.r_L * sizeof(uint32_t));
+    return MM_OK;
 }
 
 // A look at device records through the pinned buffer (k_look): look_launch enqueues the hand-over behind whatever the
@@ -2433,7 +2626,7 @@ static int pair_launch(mm_engine* e, const PairParams& P, const PairPlan& pl, ui
 
 static void report_pair_look(const mm_engine* e, uint32_t guard, uint32_t last_tp);
 // A look at the chains' records (h_pchains), and what the engine keeps of every look.
-static int pair_look(mm_engine* e, uint32_t G, uint32_t L, uint32_t guard, uint32_t last_tp)
+static int pair_look(mm_engine* e, uint32_t G, uint32_t guard, uint32_t last_tp)
 {
     MMTRY(look_launch(e, e->d_pchains, e->h_pchains, G * sizeof(PairChain)));
     MMTRY(look_wait(e));
@@ -2446,7 +2639,7 @@ static int pair_look(mm_engine* e, uint32_t G, uint32_t L, uint32_t guard, uint3
         e->ps_hand[0][g] = pc.fast ? pc.passes : 0u; e->ps_hand[1][g] = pc.fast ? pc.n_out : 0u;
         e->ps_hand[2][g] = pc.fast ? pc.ppass : 0u; e->ps_hand[3][g] = pc.fast ? pc.ptm[15] : 0u;
     }
-    if (!e->r_based) results_set_bases(e, bf, L);   // (the first look sizes the groups' regions of the match list)
+    matches_place(e, bf);
     return MM_OK;
 }
 
@@ -2466,19 +2659,19 @@ static int pair_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge)
         const mm_tuning tn = e->tn;
         PairLoop loop;
         for (uint32_t guard = 0;; ++guard) {
-            MMTRY(pair_look(e, G, M.L, guard, loop.last_tp));
+            MMTRY(pair_look(e, G, guard, loop.last_tp));
             MMTRY(pair_plan(e->h_pchains, G, tn, loop, e->kpr, e->ps, P, plan));
             if (plan.next == PN_DONE) break;
             MMTRY(pair_launch(e, P, plan, G));
             // the lobbies emitted so far leave for the host while the batch runs; the copies are enqueued BEHIND the
             // batch's launches: the device does not wait for the host's calls
-            if (plan.ship) MMTRY(results_ship(e, plan.sent_no, M.L, MM_RESULTS_MIN_PAIR));
+            if (plan.ship) MMTRY(matches_ship(e, plan.sent_no, MM_RESULTS_MIN_PAIR));
         }
     }
     hipLaunchKernelGGL(kp_late, dim3(G), dim3(PL_THREADS), 0, e->stream, P);
     hipLaunchKernelGGL(kp_finish, dim3(G), dim3(1024), 0, e->stream, P);
     HIPCHK(e, hipGetLastError());
-    if (plan.ship) MMTRY(results_ship(e, plan.sent_no, M.L, MM_RESULTS_MIN_PAIR));   // (behind kp_late's launch, as above)
+    if (plan.ship) MMTRY(matches_ship(e, plan.sent_no, MM_RESULTS_MIN_PAIR));   // (behind kp_late's launch, as above)
     return MM_OK;
 }
 
@@ -2715,7 +2908,7 @@ static int team_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge, 
         for (uint32_t g = 0; g < G; ++g) p0[g] = tcs[g].passes;
         MMTRY(look_launch(e, e->d_tchains, e->h_tchains, G * sizeof(TeamChain)));
         // host work while the device runs the batch: what the last look's copies brought, then this look's lobbies
-        MMTRY(results_ship(e, team_have ? team_no : nullptr, M.L, MM_RESULTS_MIN_TEAM));
+        MMTRY(matches_ship(e, team_have ? team_no : nullptr, MM_RESULTS_MIN_TEAM));
         MMTRY(look_wait(e));
         ++e->ps.host_looks;
         if (tn.debug && was_late) report_team_late(e, p0);
@@ -2729,7 +2922,7 @@ static int team_walk(mm_engine* e, uint32_t mode, const ModeDev& M, bool purge, 
             if (tcs[g].fast) fl += tcs[g].flags_late;
         }
         e->ps.team_flags_late = fl;
-        if (!e->r_based) results_set_bases(e, bf, M.L);
+        matches_place(e, bf);
         team_have = true;
         if (!team_plan(tcs, G, tn, L)) break;
         fo_total = team_order(P, tcs, G);
@@ -2881,61 +3074,25 @@ static void path_stats_team(mm_engine* e)
     }
 }
 
-// The tick's lobbies as k_pack_results and k_wait_matched address them: group g's at its prefix (h_chains holds the tick's counts).
-static PackArgs pack_args(const mm_engine* e, uint32_t mode, uint32_t L, uint32_t total)
+// Stage 1 of a tick: its record for mm_path_stats_get (the totals go on), an empty match list, the released-slots counter.
+static int tick_open(mm_engine* e, uint32_t mode, uint32_t L)
 {
-    const uint32_t G = e->cfg.n_groups;
-    PackArgs A;
-    memset(&A, 0, sizeof(A));
-    A.n_groups = G; A.L = L; A.total = total; A.out_slot_stride = e->out_slot_stride; A.out_rec_stride = e->out_rec_stride;
-    for (uint32_t g = 0; g < G; ++g) A.pre[g + 1u] = A.pre[g] + e->h_chains[mode * G + g].n_out;
-    return A;
+    const uint32_t tot = e->ps.team_flags_late_total;
+    memset(&e->ps, 0, sizeof(e->ps));
+    e->ps.mode = mode;
+    e->ps.team_flags_late_total = tot;
+    matches_open(e, L);
+    HIPCHK(e, hipMemsetAsync(e->d_counters, 0, sizeof(uint32_t), e->stream));
+    return MM_OK;
 }
 
-static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats* stats);
-
-// The exported tick: nothing may unwind into the caller (a NIF frame), and a tick that fails half
-// way must not leave kernels in flight behind the error code.
-extern "C" int mm_tick(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats* stats)
+// Stage 2: the purge and the three walks, then the chains' records to the host, and the tick's first synchronisation.
+static int tick_launch(mm_engine* e, uint32_t mode, const ModeDev& M)
 {
-    if (!e || mode >= e->cfg.n_modes) return MM_ERR_INVALID_ARG;
-    if (e->poisoned) return MM_ERR_STATE;
-    ON_ENGINE_DEVICE(e);
-    const int rc = guarded([&]() -> int { return tick_impl(e, mode, n_matches, stats); });
-    if (rc != MM_OK) {
-        // whatever was enqueued on the stream finishes before the caller sees the error; the queues
-        // and lobbies are then in an unspecified (mid-tick) state: mm_reset or mm_restore before
-        // the engine is used again (mm_engine.h)
-        (void)hipStreamSynchronize(e->stream);
-        e->r_n = 0;
-        e->poisoned = true;
-    }
-    return rc;
-}
-
-static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats* stats)
-{
-    RoctxRange rr_tick("mm_tick");
-    const double t0 = host_now_ms();
     const mm_config& cfg = e->cfg;
     const uint32_t G = cfg.n_groups;
-    const ModeDev M = make_mode_dev(cfg.modes[mode]);
     const bool timing = (cfg.flags & MM_CFG_TIMING) != 0;
     const bool purge = e->cancel_pending > 0;
-    e->r_n = 0;
-    e->mw_n = 0;
-    e->r_L = M.L;
-    {   // mm_path_stats_get: this tick's record (the totals go on)
-        const uint32_t tot = e->ps.team_flags_late_total;
-        memset(&e->ps, 0, sizeof(e->ps));
-        e->ps.mode = mode;
-        e->ps.team_flags_late_total = tot;
-    }
-    if (e->ev_copy_pending) { (void)hipEventSynchronize(e->ev_copy); e->ev_copy_pending = false; }   // (a tick that failed half way)
-    e->r_based = false;
-    for (uint32_t g = 0; g < G; ++g) { e->r_sent[g] = 0; e->r_marked[g] = 0; e->r_cnt[g] = 0; }
-
-    HIPCHK(e, hipMemsetAsync(e->d_counters, 0, sizeof(uint32_t), e->stream));
     if (timing) HIPCHK(e, hipEventRecord(e->ev[0], e->stream));
     if (purge) {
         hipLaunchKernelGGL(k_purge, dim3(G), dim3(WK_THREADS), 0, e->stream, mode, G, cfg.capacity, e->d_chains,
@@ -2972,106 +3129,76 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
     // (mm_path_stats: the pair chains' records as kp_late and kp_finish left them — the last look was taken before them)
     if (use_pair) HIPCHK(e, hipMemcpyAsync(e->h_pchains, e->d_pchains, G * sizeof(PairChain), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    const double t_copy0 = host_now_ms();
-    if (use_pair && e->tn.debug) MMTRY(report_pair(e));
+    return MM_OK;
+}
 
-    uint32_t total = 0, after = 0, before = 0, pmax = 0, errf = 0;
-    unsigned long long pairs = 0, scanned = 0;
+// Stage 3: one loop over the mode's chains (h_chains).
+static void tick_totals(const mm_engine* e, uint32_t mode, TickTotals& T)
+{
+    const uint32_t G = e->cfg.n_groups;
+    const ChainDev* const ch = e->h_chains + (size_t)mode * G;
+    memset(&T, 0, sizeof(T));
     for (uint32_t g = 0; g < G; ++g) {
-        const ChainDev& c = e->h_chains[mode * G + g];
-        total += c.n_out;
-        after += c.len + c.lobby.n;
-        before += c.before;
-        pairs += c.pairs;
-        scanned += c.scanned;
-        errf |= c.err;
-        if (c.passes > pmax) pmax = c.passes;
+        const ChainDev& c = ch[g];
+        T.n_out[g] = c.n_out; T.had[g] = c.before; T.left[g] = c.len + c.lobby.n;
+        T.total += c.n_out;
+        T.after += T.left[g];
+        T.before += c.before;
+        T.pairs += c.pairs;
+        T.scanned += c.scanned;
+        T.err |= c.err;
+        if (c.passes > T.pmax) T.pmax = c.passes;
     }
-    if (errf) return MM_ERR_INTERNAL;
-    if (e->tn.fail_tick && ++e->ticks_seen == e->tn.fail_tick) return MM_ERR_INTERNAL;   // test hook: a tick that dies after its walk
-    if ((size_t)total * M.L > (size_t)cfg.capacity + (size_t)MM_MAX_LOBBY * G) return MM_ERR_INTERNAL;
-    RoctxRange rr_res("mm_tick/match list");
-    bool tail_on_main = false;
-    // The match list, group-major emission order.  Most of it left for the host while the walk was still running
-    // (results_send at every look at the chains); what the last kernels emitted follows now, and the host does its
-    // part for what has arrived meanwhile — ActiveUser.remove_user for the matched players (game-lobby/worker.ex:73-103).
-    {
-        uint32_t bf[MM_MAX_GROUPS], no[MM_MAX_GROUPS];
-        for (uint32_t g = 0; g < G; ++g) {
-            const ChainDev& c = e->h_chains[mode * G + g];
-            bf[g] = c.n_out * M.L;                                   // tight: the counts are final
-            no[g] = c.n_out;
-            if (e->r_based && (c.n_out < e->r_sent[g] || (unsigned long long)c.n_out * M.L > (unsigned long long)c.before + M.L))
-                return MM_ERR_INTERNAL;
-        }
-        if (!e->r_based && total > 0u && total <= MM_PACK_MAX) {
-            // nothing has left yet and the tick is small: one packed piece, tight layout (group g at its prefix)
-            const PackArgs A = pack_args(e, mode, M.L, total);
-            for (uint32_t g = 0; g < G; ++g) { e->r_base[g] = A.pre[g]; e->r_sent[g] = no[g]; }
-            e->r_based = true;
-            hipLaunchKernelGGL(k_pack_results, dim3((total + 255u) / 256u), dim3(256), 0, e->stream, A, e->d_out_slots, e->d_out_score,
-                               e->d_out_pass, e->d_pack);
-            HIPCHK(e, hipGetLastError());
-            HIPCHK(e, hipMemcpyAsync(e->h_rslots, e->d_pack, (size_t)total * M.L * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-            HIPCHK(e, hipMemcpyAsync(e->h_rscore, e->d_pack + (size_t)total * M.L, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-            HIPCHK(e, hipMemcpyAsync(e->h_rpass, e->d_pack + (size_t)total * (M.L + 1u), (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-            tail_on_main = true;
-        } else {
-            if (!e->r_based) results_set_bases(e, bf, M.L);
-            MMTRY(results_send(e, no, M.L, 1u, &tail_on_main));
-        }
-    }
-    const uint32_t nrel = e->h_counters[0];
-    e->r_released.resize(nrel);
-    if (nrel)
-        HIPCHK(e, hipMemcpyAsync(e->r_released.data(), e->d_released, nrel * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    if (e->clock_on && total > 0u) {
-        // mm_matches_wait: the waits of the matched, while their stamps are still theirs (the emission logs are final:
-        // the stream was synchronised above).  Queued BEHIND the match list's tail, so the list reaches the host as early
-        // as without the clock; the copy goes into pinned memory and is covered by this tick's last synchronisation
-        const PackArgs A = pack_args(e, mode, M.L, total);
-        const uint32_t words = total * M.L;
-        hipLaunchKernelGGL(k_wait_matched, dim3((words + 255u) / 256u), dim3(256), 0, e->stream, A, e->d_out_slots, e->d_stamp,
-                           cfg.capacity, e->clock_now, e->d_wt_matched);
-        HIPCHK(e, hipGetLastError());
-        HIPCHK(e, hipMemcpyAsync(e->h_mwait, e->d_wt_matched, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    }
-    {
-        MMTRY(results_absorb(e, M.L));
-    }
-    e->r_pre[0] = 0;
-    for (uint32_t g = 0; g < G; ++g) {
-        e->tk_last_len[mode * G + g] = e->h_chains[mode * G + g].len + e->h_chains[mode * G + g].lobby.n;
-        e->r_cnt[g] = e->h_chains[mode * G + g].n_out;
-        e->r_pre[g + 1u] = e->r_pre[g] + e->r_cnt[g];
-    }
+}
+
+// Stage 5: the tick's last synchronisation, then the host's books — ActiveUser.remove_user for the matched players
+// (game-lobby/worker.ex:73-103) and the slots the liveness filter released, the bounds of what is still queued, mm_path_stats.
+static int tick_close(mm_engine* e, uint32_t mode, uint32_t L, const TickTotals& T, uint32_t nrel)
+{
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (tail_on_main)
-        for (uint32_t g = 0; g < G; ++g) results_mark(e, g, e->r_sent[g], M.L);
-    // ... and the slots the liveness filter released
-    for (uint32_t i = 0; i < nrel; ++i) e->h_state[e->r_released[i]] = MM_ST_FREE;
+    matches_close(e, T);
     e->cancel_pending = e->cancel_pending >= nrel ? e->cancel_pending - nrel : 0;
-    {
-        const unsigned long long gone = (unsigned long long)total * M.L + nrel;
-        e->live_upper = e->live_upper >= gone ? e->live_upper - gone : 0;
-    }
-    e->r_n = total;
-    e->mw_n = e->clock_on ? total : 0u;
-    if (n_matches) *n_matches = total;
+    const unsigned long long gone = (unsigned long long)T.total * L + nrel;
+    e->live_upper = e->live_upper >= gone ? e->live_upper - gone : 0;
+    uint32_t* const last = e->tk_last_len.data() + (size_t)mode * e->cfg.n_groups;
+    for (uint32_t g = 0, G = e->cfg.n_groups; g < G; ++g) last[g] = T.left[g];
     if (e->ps.paths & MM_PATH_PAIR) path_stats_pair(e, mode);
     e->ps.crit_team_group = 0xFFFFFFFFu;
     if (e->ps.paths & MM_PATH_TEAM) path_stats_team(e);
+    return MM_OK;
+}
+
+static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats* stats)
+{
+    RoctxRange rr_tick("mm_tick");
+    const double t0 = host_now_ms();
+    const ModeDev M = make_mode_dev(e->cfg.modes[mode]);
+    MMTRY(tick_open(e, mode, M.L));
+    MMTRY(tick_launch(e, mode, M));
+    const double t_copy0 = host_now_ms();
+    if ((e->ps.paths & MM_PATH_PAIR) && e->tn.debug) MMTRY(report_pair(e));
+    TickTotals T;
+    tick_totals(e, mode, T);
+    if (T.err) return MM_ERR_INTERNAL;
+    if (e->tn.fail_tick && ++e->ticks_seen == e->tn.fail_tick) return MM_ERR_INTERNAL;   // test hook: a tick that dies after its walk
+    RoctxRange rr_res("mm_tick/match list");
+    // Stage 4: the end of the match list (group-major emission order), and behind it the released slots and the waits of the matched
+    uint32_t nrel = 0;
+    MMTRY(matches_finish(e, T));
+    MMTRY(matches_extras(e, T, &nrel));
+    MMTRY(tick_close(e, mode, M.L, T, nrel));
+    if (n_matches) *n_matches = T.total;
     if (stats) {
         memset(stats, 0, sizeof(*stats));
-        stats->pool_before = before;
-        stats->pool_after = after;
-        stats->matches = total;
-        stats->players_matched = total * M.L;
-        stats->passes_max = pmax;
-        stats->chains = G;
-        stats->pairs = pairs;
-        stats->scanned = scanned;
-        if (timing) {
+        stats->pool_before = T.before;
+        stats->pool_after = T.after;
+        stats->matches = T.total;
+        stats->players_matched = T.total * M.L;
+        stats->passes_max = T.pmax;
+        stats->chains = e->cfg.n_groups;
+        stats->pairs = T.pairs;
+        stats->scanned = T.scanned;
+        if (e->cfg.flags & MM_CFG_TIMING) {
             (void)hipEventElapsedTime(&stats->filter_ms, e->ev[0], e->ev[1]);
             (void)hipEventElapsedTime(&stats->walk_ms, e->ev[1], e->ev[2]);
         }
@@ -3082,29 +3209,29 @@ static int tick_impl(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats*
     return MM_OK;
 }
 
+// The exported tick: nothing may unwind into the caller (a NIF frame), and a tick that fails half
+// way must not leave kernels in flight behind the error code.
+extern "C" int mm_tick(mm_engine* e, uint32_t mode, uint32_t* n_matches, mm_stats* stats)
+{
+    if (!e || mode >= e->cfg.n_modes) return MM_ERR_INVALID_ARG;
+    if (e->poisoned) return MM_ERR_STATE;
+    ON_ENGINE_DEVICE(e);
+    const int rc = guarded([&]() -> int { return tick_impl(e, mode, n_matches, stats); });
+    if (rc != MM_OK) {
+        // whatever was enqueued on the stream finishes before the caller sees the error; the queues
+        // and lobbies are then in an unspecified (mid-tick) state: mm_reset or mm_restore before
+        // the engine is used again (mm_engine.h)
+        (void)hipStreamSynchronize(e->stream);
+        e->ml.drop();
+        e->poisoned = true;
+    }
+    return rc;
+}
+
 extern "C" int mm_matches(mm_engine* e, uint32_t first, uint32_t count, uint32_t* slots, float* score,
                           uint32_t* group, uint32_t* pass)
 {
-    return guarded([&]() -> int {
-        if (!e) return MM_ERR_INVALID_ARG;
-        if (first > e->r_n || count > e->r_n - first) return MM_ERR_RANGE;
-        if (count == 0) return MM_OK;
-        // emission index i of the tick = lobby i - r_pre[g] of group g, stored at r_base[g] + that (tick_impl)
-        const uint32_t L = e->r_L;
-        // (Round 5, measured and taken out: the 10 MB of a big tick's list copied by four threads in 256 KB pieces —
-        // 10.01-10.28 ms a step with one thread, 10.03-10.26 with four, profiles/r05_ab_pair_micro.txt.)
-        for (uint32_t g = 0; g < e->cfg.n_groups; ++g) {
-            const uint32_t lo = e->r_pre[g] > first ? e->r_pre[g] : first;
-            const uint32_t hi = e->r_pre[g + 1u] < first + count ? e->r_pre[g + 1u] : first + count;
-            if (hi <= lo) continue;
-            const size_t src = (size_t)e->r_base[g] + (lo - e->r_pre[g]), dst = lo - first, n = hi - lo;
-            if (slots) memcpy(slots + dst * L, &e->h_rslots[src * L], n * L * sizeof(uint32_t));
-            if (score) memcpy(score + dst, &e->h_rscore[src], n * sizeof(float));
-            if (pass) memcpy(pass + dst, &e->h_rpass[src], n * sizeof(uint32_t));
-            if (group) std::fill_n(group + dst, n, g);
-        }
-        return MM_OK;
-    });
+    return guarded([&]() -> int { return e ? matches_read(e, first, count, slots, score, group, pass) : MM_ERR_INVALID_ARG; });
 }
 
 static int fetch_chains(mm_engine* e)
@@ -3357,12 +3484,12 @@ static int wait_alloc(mm_engine* e)
         MMTRY(dev_alloc(e, e->d_wt_out, 3u * cap * sizeof(uint32_t)));
         MMTRY(dev_alloc(e, e->d_wt_stats, MM_MAX_GROUPS * sizeof(WaitGroupDev)));
         MMTRY(dev_alloc(e, e->d_wt_matched, (cap + (size_t)MM_MAX_LOBBY * MM_MAX_GROUPS + 64u) * sizeof(uint32_t)));
-        MMTRY(pin_alloc(e, e->h_mwait, (cap + (size_t)MM_MAX_LOBBY * MM_MAX_GROUPS + 64u) * sizeof(uint32_t)));
+        MMTRY(pin_alloc(e, e->ml.h_mwait, (cap + (size_t)MM_MAX_LOBBY * MM_MAX_GROUPS + 64u) * sizeof(uint32_t)));
         return dev_alloc(e, e->d_stamp, cap * sizeof(uint32_t));   // last: its presence says all of them are there
     });
     if (rc) {                                      // (out of memory half way: the next attempt starts from nothing)
         mem_release(e, e->d_wt_rows); mem_release(e, e->d_wt_out); mem_release(e, e->d_wt_stats);
-        mem_release(e, e->d_wt_matched); mem_release(e, e->h_mwait); mem_release(e, e->d_stamp);
+        mem_release(e, e->d_wt_matched); mem_release(e, e->ml.h_mwait); mem_release(e, e->d_stamp);
     }
     return rc;
 }
@@ -3983,10 +4110,7 @@ extern "C" int mm_matches_wait(mm_engine* e, uint32_t first, uint32_t count, uin
 {
     if (!e) return MM_ERR_INVALID_ARG;
     if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
-    if (first > e->mw_n || count > e->mw_n - first) return MM_ERR_RANGE;
-    if (count == 0 || !wait) return MM_OK;
-    memcpy(wait, &e->h_mwait[(size_t)first * e->r_L], (size_t)count * e->r_L * sizeof(uint32_t));
-    return MM_OK;
+    return matches_read_wait(e, first, count, wait);
 }
 
 extern "C" int mm_last_hip_error(const mm_engine* e) { return e ? e->last_hip : 0; }

@@ -156,6 +156,64 @@ def run_full_tile_one_pass(engine_cls, oracle_cls, tag):
         assert me.stats["passes_max"] <= 2, (tag, me.stats["passes_max"])
 
 
+def read_matches(e, first, count, mode=0):
+    """mm_matches for the window [first, first + count) of the engine's last tick: (slots, score, group, pass)."""
+    import ctypes as C
+    L = e.lobby_size(mode)
+    slots, score = np.empty((count, L), np.uint32), np.empty(count, np.float32)
+    group, pass_ = np.empty(count, np.uint32), np.empty(count, np.uint32)
+    e._check(e._fn("matches")(e._h, first, count, *(a.ctypes.data_as(C.c_void_p) for a in (slots, score, group, pass_))), "matches")
+    return slots, score, group, pass_
+
+
+def run_match_list_routes(engine_cls, oracle_cls, tag):
+    """The routes a tick's match list takes to the host, end to end.
+    One: run_full_tile_one_pass's pool — 20 000 all-fitting players of one rating group, 10 000 lobbies, more than either
+    8192 threshold, behind a look at the chains — under the four combinations of results_early and results_tail (the
+    tail kernel, or copy commands on the copy stream): every list is the oracle's, and the four are each other's to the
+    bit, slots, score, pass and group.
+    Two: a seven-group pool of 600 players that takes no look (no chain is long enough for the tiled rounds), so its list
+    leaves packed: read whole, and again in windows of 1, 3 and 64 entries whose concatenation is the whole."""
+    n = 20000
+    cfg = make_config([mode_1v1(window=1500, region_filter=True)], capacity=1 << 15)
+    rating = np.random.default_rng(41).integers(0, 1400, size=n).astype(np.int32)
+    cons = cons_make(np.zeros(n, np.int64), 0, 0, 0)
+    with oracle_cls(cfg) as o:
+        o.enqueue(rating, cons)
+        mo = o.tick(0)
+    assert len(mo) == n // 2, (tag, len(mo))
+    first = None
+    for early in (1, 0):
+        for tail in (1, 0):
+            t = "%s early %d tail %d" % (tag, early, tail)
+            with engine_cls(cfg, {"pair_tile_fixed": 1, "results_early": early, "results_tail": tail}) as e:
+                e.enqueue(rating, cons)
+                me = e.tick(0)
+                assert e.path_stats()["host_looks"] >= 1, t
+            assert_same_tick(me, mo, t)
+            if first is None:
+                first = me
+            for a, b, what in ((me.slots, first.slots, "slots"), (me.score.view(np.uint32), first.score.view(np.uint32), "score"),
+                               (me.pass_, first.pass_, "pass"), (me.group, first.group, "group")):
+                assert np.array_equal(a, b), (t, what)
+    cfg = make_config([mode_1v1(window=40, region_filter=True)], capacity=4096)
+    rng = np.random.default_rng(43)
+    rating = rng.integers(0, 5001, size=600).astype(np.int32)
+    cons = cons_make(0, rng.integers(0, 2, size=600), 0, 0)
+    with engine_cls(cfg) as e, oracle_cls(cfg) as o:
+        assert np.array_equal(e.enqueue(rating, cons), o.enqueue(rating, cons))
+        me, mo = e.tick(0), o.tick(0)
+        assert_same_tick(me, mo, tag + " packed")
+        assert e.path_stats()["host_looks"] == 0 and len(np.unique(me.group)) == 7 and 64 < len(me) <= 300, (tag, len(me))
+        whole = read_matches(e, 0, len(me))
+        for a, b in zip(whole, (me.slots, me.score, me.group, me.pass_)):
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (tag, "packed, whole")
+        for w in (1, 3, 64):
+            parts = [read_matches(e, at, min(w, len(me) - at)) for at in range(0, len(me), w)]
+            for k in range(4):
+                assert np.array_equal(np.concatenate([p[k] for p in parts]).view(np.uint32), whole[k].view(np.uint32)), (tag, "windows of", w, k)
+
+
 def random_scenario(rng, cfg, ea, eb, n_rounds=4, batch=200, cancel_frac=0.05, n_regions=3,
                     rating_lo=0, rating_hi=5000, n_parties=2):
     """Drive two engines with the same random enqueue/cancel/tick script and compare."""

@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 from helpers import (ANCHOR_MOVES_PRODUCT, ANCHOR_MOVES_PRODUCT_IDS, assert_path_counts, assert_same_state, assert_same_tick, load_golden,
-                     random_scenario, run_anchor_moves_to_the_emptied_first_team, run_full_tile_one_pass, run_golden_case)
+                     random_scenario, run_anchor_moves_to_the_emptied_first_team, run_full_tile_one_pass, run_golden_case,
+                     run_match_list_routes)
 from microservice_matchmaking_amd import cons_make, make_config, mode_1v1, mode_team
 from microservice_matchmaking_amd.synth import ROLE_WEIGHTS_5V5, make_pool
 
@@ -633,6 +634,12 @@ def test_gpu_pair_more_than_1024_lobbies_in_a_tile_and_pass(gpu_cls, oracle_cls,
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     run_full_tile_one_pass(gpu_cls, oracle_cls, "full tile, one pass %s" % env)
+
+
+@pytest.mark.gpu
+def test_gpu_match_list_routes(gpu_cls, oracle_cls):
+    """The match list by the tail kernel, by copy commands on the copy stream and packed: helpers.run_match_list_routes."""
+    run_match_list_routes(gpu_cls, oracle_cls, "match list routes")
 
 
 @pytest.mark.gpu
