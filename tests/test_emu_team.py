@@ -130,7 +130,7 @@ def test_one_pass_body_in_every_kernel_small_geometry(oracle_cls, tuning, want):
     that the head of the queue fills and that is emitted on the spot: tick 2's fill in kt_f's head-fill column (default), in
     kt_fc, in kt_chase's own launch; tick 3's in kt_late (default) or in the pass kernels.  The path counters say which
     kernel it was.  The anchor moves in tick 2 only, which a head that sat out keeps from kt_late: the restart of kt_late's
-    head_fill is not run here."""
+    head_fill is run by tests/test_stale_lobby.py (a cancelled head, or one the stale lobby takes, leaves the tick to kt_late)."""
     stats, _ = run_anchor_moves_to_the_emptied_first_team(tuning, EmuEngineSmall, oracle_cls)
     assert_path_counts(stats, want)
 
