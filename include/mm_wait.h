@@ -2,7 +2,8 @@
  * mm_wait.h — the engine's clock: arrival stamps, expiry of long-waiting players, their move to a
  * fallback mode — inside one engine or carried to another one with their rows and stamps — the
  * rotation of a blocked lobby's players to their queue's tail, wait times, a player's place in
- * its queue, how many waiting players fit a player and how far away the nearest one is.
+ * its queue, how many waiting players fit a player and how far away the nearest one is, and expiry and moves that
+ * select by that number.
  *
  * An extension of include/mm_engine.h (same rules: plain C types, status codes and never an
  * abort, every entry point selects the engine's HIP device itself, MM_ERR_STATE on an engine
@@ -62,6 +63,12 @@
  * player would first have a partner.  It applies the existing predicate to a question, matches nobody
  * and changes nothing; the witness is numpy over the oracle's lists.
  *
+ * Acting on that answer is mm_expire_if, mm_move_if and mm_move_out_if: the plain call's selection by age, kept only
+ * where the player's partner count lies in a range the owner names (mm_partner_rule).  Age alone is the wrong rule for
+ * a first-fit chain: an old player with forty partners inside its window leaves a queue that would have seated it in
+ * the next tick, and a player with nobody in range sits out the full max_age for nothing.  No new matching rule: the
+ * selection is mm_expire's list filtered by mm_partners' number, and everything after it is the plain call's.
+ *
  * Not here: the NIF binding (native/mm_nif.c; INTEGRATION.md section 7 names the calls to add);
  * an ALL-OR-NOTHING move across engines (chain (A, g) and chain (B, g) of a ShardedSearch may have
  * different owners: mm_move_out has expired the players on their source before the destination's
@@ -70,9 +77,8 @@
  * gathered stamps to the stamped scatter inside the engine); matching a waiting player against a wider window
  * INSIDE its own queue (a new matching rule, with no witness in the reference or the oracle — mm_partners
  * is the measurement such a decision would rest on: how many partners at window W, and nothing more);
- * ACTING on mm_partners' answer inside the engine (an mm_move that selects by partner count); mm_partners
- * across two engines (chain (mode, g) and chain (in_mode, g) of a ShardedSearch may have different owners:
- * sharding.py raises for in_mode != mode).
+ * mm_partners and the rule calls across two engines (chain (mode, g) and chain (in_mode, g) of a ShardedSearch
+ * may have different owners: sharding.py raises for in_mode != mode).
  */
 #ifndef MM_WAIT_H
 #define MM_WAIT_H
@@ -299,6 +305,48 @@ int mm_locate(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, ui
  * Reference: none.  Search.Worker.status/0 (lib/search/worker.ex:115-117, :326-334) sees the depth only. */
 int mm_partners(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags, uint32_t n,
                 const uint32_t* slots, uint32_t* partners, uint32_t* by_role, uint32_t* gap);
+
+/* Which of the players old enough a rule call selects: those whose partner count lies in a range. */
+typedef struct mm_partner_rule {
+    uint32_t in_mode;       /* whose chains are searched: chain (in_mode, g), g the player's rating group        */
+    uint32_t window, flags; /* mm_partners' predicate: |rating difference| <= window, MM_MODE_* filters          */
+    uint32_t min_partners;  /* selected iff min_partners <= partners <= max_partners                             */
+    uint32_t max_partners;
+} mm_partner_rule;
+
+/* mm_expire, mm_move and mm_move_out with a second condition.  Player p is selected iff
+ *   mm_expire(mode, max_age) — from_mode for the moves — would select p, AND
+ *   the `partners` word mm_partners(mode, rule->in_mode, rule->window, rule->flags, 1, &p.slot, ..) would return lies
+ *   in [rule->min_partners, rule->max_partners],
+ * both on the pool as it stands when the call enters: a candidate this same call goes on to select still counts (two old
+ * players in range of each other are each other's partners, and with max_partners == 0 both stay), so the selection
+ * does not depend on any order.  mm_partners' rules hold unchanged: p is never its own partner, MARKED candidates do
+ * not count, p's rating and constraint word are the ones the engine holds — the un-rewritten word, whatever cons_clear
+ * says — and the seats of stored lobbies are queries and candidates alike.
+ * The list is mm_expire's order restricted to the selected players, and everything from there on is the plain call's,
+ * word for word: the marks, the host mirrors, mm_expired / mm_moved / mm_moved_rows and their lifetimes, the new slots
+ * "as mm_enqueue takes them for a batch of *n_selected", the stamps carried over, the refused rows, and MM_ERR_FULL all
+ * or nothing — judged on the number finally selected, not on the number old enough.
+ * With [0, 0xFFFFFFFF] each call is its plain call.  The two intended uses:
+ *   in_mode == from_mode, [0, 0], the mode's own window and flags            "nobody here fits me";
+ *   in_mode == to_mode, [1, 0xFFFFFFFF], the destination's window and flags  "move only where someone fits".
+ * MM_ERR_INVALID_ARG: the plain call's cases, rule == NULL, rule->in_mode >= n_modes, a flags bit outside the two
+ * MM_MODE_* filters, min_partners > max_partners.  MM_ERR_STATE: as the plain call.  A failure before the first mark
+ * leaves the engine usable and, MM_ERR_FULL apart, releases the call's scratch as mm_partners does; from the first mark
+ * on it leaves the engine MM_ERR_STATE until mm_reset / mm_restore, as for the plain call.  An engine that never calls
+ * them allocates and launches nothing for them; results never depend on mm_tuning; nothing new goes into a snapshot.
+ * Cost: the plain call's age count, then — only when somebody is old enough — one more stream of from_mode's queues that
+ * writes a record per candidate and marks nothing, one stream of in_mode's queues per tile of 512 candidates
+ * (candidates x group length predicate tests, as mm_partners), a count, a scan and a scatter over the candidates.
+ * Scratch is mm_partners', sized by the candidates.  Waits on the stream: mm_move_if three at the most (the candidates,
+ * the selected — before anything is marked, for MM_ERR_FULL — and the lists); mm_expire_if and mm_move_out_if two
+ * (nobody can be refused, so the selected count comes back with the lists); one when nobody is old enough.
+ * Reference: none (as mm_expire, mm_move, mm_move_out); to the oracle the effect is mo_cancel plus mo_enqueue. */
+int mm_expire_if(mm_engine* e, uint32_t mode, uint32_t max_age, const mm_partner_rule* rule, uint32_t* n_expired);
+int mm_move_if(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
+               const mm_partner_rule* rule, uint32_t* n_selected, uint32_t* n_refused);
+int mm_move_out_if(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
+                   const mm_partner_rule* rule, uint32_t* n_selected);
 
 /* How long the players of the last tick's lobbies had waited: L = teams * team_size words per
  * match, laid out like mm_matches' `slots`; each word is the clock at that tick minus the seated

@@ -105,6 +105,11 @@ class MMWaitGroup(C.Structure):
                 "hist": np.asarray(self.hist[:], dtype=np.uint32)}
 
 
+class MMPartnerRule(C.Structure):
+    _fields_ = [("in_mode", C.c_uint32), ("window", C.c_uint32), ("flags", C.c_uint32),
+                ("min_partners", C.c_uint32), ("max_partners", C.c_uint32)]
+
+
 class MMError(RuntimeError):
     def __init__(self, status, where):
         self.status = int(status)
@@ -258,7 +263,27 @@ def bind(lib, prefix):
     if hasattr(lib, prefix + "partners"):                 # include/mm_wait.h: how many waiting players fit a player
         f("partners").argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p] * 4
         f("partners").restype = C.c_int
+    if hasattr(lib, prefix + "move_if"):                  # include/mm_wait.h: expiry and moves that select by partner count
+        rulep = C.POINTER(MMPartnerRule)
+        f("expire_if").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, rulep, u32p]
+        f("expire_if").restype = C.c_int
+        f("move_if").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, rulep, u32p, u32p]
+        f("move_if").restype = C.c_int
+        f("move_out_if").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, rulep, u32p]
+        f("move_out_if").restype = C.c_int
     return lib
+
+
+@dataclass
+class PartnerRule:
+    """mm_partner_rule (include/mm_wait.h): selected iff min_partners <= partners <= max_partners, `partners` counted in
+    chain (in_mode, the player's rating group) at `window` and `flags`.  in_mode=None: the source mode; window=None /
+    flags=None: in_mode's own.  The defaults select everybody old enough: the plain call."""
+    in_mode: int = None
+    window: int = None
+    flags: int = None
+    min_partners: int = 0
+    max_partners: int = 0xFFFFFFFF
 
 
 @dataclass
@@ -522,6 +547,54 @@ class EngineBase:
         n = C.c_uint32()
         self._check(self._fn("move_out")(self._h, from_mode, to_mode, int(max_age) & 0xFFFFFFFF,
                                          int(cons_clear) & 0xFFFFFFFF, C.byref(n)), "move_out")
+        k = int(n.value)
+        slots, group, age, cons, stamp = (np.empty(k, dtype=np.uint32) for _ in range(5))
+        rating = np.empty(k, dtype=np.int32)
+        self._check(self._fn("expired")(self._h, 0, k, _ptr(slots), _ptr(group), _ptr(age)), "expired")
+        self._check(self._fn("moved_rows")(self._h, 0, k, _ptr(rating), _ptr(cons), _ptr(stamp)), "moved_rows")
+        return slots, group, age, rating, cons, stamp
+
+    def _rule(self, rule, mode):
+        """A PartnerRule or a dict of its fields -> mm_partner_rule, the defaults filled in from `mode` and the configuration."""
+        r = rule if isinstance(rule, PartnerRule) else PartnerRule(**dict(rule))
+        in_mode = mode if r.in_mode is None else int(r.in_mode)
+        window, flags = r.window, r.flags
+        if 0 <= in_mode < self.cfg.n_modes:
+            window = self.cfg.modes[in_mode].window if window is None else window
+            flags = self.cfg.modes[in_mode].flags if flags is None else flags
+        return MMPartnerRule(in_mode & 0xFFFFFFFF, int(window or 0) & 0xFFFFFFFF, int(flags or 0) & 0xFFFFFFFF,
+                             int(r.min_partners) & 0xFFFFFFFF, int(r.max_partners) & 0xFFFFFFFF)
+
+    def expire_if(self, mode, max_age, rule):
+        """mm_expire_if + mm_expired: `expire` over the players old enough whose partner count lies in the rule's range
+        (PartnerRule or a dict of its fields).  -> (slots, group, age) in mm_expire's order."""
+        n = C.c_uint32()
+        self._check(self._fn("expire_if")(self._h, mode, int(max_age) & 0xFFFFFFFF, C.byref(self._rule(rule, mode)),
+                                          C.byref(n)), "expire_if")
+        k = int(n.value)
+        slots, group, age = (np.empty(k, dtype=np.uint32) for _ in range(3))
+        self._check(self._fn("expired")(self._h, 0, k, _ptr(slots), _ptr(group), _ptr(age)), "expired")
+        return slots, group, age
+
+    def move_if(self, from_mode, to_mode, max_age, cons_clear=0, rule=None):
+        """mm_move_if + mm_expired + mm_moved: `move` over the players old enough whose partner count lies in the rule's
+        range.  -> (slots, group, age, new_slots); self.last_move as `move` sets it."""
+        n, r = C.c_uint32(), C.c_uint32()
+        self._check(self._fn("move_if")(self._h, from_mode, to_mode, int(max_age) & 0xFFFFFFFF, int(cons_clear) & 0xFFFFFFFF,
+                                        C.byref(self._rule(rule or {}, from_mode)), C.byref(n), C.byref(r)), "move_if")
+        k = int(n.value)
+        self.last_move = {"selected": k, "refused": int(r.value)}
+        slots, group, age, new = (np.empty(k, dtype=np.uint32) for _ in range(4))
+        self._check(self._fn("expired")(self._h, 0, k, _ptr(slots), _ptr(group), _ptr(age)), "expired")
+        self._check(self._fn("moved")(self._h, 0, k, _ptr(new)), "moved")
+        return slots, group, age, new
+
+    def move_out_if(self, from_mode, to_mode, max_age, cons_clear=0, rule=None):
+        """mm_move_out_if + mm_expired + mm_moved_rows: `move_out` over the players old enough whose partner count lies in
+        the rule's range.  -> (slots, group, age, rating, cons, stamp)."""
+        n = C.c_uint32()
+        self._check(self._fn("move_out_if")(self._h, from_mode, to_mode, int(max_age) & 0xFFFFFFFF, int(cons_clear) & 0xFFFFFFFF,
+                                            C.byref(self._rule(rule or {}, from_mode)), C.byref(n)), "move_out_if")
         k = int(n.value)
         slots, group, age, cons, stamp = (np.empty(k, dtype=np.uint32) for _ in range(5))
         rating = np.empty(k, dtype=np.int32)

@@ -417,6 +417,7 @@ __global__ __launch_bounds__(256) void k_reset(uint32_t n_chains, ChainDev* __re
 #define WT_ROWS (WT_WAVES + 1)                // counters per chunk: the stored lobby's seats, then one per wave
 #define WT_SEATS (MM_MAX_TEAMS * 8)           // seats a LobbyDev has room for
 #define PAR_QTILE 512                         // query records a workgroup of k_par_count* stages in LDS at a time (mm_partners)
+#define SEL_TILE 256                          // candidates per workgroup of k_sel_count / k_sel_scatter*, one per thread (mm_*_if)
 #include "mm_wait.inc"
 
 // ------------------------------------------------------------------------------------
@@ -4045,6 +4046,181 @@ extern "C" int mm_moved_rows(mm_engine* e, uint32_t first, uint32_t count, int32
     if (cons) memcpy(cons, &e->x.cons[first], (size_t)count * sizeof(uint32_t));
     if (stamp) memcpy(stamp, &e->x.stamp[first], (size_t)count * sizeof(uint32_t));
     return MM_OK;
+}
+
+// ---- the selection by partner count (mm_expire_if, mm_move_if, mm_move_out_if) ----
+
+static bool rule_ok(const mm_engine* e, const mm_partner_rule* r)
+{
+    return r && r->in_mode < e->cfg.n_modes && !(r->flags & ~(MM_MODE_REGION_FILTER | MM_MODE_PARTY_FILTER)) &&
+           r->min_partners <= r->max_partners;
+}
+
+// The candidates of a rule call and their compaction, queued behind the age count that found k1 of them; nothing is
+// marked.  k_cand_scatter writes a query record, the age and a zeroed count per candidate at its rank; k_par_count streams
+// in_mode's chains against those records, exactly as mm_partners does behind its gather; k_sel_count and k_sel_scan rank
+// the candidates whose count lies in the rule's range.  The scratch is par_alloc's, sized by k1: the records in d_par_rec,
+// the counts in the `partners` column of d_par_out, the ages in its `gap` column and the ranks (k1 / 64 words and the
+// total) in its by_role columns, none of which this pass of the count fills.  *S: what the marking scatter needs.
+static int rule_rank(mm_engine* e, const WaitParams& P, uint32_t grid, uint32_t k1, const mm_partner_rule& rule, SelParams* S)
+{
+    MMTRY(par_alloc(e, k1));
+    const size_t stride = e->par_cap;
+    MoveCols src = move_cols(e, 0u, 0u, true);
+    src.rating = nullptr; src.cons = nullptr; src.stamp = nullptr; src.group = nullptr;   // (read the queues' columns, write none)
+    CandCols C;
+    C.rec = e->d_par_rec;
+    C.cnt = e->d_par_out;
+    C.age = e->d_par_out + stride;
+    C.n = k1;
+    WaitParams W = P;                                          // the count: the same walk over in_mode's chains
+    W.mode = rule.in_mode;
+    W.teams = e->cfg.modes[rule.in_mode].teams;
+    ParParams Q;
+    memset(&Q, 0, sizeof(Q));
+    Q.n = k1;
+    Q.stride = e->par_cap;
+    Q.window = rule.window;
+    Q.eqmask = ((rule.flags & MM_MODE_REGION_FILTER) ? (0xFFu << 4) : 0u) | ((rule.flags & MM_MODE_PARTY_FILTER) ? (0xFu << 12) : 0u);
+    Q.q_rating = e->d_q_rating;
+    Q.q_cons = e->d_q_cons;
+    Q.rec = e->d_par_rec;
+    Q.out = e->d_par_out;
+    const uint32_t n_tiles = (k1 + PAR_QTILE - 1u) / PAR_QTILE, room = 2048u / grid ? 2048u / grid : 1u;   // as partners_impl
+    Q.gx = grid;
+    const uint32_t gy = n_tiles < room ? n_tiles : room;
+    memset(S, 0, sizeof(*S));
+    S->n = k1;
+    S->capacity = e->cfg.capacity;
+    S->lo = rule.min_partners;
+    S->hi = rule.max_partners;
+    S->now = e->clock_now;
+    S->rec = C.rec;
+    S->age = C.age;
+    S->cnt = C.cnt;
+    S->rows = e->d_par_out + 2u * stride;                      // ((k1 + 63) / 64 + 1 <= MM_MAX_ROLES * stride words)
+    S->state = e->d_state;
+    S->out_slot = P.out_slot;
+    S->out_group = P.out_group;
+    S->out_age = P.out_age;
+    const dim3 wg(WT_THREADS), per_cand((k1 + SEL_TILE - 1u) / SEL_TILE), tile(SEL_TILE);
+    hipLaunchKernelGGL(k_cand_scatter, dim3(grid), wg, 0, e->stream, P, src, C);
+    hipLaunchKernelGGL(k_par_count, dim3(grid * gy), wg, 0, e->stream, W, Q);
+    hipLaunchKernelGGL(k_sel_count, per_cand, tile, 0, e->stream, *S);
+    hipLaunchKernelGGL(k_sel_scan, dim3(1), wg, 0, e->stream, *S);
+    HIPCHK(e, hipGetLastError());
+    return MM_OK;
+}
+
+static const uint32_t* rule_total(const SelParams& S) { return S.rows + (S.n + 63u) / 64u; }
+
+// The marking scatter of a rule call: the kept candidates into the list (and M's rows), state[] marked.
+static void rule_mark(mm_engine* e, const SelParams& S, const MoveCols* M)
+{
+    const dim3 per_cand((S.n + SEL_TILE - 1u) / SEL_TILE), tile(SEL_TILE);
+    if (M) hipLaunchKernelGGL(k_sel_scatter_rows, per_cand, tile, 0, e->stream, S, *M);
+    else hipLaunchKernelGGL(k_sel_scatter, per_cand, tile, 0, e->stream, S);
+}
+
+// marking_call for a rule call: a failure before the first mark other than MM_ERR_FULL releases the call's scratch, as
+// mm_partners does, and leaves the engine usable.
+template <class Body>
+static int rule_call(mm_engine* e, const char* name, std::initializer_list<uint32_t*> counters, Body&& body)
+{
+    return marking_call(e, name, counters, [&](bool* marked_on_device) -> int {
+        const int rc = guarded([&]() -> int { return body(marked_on_device); });
+        if (rc != MM_OK && rc != MM_ERR_FULL && !*marked_on_device) {
+            (void)hipStreamSynchronize(e->stream);
+            par_release(e);
+        }
+        return rc;
+    });
+}
+
+// mm_expire_if and mm_move_out_if behind their age count: nobody can be refused, so the marking scatter is queued behind
+// the ranks without waiting for k2, and k2 comes back WITH the list — the first k1 rows of every column are fetched (k2 of
+// them are the list; the host cuts the rest off).  Two waits in all.
+static int rule_mark_and_fetch(mm_engine* e, const WaitParams& P, uint32_t grid, uint32_t k1, const mm_partner_rule& rule,
+                               const MoveCols* M, bool* marked_on_device, uint32_t* k2)
+{
+    SelParams S;
+    MMTRY(rule_rank(e, P, grid, k1, rule, &S));
+    *marked_on_device = true;
+    rule_mark(e, S, M);
+    HIPCHK(e, hipGetLastError());
+    MMTRY(fetch_list(e, k1, nullptr, M));
+    MMTRY(read_selected(e, rule_total(S), k2));
+    if (*k2 > k1) return MM_ERR_INTERNAL;
+    WaitLists& x = e->x;
+    x.slot.resize(*k2); x.group.resize(*k2); x.age.resize(*k2);
+    if (M) { x.rating.resize(*k2); x.cons.resize(*k2); x.stamp.resize(*k2); }
+    return mirror_marks(e, *k2);
+}
+
+extern "C" int mm_expire_if(mm_engine* e, uint32_t mode, uint32_t max_age, const mm_partner_rule* rule, uint32_t* n_expired)
+{
+    if (!e || mode >= e->cfg.n_modes || !rule_ok(e, rule)) return MM_ERR_INVALID_ARG;
+    if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
+    return rule_call(e, "mm_expire_if", { n_expired }, [&](bool* marked_on_device) -> int {
+        const WaitParams P = wait_params(e, mode, max_age);
+        const uint32_t grid = wait_grid(e);
+        uint32_t k1 = 0, k2 = 0;
+        MMTRY(wait_select(e, P, grid, &k1));
+        if (k1 == 0u) return MM_OK;
+        MMTRY(rule_mark_and_fetch(e, P, grid, k1, *rule, nullptr, marked_on_device, &k2));
+        if (n_expired) *n_expired = k2;
+        return MM_OK;
+    });
+}
+
+// mm_move_if: three waits at the most — k1, then k2 BEFORE anything is marked (MM_ERR_FULL is judged on k2), then
+// requeue_selected with the compaction's marking scatter in k_move_scatter's place.
+extern "C" int mm_move_if(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
+                          const mm_partner_rule* rule, uint32_t* n_selected, uint32_t* n_refused)
+{
+    if (!e || from_mode >= e->cfg.n_modes || to_mode >= e->cfg.n_modes || from_mode == to_mode ||
+        (cons_clear & (~MM_CONS_USER_MASK | 0xFu)) || !rule_ok(e, rule))
+        return MM_ERR_INVALID_ARG;
+    if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
+    return rule_call(e, "mm_move_if", { n_selected, n_refused }, [&](bool* marked_on_device) -> int {
+        MMTRY(move_alloc(e));
+        const WaitParams P = wait_params(e, from_mode, max_age);
+        const uint32_t grid = wait_grid(e);
+        uint32_t k1 = 0, k2 = 0, refused = 0;
+        MMTRY(wait_select(e, P, grid, &k1));
+        if (k1 == 0u) return MM_OK;
+        SelParams S;
+        MMTRY(rule_rank(e, P, grid, k1, *rule, &S));
+        MMTRY(read_selected(e, rule_total(S), &k2));
+        if (k2 > k1) return MM_ERR_INTERNAL;
+        if (k2 == 0u) return MM_OK;
+        const MoveCols M = move_cols(e, cons_clear, to_mode, true);
+        MMTRY(requeue_selected(e, k2, M, marked_on_device, [&]() { rule_mark(e, S, &M); }, &refused));
+        if (n_selected) *n_selected = k2;
+        if (n_refused) *n_refused = refused;
+        return MM_OK;
+    });
+}
+
+extern "C" int mm_move_out_if(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
+                              const mm_partner_rule* rule, uint32_t* n_selected)
+{
+    if (!e || from_mode >= e->cfg.n_modes || to_mode >= MM_MAX_MODES || from_mode == to_mode ||
+        (cons_clear & (~MM_CONS_USER_MASK | 0xFu)) || !rule_ok(e, rule))
+        return MM_ERR_INVALID_ARG;
+    if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
+    return rule_call(e, "mm_move_out_if", { n_selected }, [&](bool* marked_on_device) -> int {
+        MMTRY(move_alloc(e));
+        const WaitParams P = wait_params(e, from_mode, max_age);
+        const uint32_t grid = wait_grid(e);
+        uint32_t k1 = 0, k2 = 0;
+        MMTRY(wait_select(e, P, grid, &k1));
+        if (k1 == 0u) return MM_OK;
+        const MoveCols M = move_cols(e, cons_clear, to_mode, true);
+        MMTRY(rule_mark_and_fetch(e, P, grid, k1, *rule, &M, marked_on_device, &k2));
+        if (n_selected) *n_selected = k2;
+        return MM_OK;
+    });
 }
 
 // mm_rotate = mm_move onto the players' own chains, selected by the stored lobbies instead of by age: no queue is

@@ -131,34 +131,39 @@ __global__ __launch_bounds__(WT_THREADS) void k_wait_count(WaitParams P)
     }
 }
 
-// Exclusive scan down the rows of k_wait_count, in place; the total behind them.  One workgroup.
-__global__ __launch_bounds__(WT_THREADS) void k_wait_scan(WaitParams P)
+// Exclusive scan down n_rows counters, in place; the total goes to *total.  One workgroup; every thread must call it.
+static __device__ __forceinline__ void rows_scan_body(uint32_t* __restrict__ rows, uint32_t n_rows, uint32_t* __restrict__ total_out)
 {
     __shared__ uint32_t wtot[WT_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t chunks = 0;
-    for (uint32_t g = 0; g < P.n_groups; ++g) chunks += wait_chunks_of(dev_min_u32(P.chains[P.mode * P.n_groups + g].len, P.capacity));
-    chunks = dev_min_u32(chunks, P.max_chunks);
-    const uint32_t n_rows = chunks * WT_ROWS;
     const uint32_t per = (n_rows + WT_THREADS - 1) / WT_THREADS;
     const uint32_t r0 = dev_min_u32(tid * per, n_rows), r1 = dev_min_u32(r0 + per, n_rows);
     uint32_t s = 0;
-    for (uint32_t r = r0; r < r1; ++r) s += P.rows[r];
+    for (uint32_t r = r0; r < r1; ++r) s += rows[r];
     const uint32_t incl = wave_incl_scan(s, lane);
     if (lane == 63) wtot[wave] = incl;
     __syncthreads();
     uint32_t run = incl - s;
     for (int w = 0; w < wave; ++w) run += wtot[w];
     for (uint32_t r = r0; r < r1; ++r) {
-        const uint32_t h = P.rows[r];
-        P.rows[r] = run;
+        const uint32_t h = rows[r];
+        rows[r] = run;
         run += h;
     }
     if (tid == 0) {
         uint32_t total = 0;
         for (int w = 0; w < WT_WAVES; ++w) total += wtot[w];
-        P.rows[(size_t)P.max_chunks * WT_ROWS] = total;
+        *total_out = total;
     }
+}
+
+// Exclusive scan down the rows of k_wait_count, in place; the total behind them.  One workgroup.
+__global__ __launch_bounds__(WT_THREADS) void k_wait_scan(WaitParams P)
+{
+    uint32_t chunks = 0;
+    for (uint32_t g = 0; g < P.n_groups; ++g) chunks += wait_chunks_of(dev_min_u32(P.chains[P.mode * P.n_groups + g].len, P.capacity));
+    chunks = dev_min_u32(chunks, P.max_chunks);
+    rows_scan_body(P.rows, chunks * WT_ROWS, P.rows + (size_t)P.max_chunks * WT_ROWS);
 }
 
 // What mm_move's scatter gathers beside the list (include/mm_wait.h): the rows of an enqueue into the other mode, on the
@@ -185,14 +190,27 @@ static __device__ __forceinline__ bool wait_seat_at(const LobbyDev& lb, uint32_t
     return false;
 }
 
+// What the non-marking scatter of the mm_*_if calls writes at a candidate's rank instead of the list: the query record
+// par_count_body stages (x rating | y constraint word, un-rewritten | z rating group | w slot), the age the selection
+// computed, and the partner count preset to 0.  n: the candidates the columns have room for.
+struct CandCols {
+    uint4* rec;
+    uint32_t* age;
+    uint32_t* cnt;
+    uint32_t n;
+};
+
 // Every selected player at its rank, and marked as k_cancel marks a slot.  A slot is in one queue or one lobby, once:
 // the mark a thread sets is read by nobody else, so the selection is the one k_wait_count counted.
 // GATHER (mm_move): the selected player's row goes along — a queue entry's rating and constraint word from the position
 // the wave streams anyway (loaded with the slots, before the gathers of wait_load are waited for), a lobby seat's from
 // the LobbyDev record; the stamp is the clock minus the age the selection computed.
-template <bool GATHER>
-static __device__ __forceinline__ void wait_scatter_body(const WaitParams& P, const MoveCols& M)
+// CAND (mm_expire_if, mm_move_if, mm_move_out_if): the same selection at the same ranks, but NOTHING is marked and no
+// list is written — the row goes into C as a query record for the partner count; state[] is only read.
+template <bool GATHER, bool CAND>
+static __device__ __forceinline__ void wait_scatter_body(const WaitParams& P, const MoveCols& M, const CandCols& C)
 {
+    constexpr bool ROWS = GATHER || CAND;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned long long lt = (1ull << lane) - 1ull;
     for (uint32_t b = blockIdx.x;; b += gridDim.x) {
@@ -205,7 +223,7 @@ static __device__ __forceinline__ void wait_scatter_body(const WaitParams& P, co
             uint32_t sl[WT_ITERS], age[WT_ITERS];
             int32_t rt[WT_ITERS];
             uint32_t cn[WT_ITERS];
-            if (GATHER) {
+            if (ROWS) {
 #pragma unroll
                 for (uint32_t r = 0; r < WT_ITERS; ++r) {
                     const uint32_t i = w0 + r * 64 + lane;
@@ -219,7 +237,13 @@ static __device__ __forceinline__ void wait_scatter_body(const WaitParams& P, co
                 const bool sel = ((live >> r) & 1u) && age[r] > P.max_age;
                 const unsigned long long m = __ballot(sel);
                 const uint32_t at = base + (uint32_t)__popcll(m & lt);
-                if (sel && at < P.capacity) {
+                if (CAND) {
+                    if (sel && at < C.n) {
+                        C.rec[at] = make_uint4((uint32_t)rt[r], cn[r], g, sl[r]);
+                        C.age[at] = age[r];
+                        C.cnt[at] = 0u;
+                    }
+                } else if (sel && at < P.capacity) {
                     P.out_slot[at] = sl[r];
                     P.out_group[at] = g;
                     P.out_age[at] = age[r];
@@ -238,13 +262,19 @@ static __device__ __forceinline__ void wait_scatter_body(const WaitParams& P, co
             const LobbyDev& lb = P.chains[P.mode * P.n_groups + g].lobby;
             uint32_t age = 0, sl = MM_NO_SLOT, t = 0, i = 0;
             if (k == 0u && (uint32_t)lane < WT_SEATS) {
-                if (!GATHER) sl = wait_seat(lb, P.teams, (uint32_t)lane);
+                if (!ROWS) sl = wait_seat(lb, P.teams, (uint32_t)lane);
                 else if (wait_seat_at(lb, P.teams, (uint32_t)lane, t, i)) sl = lb.slot[t][i];
             }
             const bool sel = wait_age(P, sl, age) && age > P.max_age;
             const unsigned long long m = __ballot(sel);
             const uint32_t at = P.rows[(size_t)b * WT_ROWS] + (uint32_t)__popcll(m & lt);
-            if (sel && at < P.capacity) {
+            if (CAND) {
+                if (sel && at < C.n) {
+                    C.rec[at] = make_uint4((uint32_t)lb.rating[t][i], lb.cons[t][i], g, sl);
+                    C.age[at] = age;
+                    C.cnt[at] = 0u;
+                }
+            } else if (sel && at < P.capacity) {
                 P.out_slot[at] = sl;
                 P.out_group[at] = g;
                 P.out_age[at] = age;
@@ -260,17 +290,90 @@ static __device__ __forceinline__ void wait_scatter_body(const WaitParams& P, co
     }
 }
 
-__global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P)
+static __device__ __forceinline__ MoveCols move_cols_none()
 {
     MoveCols none;
     none.q_rating = nullptr; none.q_cons = nullptr; none.rating = nullptr; none.cons = nullptr;
     none.stamp = nullptr; none.group = nullptr; none.keep = 0u; none.to_mode = 0u;
-    wait_scatter_body<false>(P, none);
+    return none;
 }
+
+static __device__ __forceinline__ CandCols cand_cols_none()
+{
+    CandCols none;
+    none.rec = nullptr; none.age = nullptr; none.cnt = nullptr; none.n = 0u;
+    return none;
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_wait_scatter(WaitParams P) { wait_scatter_body<false, false>(P, move_cols_none(), cand_cols_none()); }
 
 // mm_move's and mm_move_out's scatter: the list as k_wait_scatter writes it, plus the rows — for k_bucket_* on this engine
 // (mm_move), or for the host to hand to another engine's mm_enqueue_stamped (mm_move_out reads rating, word and stamp back).
-__global__ __launch_bounds__(WT_THREADS) void k_move_scatter(WaitParams P, MoveCols M) { wait_scatter_body<true>(P, M); }
+__global__ __launch_bounds__(WT_THREADS) void k_move_scatter(WaitParams P, MoveCols M) { wait_scatter_body<true, false>(P, M, cand_cols_none()); }
+
+// The candidates of an mm_*_if call: who k_wait_count counted, as query records at their ranks.  M: q_rating and q_cons only.
+__global__ __launch_bounds__(WT_THREADS) void k_cand_scatter(WaitParams P, MoveCols M, CandCols C) { wait_scatter_body<false, true>(P, M, C); }
+
+// The second selection of the mm_*_if calls (include/mm_wait.h): candidate i of n stays iff lo <= cnt[i] <= hi, cnt the
+// partner count par_count_body left beside its record.  Count / scan / scatter again, over a LIST this time — a thread per
+// candidate, a row per wave (k_sel_count), rows_scan_body down the rows with the total behind them (k_sel_scan), then every
+// kept candidate goes to its rank in the call's final columns and is marked as k_cancel marks a slot (k_sel_scatter): a
+// stable compaction, so the list is mm_expire's order restricted to the kept.  The candidates and the final columns are
+// different buffers: a compaction in place would race across workgroups.
+struct SelParams {
+    uint32_t n, capacity;                     // candidates; slots of the pool
+    uint32_t lo, hi;                          // min_partners, max_partners
+    uint32_t now;
+    const uint4* rec;                         // [n] as CandCols
+    const uint32_t* age;
+    const uint32_t* cnt;
+    uint32_t* rows;                           // [ceil(n / 64)]; behind them the total
+    uint8_t* state;
+    uint32_t* out_slot;                       // the list, as WaitParams
+    uint32_t* out_group;
+    uint32_t* out_age;
+};
+
+static __device__ __forceinline__ uint32_t sel_rows_of(uint32_t n) { return (n + 63u) / 64u; }
+
+__global__ __launch_bounds__(SEL_TILE) void k_sel_count(SelParams S)
+{
+    const uint32_t i = blockIdx.x * SEL_TILE + threadIdx.x;
+    const uint32_t c = i < S.n ? S.cnt[i] : 0u;
+    const unsigned long long m = __ballot(i < S.n && c >= S.lo && c <= S.hi);
+    if ((threadIdx.x & 63) == 0 && i < S.n) S.rows[i >> 6] = (uint32_t)__popcll(m);
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_sel_scan(SelParams S) { rows_scan_body(S.rows, sel_rows_of(S.n), S.rows + sel_rows_of(S.n)); }
+
+// ROWS (mm_move_if, mm_move_out_if): the rows of the enqueue go along, the constraint word rewritten here.
+template <bool ROWS>
+static __device__ __forceinline__ void sel_scatter_body(const SelParams& S, const MoveCols& M)
+{
+    const uint32_t i = blockIdx.x * SEL_TILE + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const uint32_t c = i < S.n ? S.cnt[i] : 0u;
+    const bool sel = i < S.n && c >= S.lo && c <= S.hi;
+    const unsigned long long m = __ballot(sel);
+    if (!sel) return;
+    const uint32_t at = S.rows[i >> 6] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    const uint4 q = S.rec[i];
+    if (at >= S.capacity || q.w >= S.capacity) return;
+    const uint32_t age = S.age[i];
+    S.out_slot[at] = q.w;
+    S.out_group[at] = q.z;
+    S.out_age[at] = age;
+    if (ROWS) {
+        M.rating[at] = (int32_t)q.x;
+        M.cons[at] = (q.y & M.keep) | M.to_mode;
+        M.group[at] = (uint8_t)q.z;
+        M.stamp[at] = S.now - age;
+    }
+    S.state[q.w] = MM_ST_CANCELLED;
+}
+
+__global__ __launch_bounds__(SEL_TILE) void k_sel_scatter(SelParams S) { sel_scatter_body<false>(S, move_cols_none()); }
+__global__ __launch_bounds__(SEL_TILE) void k_sel_scatter_rows(SelParams S, MoveCols M) { sel_scatter_body<true>(S, M); }
 
 // mm_rotate (include/mm_wait.h): the LIVE seats of the stored lobbies of one mode leave and rejoin their own queue's
 // tail.  No queue is streamed: a chain is selected by its LobbyDev record, state[] of its seats and ChainDev.len alone, so

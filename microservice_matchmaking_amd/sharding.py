@@ -192,16 +192,47 @@ class ShardedSearch:
         after the sources have expired their players and the destinations WITH room have taken theirs in (those players
         wait there under their global index)."""
         if self.world_size != 1:
-            return self._move_across_ranks(from_mode, to_mode, max_age, cons_clear)
-        got = self.engine.move(from_mode, to_mode, max_age, cons_clear)
+            return self._move_across_ranks(from_mode, to_mode, lambda: self.engine.move_out(from_mode, to_mode, max_age, cons_clear))
+        return self._moved_here(self.engine.move(from_mode, to_mode, max_age, cons_clear))
+
+    def _moved_here(self, got):
         ok = got[3] != NO_SLOT
         self.local_to_global[got[3][ok].astype(np.int64)] = self.local_to_global[got[0][ok].astype(np.int64)]
         return got
 
-    def _move_across_ranks(self, from_mode, to_mode, max_age, cons_clear):
+    def _chain_local(self, what, mode, rule):
+        """The rule's in_mode (None: `mode`), which on several ranks must be `mode`: chain (mode, g) and chain (in_mode, g)
+        may have different owners, as for `partners`."""
+        in_mode = rule.in_mode if hasattr(rule, "in_mode") else dict(rule).get("in_mode")
+        if self.world_size != 1 and in_mode is not None and in_mode != mode:
+            raise NotImplementedError("ShardedSearch.%s with in_mode != mode on several ranks: chain (mode %d, g) and chain "
+                                      "(in_mode %d, g) may have different owners, and carrying query rows between ranks is "
+                                      "not built" % (what, mode, in_mode))
+
+    def move_if(self, from_mode, to_mode, max_age, cons_clear=0, rule=None):
+        """mm_move_if (include/mm_wait.h): `move` over the players whose partner count lies in the rule's range.  On ONE
+        rank it is the engine's mm_move_if.  On several, with the rule's in_mode == from_mode, the selection is chain-local
+        (the candidates are the waiting players of the chain the player sits in, which this rank owns) and the rest is
+        `move`'s collective with mm_move_out_if in mm_move_out's place; with in_mode != from_mode the query rows would have
+        to travel between ranks: not built, NotImplementedError on every rank."""
+        rule = rule or {}
+        self._chain_local("move_if", from_mode, rule)
+        if self.world_size != 1:
+            return self._move_across_ranks(from_mode, to_mode,
+                                           lambda: self.engine.move_out_if(from_mode, to_mode, max_age, cons_clear, rule))
+        return self._moved_here(self.engine.move_if(from_mode, to_mode, max_age, cons_clear, rule))
+
+    def expire_if(self, mode, max_age, rule):
+        """mm_expire_if (include/mm_wait.h).  Chain-local for the rule's in_mode == mode: every rank expires on the chains
+        it owns, no collective.  in_mode != mode on several ranks: NotImplementedError on every rank, as `move_if`."""
+        self._chain_local("expire_if", mode, rule)
+        return self.engine.expire_if(mode, max_age, rule)
+
+    def _move_across_ranks(self, from_mode, to_mode, move_out):
+        """`move_out`: this rank's selection call, mm_move_out or mm_move_out_if -> its six columns."""
         if not 0 <= int(to_mode) < self.cfg.n_modes:
             raise MMError(-1, "move across ranks (to_mode)")
-        old, group, age, rating, cons, stamp = self.engine.move_out(from_mode, to_mode, max_age, cons_clear)
+        old, group, age, rating, cons, stamp = move_out()
         gid = self.local_to_global[old.astype(np.int64)]
         rows = np.stack([group.astype(np.int64), rating.astype(np.int64), cons.astype(np.int64), stamp.astype(np.int64),
                          gid, np.full(old.size, self.rank, np.int64), np.arange(old.size, dtype=np.int64)], axis=1)

@@ -60,7 +60,9 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
     the deepest the queues were after a tick).  None: no clock, nothing of this runs.
     `fallback`: rules [(from_mode, to_mode, after_ms, cons_clear)] of mm_move (include/mm_wait.h): every period, after the
     clock is set and the arrivals are in and before the expiry, whoever has waited in from_mode for longer than after_ms
-    moves to to_mode with its stamp, the rules in list order (so tiers chain within a period).  The clock runs as for
+    moves to to_mode with its stamp, the rules in list order (so tiers chain within a period).  A rule may carry a fifth
+    element, a partner rule (_abi.PartnerRule or a dict of its fields): the move is then mm_move_if — of the players old
+    enough only those whose partner count lies in the rule's range (ShardedSearch.move_if).  The clock runs as for
     ttl_ms; the result also holds `moved` and `refused` (players per rule: the ones THIS rank selected, and the ones it
     refused — on several ranks every rank calls the move collectively, sharding.ShardedSearch.move, and the sums over the
     ranks are the one-engine figures), `wait_ms` and `depth_max`.  A move that finds a destination without room
@@ -167,8 +169,11 @@ def run_stream(search, schedule, mode_weights=None, role_weights=None, realtime=
                 break
             first += n
             try:
-                for i, (src, dst, after_ms, cons_clear) in enumerate(fallback):
-                    got = search.move(src, dst, int(after_ms), int(cons_clear))
+                for i, (src, dst, after_ms, cons_clear, *rule) in enumerate(fallback):
+                    if rule:
+                        got = search.move_if(src, dst, int(after_ms), int(cons_clear), rule[0])
+                    else:
+                        got = search.move(src, dst, int(after_ms), int(cons_clear))
                     moved[i] += int(got[0].size)
                     refused[i] += int((search.engine if search.world_size == 1 else search).last_move["refused"])
             except MMError as ex:
