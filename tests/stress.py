@@ -2,7 +2,7 @@
 """Test infrastructure (it drives the oracle, so it lives under tests/).  Randomised differential stress on a real GPU: HIP engine vs oracle over many seeded
 scenarios (pool sizes that hit the LDS-resident walk, the tiled rounds and the hand-over
 between them; windows from 0 to wider than the rating span; 1..64 regions; multi-tick with
-arrivals and cancels).  Usage: python tests/stress.py [seconds] [seed] [team] [--fuzz-knobs] [--wide] [--edges] [--patterns]
+arrivals and cancels).  Usage: python tests/stress.py [seconds] [seed] [team] [--fuzz-knobs] [--wide] [--edges] [--patterns] [--wait]
 
 --fuzz-knobs (round 6): every scenario's engine is created with a random COMBINATION of the engine's tuning fields
 (include/mm_engine.h mm_tuning, passed per engine through mm_engine_create_ex) off their defaults — batch sizes, the
@@ -24,6 +24,11 @@ behaviour, read from the source and computed from the drawn tuning), d from -2 .
 shifted, sorted, runs, interleaved, blocked head, dead tiles, alive share; with `team`: dense, nested, shifted members,
 scarce / sorted / missing roles) with its parameter from the geometry tables of the drawn tuning; later batches are
 another pattern or a random pool; cancels are a whole range, every m-th player or random.  A stream of its own.
+
+--wait: the wait layer (include/mm_wait.h) in front of the long-chain walks instead — tests/long_chain_scenarios.py's
+long_script with a drawn seed, round count and restart round: moves, rule calls, stamped enqueues, rotations, locate and
+partners between ticks whose chains the tiled pair path and the team path take, against the oracle and the numpy witnesses
+after every call; sizes from tests/geometry.py for the engine's build.  A stream of its own.
 
 MM_STRESS_ENGINE=emu_small runs the same scenarios without a GPU on the fiber-shim build of the
 kernel source with the tiny tile geometry (tests/emu/), pool sizes divided by 16 so that they
@@ -438,6 +443,37 @@ def team_main(budget, seed0):
     print("gpu_stress team%s: %d scenarios ok (seeds %d..%d)" % (" --fuzz-knobs" if FUZZ else "", n_done, seed0 * 100003, seed0 * 100003 + k - 1))
 
 
+def wait_main(budget, seed0):
+    """--wait: long_chain_scenarios.long_script, drawn."""
+    import geometry as G
+    from long_chain_scenarios import long_script
+    geo = G.geometry(Engine, small=SCALE != 1)
+    t_end = time.time() + budget
+    n_done = 0
+    k = 0
+    only = os.environ.get("MM_STRESS_ONLY")
+    while time.time() < t_end:
+        seed = seed0 * 100003 + k
+        k += 1
+        if only:
+            if k > 1:
+                break
+            seed = int(only)
+        rng = np.random.default_rng([seed, 0x77616974])
+        rounds = int(rng.integers(2, 4))
+        restart_at = (int(rng.integers(0, rounds)),) if rng.integers(0, 3) == 0 else ()
+        tuning = draw_tuning(seed, [PAIR_KNOBS, TEAM_KNOBS])
+        tag = "wait seed %d rounds=%d restart_at=%s tuning=%s" % (seed, rounds, restart_at, tuning)
+        if os.environ.get("MM_STRESS_VERBOSE"):
+            print(tag, flush=True)
+        try:
+            long_script(Engine, OracleEngine, geo, seed=seed, rounds=rounds, restart_at=restart_at, tuning=tuning, coverage=False)
+        except AssertionError as ex:
+            raise AssertionError("%s: %s" % (tag, ex)) from ex
+        n_done += 1
+    print("gpu_stress --wait%s: %d scenarios ok (seeds %d..%d)" % (" --fuzz-knobs" if FUZZ else "", n_done, seed0 * 100003, seed0 * 100003 + k - 1))
+
+
 def main(argv=None):
     global FUZZ
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -449,6 +485,8 @@ def main(argv=None):
         return wide_main(budget, seed0)
     if "--edges" in argv:
         return edges_main(budget, seed0)
+    if "--wait" in argv:
+        return wait_main(budget, seed0)
     if "--patterns" in argv:
         return patterns_main(budget, seed0, team=len(ARGV) > 2 and ARGV[2] == "team")
     if len(ARGV) > 2 and ARGV[2] == "team":

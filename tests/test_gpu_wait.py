@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "wait_gpu_worker.py")
 
 # seconds: a generous multiple of what the oracle (the slow side) needs for the scenario
-LIMITS = {"script_seed1": 240, "script_seed2": 240, "script_generic_walk": 300, "script_restart": 420,
+LIMITS = {"script_seed1": 240, "script_seed2": 240, "script_generic_walk": 300, "script_restart": 420, "script_tiled": 240,
           "cfg2_1m": 420, "cfg3_1m": 420}
 # The targeted cases of tests/test_wait.py at its sizes (pools of 900 to 6000, chains of WT_CHUNK +- 1).  Measured once on an
 # MI355X, the whole process (interpreter and imports included) / the drivers alone, in seconds:

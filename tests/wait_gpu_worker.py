@@ -22,7 +22,8 @@ from wait_scenarios import (Tracker, assert_wait_stats, expire_both, expiry_scri
 
 
 def script(seed, restart_at=(), tuning=None):
-    """Script 1 at product geometry: tens of thousands of players a mode, so the tiled pair path, the team path and
+    """Script 1 at product geometry: tens of thousands of players a mode over seven rating groups, so the LDS-resident pair
+    walk (kp_late: the longest 1v1 chain stays under PL_MAX; script_tiled below reaches the tiled rounds), the team path and
     the selection kernels' many-chunk grids all see expired entries.  Every mode expires in every round, with a
     threshold drawn from the range of one round's clock step, so whoever a round leaves behind is about as likely to go
     as to stay.  What the script must have covered to count: expired lists that together are longer than one workgroup's
@@ -38,6 +39,37 @@ def script(seed, restart_at=(), tuning=None):
 
 def script_restart(seed):
     assert script(seed) == script(seed, restart_at=(1, 3))
+
+
+TWO_GROUPS = [(0, 2499, "low"), (2500, 5000, "high")]
+
+
+def script_tiled(seed, engine_cls=Engine, small=False):
+    """The same script on a two-group table with batches of up to 8 x PL_MAX players over its three modes: mode 0's longest
+    chain reaches PL_MAX (asserted before the first tick), in the first round and again whenever a later batch is large enough,
+    so the tiled pair rounds filter expired entries.  What it must have covered: pair_tiled_passes > 0 in a tick of mode 0 of
+    a round whose expiry of mode 0 selected somebody."""
+    import geometry as G
+    pl_max = G.geometry(engine_cls, small=small)["PL_MAX"]
+    ticks = []
+
+    class Recording(engine_cls):
+        def tick(self, mode=0, *args, **kw):
+            if not ticks:
+                assert int(self.queue_depth(0).max()) >= pl_max, (self.queue_depth(0), pl_max)
+            m = super().tick(mode, *args, **kw)
+            ticks.append((mode, self.path_stats()["pair_tiled_passes"]))
+            return m
+
+    cfg = make_config([mode_1v1(window=40, region_filter=True), mode_team(2, 3, 300, (1, 1)), mode_team(5, 2, 200, (1, 1, 1, 1, 1))],
+                      capacity=1 << (40 * pl_max).bit_length(), groups=TWO_GROUPS)
+    log = expiry_script(Recording, OracleEngine, cfg=cfg, seed=seed, rounds=4, first=8 * pl_max, batch=8 * pl_max,
+                        cancel_frac=0.02, expire_p=1.0, age_max=60)
+    assert len(ticks) == 3 * 4
+    tiled = [ticks[3 * rnd][1] for rnd in range(4)]                                  # mode 0's tick of every round
+    expired = [sum(len(x[3]) for x in log if x[0] == "expired" and x[1] == rnd and x[2] == 0) for rnd in range(4)]
+    print("script_tiled: mode 0 per round: pair_tiled_passes %s, expired just before %s" % (tiled, expired))
+    assert any(t > 0 and x > 0 for t, x in zip(tiled, expired)), (tiled, expired)
 
 
 def million(mode_dict, pool_kw, seed, n=1_000_000, engine_cls=Engine):
@@ -127,6 +159,7 @@ CASES = {
     "script_seed2": lambda: script(2),
     "script_generic_walk": lambda: script(3, tuning={"force_generic": 1}),
     "script_restart": lambda: script_restart(4),
+    "script_tiled": lambda: script_tiled(3),      # (round 1: a chain of 20 145 entries of which 1 399 have just expired)
     "cfg2_1m": lambda: million(mode_1v1(window=25, region_filter=True), {}, 1),
     "cfg3_1m": lambda: million(mode_team(5, 2, 50, (1, 1, 1, 1, 1)), {"role_weights": ROLE_WEIGHTS_5V5}, 2),
 }
