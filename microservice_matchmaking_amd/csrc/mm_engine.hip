@@ -2955,8 +2955,8 @@ static int report_pair(mm_engine* e)
     HIPCHK(e, hipMemcpy(hp.data(), e->d_pchains, G * sizeof(PairChain), hipMemcpyDeviceToHost));
     for (uint32_t g = 0; g < G; ++g)
         fprintf(stderr, "[mm-pair] g%u fast %u m %u qlen %u passes %u out %u rounds %u (group hops of tile 0: %u of %u entries looked at, %u not of the round) | stale %u inv %u slowsucc %u compact %u fixed(w1) %u | chase clk %u wall(100MHz) %u wrapscan clk %u\n",
-                g, hp[g].fast, hp[g].m, hp[g].qlen, hp[g].passes, hp[g].n_out, hp[g].rounds, hp[g].ghops, hp[g].gtry, hp[g].gstale, hp[g].dbg[0], hp[g].dbg[1],
-                hp[g].dbg[2], hp[g].dbg[3], hp[g].dbg[4], hp[g].dbg[5], hp[g].dbg[6], hp[g].dbg[7]);
+                g, hp[g].fast, hp[g].m, hp[g].qlen, hp[g].passes, hp[g].n_out, hp[g].rounds, hp[g].ghops, hp[g].gtry, hp[g].gstale, hp[g].dbg[PD_STALE], hp[g].dbg[PD_INV],
+                hp[g].dbg[PD_SLOWSUCC], hp[g].dbg[PD_COMPACT], hp[g].dbg[PD_FIXED], hp[g].dbg[PD_CLK], hp[g].dbg[PD_WALL], hp[g].dbg[PD_WRAPC]);
     for (uint32_t g = 0; g < G; ++g)
         if (hp[g].rounds) {
             const uint32_t nr = hp[g].tm[5] ? hp[g].tm[5] : 1u;
@@ -3042,8 +3042,8 @@ static void path_stats_pair(mm_engine* e, uint32_t mode)
         e->ps.crit_timed_hops = pc.ptm[15];
         e->ps.crit_barrier_cycles = pc.ptm[0];
         e->ps.crit_hop_cycles = pc.ptm[3];
-        e->ps.clk_cycles = pc.dbg[5];
-        e->ps.clk_wall_ticks = pc.dbg[6];
+        e->ps.clk_cycles = pc.dbg[PD_CLK];
+        e->ps.clk_wall_ticks = pc.dbg[PD_WALL];
     }
     if (e->ev_nx_set) {
         float ms = 0.f;

@@ -110,6 +110,18 @@ struct RoundState {
     unsigned long long pairs, scanned;
 };
 
+// PairChain.dbg[]: what kp_late counted in the tick (late_store writes them; report_pair and path_stats_pair read them)
+enum : uint32_t {
+    PD_STALE = 0,          // careful steps whose next[] pointed at a player who had left
+    PD_INV = 1,            // ... whose next[] was unknown
+    PD_SLOWSUCC = 2,       // careful steps
+    PD_COMPACT = 3,        // compactions inside the kernel
+    PD_FIXED = 4,          // repairs done by wave 3
+    PD_CLK = 5,            // the chaser: shader-clock cycles
+    PD_WALL = 6,           // ... and 100 MHz ticks
+    PD_WRAPC = 7           // ... of the cycles, the carried anchor's scans from the head of the queue
+};
+
 struct PairChain {
     uint32_t fast;         // 1 = this chain is walked by the pair path this tick
     uint32_t m;            // index-space length
@@ -126,7 +138,7 @@ struct PairChain {
     unsigned long long pairs, scanned;
     unsigned long long tested;   // diagnostics (MM_PAIR_TUNE bit 13): predicate tests the kernels physically performed
     unsigned long long tested_nx;   // ... of them in kp_nx_init
-    uint32_t dbg[8];       // diagnostics (MM_PAIR_DEBUG): stale hits, rescans, slow successors, ...
+    uint32_t dbg[8];       // diagnostics (MM_PAIR_DEBUG): PD_* above
     // tiled path
     uint32_t stage;        // PS_TILED: walked by the tile kernels; PS_LATE: fits kp_late; PS_DONE
     uint32_t ntiles;
@@ -488,75 +500,73 @@ static __device__ __forceinline__ uint32_t l_alive(const uint32_t* bits, uint32_
     return (lds_ld(bits + (i >> 5)) >> (i & 31u)) & 1u;
 }
 
-// first index in [from, end) whose key is queued (no dead flag) and fits akey, or PK_NO.
-// Wave-wide.  `ev`, when given, aborts the scan (PK_ABORT) once an event is posted.
-static __device__ __forceinline__ uint32_t l_scan_fit(const uint32_t* key, uint32_t akey, uint32_t from, uint32_t end,
-                                                      uint32_t w, int lane, const uint32_t* ev)
+// One round trip to LDS of a scan for the first queued key (no dead flag) inside [klo, klo + krng]: N 64-candidate
+// steps from p, all N * 64 of them inside the chain — N keys per lane loaded, then balloted in order.  The first
+// fit's index, or PK_NO.  ABORTABLE: `ev` is read along with the keys, and a trip without a fit that saw an event
+// posted says PK_ABORT.  Wave-wide.
+template <uint32_t N, bool ABORTABLE>
+static __device__ __forceinline__ uint32_t l_scan_trip(const uint32_t* key, uint32_t klo, uint32_t krng, uint32_t p, int lane,
+                                                       const uint32_t* ev = nullptr)
 {
-    uint32_t klo, krng;
+    uint32_t kv[N];
+#pragma unroll
+    for (uint32_t u = 0; u < N; ++u) kv[u] = lds_ld(key + p + 64u * u + (uint32_t)lane);
+    uint32_t e = EV_NONE;
+    if (ABORTABLE) e = lds_ld(ev);
+#pragma unroll
+    for (uint32_t u = 0; u < N; ++u) {
+        const unsigned long long b = __ballot(pk_in(kv[u], klo, krng));
+        if (b) return p + 64u * u + (uint32_t)__ffsll(b) - 1u;
+    }
+    return ABORTABLE && uni(e) != EV_NONE ? PK_ABORT : PK_NO;
+}
+// ... and one bounded step of it: the chain may end inside the 64 candidates from p
+static __device__ __forceinline__ uint32_t l_scan_step(const uint32_t* key, uint32_t klo, uint32_t krng, uint32_t p, uint32_t end, int lane)
+{
+    const uint32_t c = p + (uint32_t)lane;
+    const bool ok = c < end && pk_in(lds_ld(key + c), klo, krng);
+    const unsigned long long b = __ballot(ok);
+    return b ? p + (uint32_t)__ffsll(b) - 1u : PK_NO;
+}
+
+// first index in [from, end) whose key is queued (no dead flag) and fits akey, or PK_NO.  Wave-wide.
+// The chaser's own scans (nobody aborts them): four 64-candidate steps per round trip to LDS — late in a tick the
+// carried anchor's first fit from the head of the queue lies thousands of positions away, one dependent read per step
+// (round 5: one trip of four steps for the fit that lies near, then SIXTEEN steps a trip — the carried anchor's scan of
+// a late pass runs over thousands of positions, 2.1k cycles a pass of the longest chain at four steps a trip)
+static __device__ __forceinline__ uint32_t l_scan_fit(const uint32_t* key, uint32_t akey, uint32_t from, uint32_t end, uint32_t w, int lane)
+{
+    uint32_t klo, krng, j;
     pk_bounds(akey, w, klo, krng);
     uint32_t p = from;
-    if (!ev) {
-        // the chaser's own scans (nobody aborts them): four 64-candidate steps per round trip to LDS — late in a tick the
-        // carried anchor's first fit from the head of the queue lies thousands of positions away, one dependent read per step
-        // (round 5: one trip of four steps for the fit that lies near, then SIXTEEN steps a trip — the carried anchor's scan of
-        // a late pass runs over thousands of positions, 2.1k cycles a pass of the longest chain at four steps a trip)
-        if (p + 256u <= end) {
-            uint32_t kv[4];
-#pragma unroll
-            for (uint32_t u = 0; u < 4u; ++u) kv[u] = lds_ld(key + p + 64u * u + (uint32_t)lane);
-#pragma unroll
-            for (uint32_t u = 0; u < 4u; ++u) {
-                const unsigned long long b = __ballot(pk_in(kv[u], klo, krng));
-                if (b) return p + 64u * u + (uint32_t)__ffsll(b) - 1u;
-            }
-            p += 256u;
-        }
-        for (; p + 1024u <= end; p += 1024u) {
-            uint32_t kv[16];
-#pragma unroll
-            for (uint32_t u = 0; u < 16u; ++u) kv[u] = lds_ld(key + p + 64u * u + (uint32_t)lane);
-#pragma unroll
-            for (uint32_t u = 0; u < 16u; ++u) {
-                const unsigned long long b = __ballot(pk_in(kv[u], klo, krng));
-                if (b) return p + 64u * u + (uint32_t)__ffsll(b) - 1u;
-            }
-        }
-        for (; p + 256u <= end; p += 256u) {
-            uint32_t kv[4];
-#pragma unroll
-            for (uint32_t u = 0; u < 4u; ++u) kv[u] = lds_ld(key + p + 64u * u + (uint32_t)lane);
-#pragma unroll
-            for (uint32_t u = 0; u < 4u; ++u) {
-                const unsigned long long b = __ballot(pk_in(kv[u], klo, krng));
-                if (b) return p + 64u * u + (uint32_t)__ffsll(b) - 1u;
-            }
-        }
+    if (p + 256u <= end) {
+        if ((j = l_scan_trip<4, false>(key, klo, krng, p, lane)) != PK_NO) return j;
+        p += 256u;
     }
-    if (ev) {
-        // the repair waves' scans (round 5): four steps a trip as well, the event looked at once per trip — late in a tick a
-        // repair scans thousands of positions, the thirteen waves were as busy as the pass is long (one 64-candidate step
-        // per dependent read) and the chaser met what they had not reached yet: ~330 careful steps a tick on stale entries
-        // (sixteen steps a trip, as the chaser's own scan has them, bring the repairs nothing more: 87 stale hits against 96)
-        for (; p + 256u <= end; p += 256u) {
-            uint32_t kv[4];
-#pragma unroll
-            for (uint32_t u = 0; u < 4u; ++u) kv[u] = lds_ld(key + p + 64u * u + (uint32_t)lane);
-            const uint32_t e = lds_ld(ev);
-#pragma unroll
-            for (uint32_t u = 0; u < 4u; ++u) {
-                const unsigned long long b = __ballot(pk_in(kv[u], klo, krng));
-                if (b) return p + 64u * u + (uint32_t)__ffsll(b) - 1u;
-            }
-            if (uni(e) != EV_NONE) return PK_ABORT;
-        }
-    }
+    for (; p + 1024u <= end; p += 1024u)
+        if ((j = l_scan_trip<16, false>(key, klo, krng, p, lane)) != PK_NO) return j;
+    for (; p + 256u <= end; p += 256u)
+        if ((j = l_scan_trip<4, false>(key, klo, krng, p, lane)) != PK_NO) return j;
+    for (; p < end; p += 64u)
+        if ((j = l_scan_step(key, klo, krng, p, end, lane)) != PK_NO) return j;
+    return PK_NO;
+}
+// The same for the repair waves, which give up (PK_ABORT) once an event is posted at `ev`.
+// (round 5): four steps a trip as well, the event looked at once per trip — late in a tick a
+// repair scans thousands of positions, the thirteen waves were as busy as the pass is long (one 64-candidate step
+// per dependent read) and the chaser met what they had not reached yet: ~330 careful steps a tick on stale entries
+// (sixteen steps a trip, as the chaser's own scan has them, bring the repairs nothing more: 87 stale hits against 96)
+static __device__ __forceinline__ uint32_t l_scan_fit_ev(const uint32_t* key, uint32_t akey, uint32_t from, uint32_t end, uint32_t w, int lane,
+                                                         const uint32_t* ev)
+{
+    uint32_t klo, krng, j;
+    pk_bounds(akey, w, klo, krng);
+    uint32_t p = from;
+    for (; p + 256u <= end; p += 256u)
+        if ((j = l_scan_trip<4, true>(key, klo, krng, p, lane, ev)) != PK_NO) return j;
     for (; p < end; p += 64u) {
-        const uint32_t c = p + (uint32_t)lane;
-        const bool ok = c < end && pk_in(lds_ld(key + c), klo, krng);
-        const unsigned long long b = __ballot(ok);
-        if (b) return p + (uint32_t)__ffsll(b) - 1u;
-        if (ev && lds_ld(ev) != EV_NONE) return PK_ABORT;
+        if ((j = l_scan_step(key, klo, krng, p, end, lane)) != PK_NO) return j;
+        if (lds_ld(ev) != EV_NONE) return PK_ABORT;
     }
     return PK_NO;
 }
@@ -592,8 +602,11 @@ static __device__ __forceinline__ uint32_t l_succ(const uint32_t* bits, uint32_t
 //            (i, next[i]) is emitted;  PL_S when unknown or when the queue ends first
 // Both only go stale by their target leaving the queue, which the bitmap shows.  The walk
 // a -> g[a] -> g[g[a]] ... is then a bare chain of dependent LDS reads (three instructions a
-// step); 64 steps are chased blind, checked against the bitmap by 64 lanes at once, and the
-// confirmed prefix is handed to the consumer waves (1: bitmap, 2: emission).  Thirteen waves keep nxg repaired.
+// step; late_blind_chase); 64 steps are chased blind, checked against the bitmap by 64 lanes at once
+// (late_blind_check), and the confirmed prefix is handed through the ring (LateRing::push_block) to the
+// consumer waves (wave 1, late_kill: bitmap; wave 2, late_emit: emission).  An anchor the blind chase cannot
+// take — carried in, stale or unknown next[] — gets one careful step (late_careful_step).  Thirteen waves
+// keep nxg repaired (late_repair).  The chaser's own state is a LateCursor, what it counts a LateDiag.
 static __device__ __forceinline__ uint32_t nxg_make(uint32_t t, uint32_t gi) { return t | ((gi << 2) << 16); }
 
 // first queued index >= from (one lane's own loop), or PL_S
@@ -609,18 +622,498 @@ static __device__ __forceinline__ uint32_t lane_succ(const uint32_t* bits, uint3
     return (wi << 5) + (uint32_t)__ffs((int)v) - 1u;
 }
 
+// kp_late's LDS, one object.
+struct LateLds {
+    uint32_t path[PL_SPEC];         // first in LDS: the chase addresses it with immediates
+    uint32_t nxg[PL_MAX];
+    uint32_t key[PL_MAX];
+    uint32_t bits[PL_WORDS + 64];   // zero padded: 64 words can be read past the end
+    uint16_t wpre[PL_WORDS];        // compaction: queued players before the word
+    uint32_t ring[PL_RING];         // anchor | partner << 16
+    uint16_t ringp[PL_RING];        // pass of the step, relative to the kernel's first
+    uint32_t wtot[16];
+    uint32_t event, m, head, tail, killed, aidx, buf, nout;
+    uint32_t ext[5];                // anchor by value: slot, rating, cons, key, team
+};
+
+// The ring of steps of the walk between the chaser and the consumer: head (pushed by wave 0) >= killed (both players
+// out of the bitmap, wave 1) >= tail (lobby emitted, wave 2: the slot is free again).  rk / rtail are the chaser's
+// registers: steps pushed, the consumer's tail as last seen.
+struct LateRing {
+    LateLds& S;
+    const int lane;
+    uint32_t rk = 0, rtail = 0;
+    __device__ __forceinline__ LateRing(LateLds& S_, int lane_) : S(S_), lane(lane_) {}
+    // the consumers' side: step i's (anchor | partner << 16), its pass
+    __device__ __forceinline__ uint32_t step(uint32_t i) const { return S.ring[i % PL_RING]; }
+    __device__ __forceinline__ uint32_t pass_of(uint32_t i) const { return S.ringp[i % PL_RING]; }
+    // the chaser's side: wait until n more steps fit
+    __device__ __forceinline__ void room(uint32_t n)
+    {
+        if (rk - rtail + n > PL_RING) {
+            rtail = uni(lds_ld(&S.tail));
+            while (rk - rtail + n > PL_RING) { __builtin_amdgcn_s_sleep(2); rtail = uni(lds_ld(&S.tail)); }
+        }
+    }
+    // ns steps handed to the consumer, lane l's the (ia, it) of lane l: it drops both players from the queue
+    // bitmap and, when there is a partner, emits the lobby
+    __device__ __forceinline__ void push_block(uint32_t ns, uint32_t ia, uint32_t it, uint32_t pass)
+    {
+        room(ns);
+        if ((uint32_t)lane < ns) {
+            S.ring[(rk + (uint32_t)lane) % PL_RING] = ia | (it << 16);
+            S.ringp[(rk + (uint32_t)lane) % PL_RING] = (uint16_t)pass;
+        }
+        rk += ns;
+        if (lane == 0) lds_st(&S.head, rk);
+    }
+    // one step (a, t), wave uniform
+    __device__ __forceinline__ void push(uint32_t a, uint32_t t, uint32_t pass) { push_block(1u, a, t, pass); }
+    // until every pushed step is in the bitmap (emission may still be under way)
+    __device__ __forceinline__ void drain()
+    {
+        uint32_t kd = uni(lds_ld(&S.killed));
+        while (kd != rk) { __builtin_amdgcn_s_sleep(1); kd = uni(lds_ld(&S.killed)); }
+    }
+};
+
+// The chaser's state (wave 0; uniform across its lanes).  a_idx: index of the anchor, or PL_EXT when it is
+// held by value (carried in from an earlier tick / over a compaction).
+struct LateCursor {
+    uint32_t has_anchor, a_idx, a_pushed;
+    uint32_t qlen, pos, passes, in_pass, changed, n_out;
+    unsigned long long pairs, scanned;
+    // the pass is over; false: it changed nothing, and the walk is over with it
+    __device__ __forceinline__ bool end_pass() { ++passes; in_pass = 0; return changed != 0u; }
+    // empty lobby: the popped player opens it (no pair evaluation)
+    __device__ __forceinline__ void open_lobby(uint32_t a)
+    {
+        --qlen; --pairs; changed = 1; has_anchor = 1; a_idx = a; a_pushed = 0;
+        pos = a + 1u;
+    }
+};
+static __device__ __forceinline__ LateCursor late_cursor_open(const PairChain* pc)
+{
+    LateCursor C;
+    C.has_anchor = pc->has_anchor; C.a_idx = PL_EXT; C.a_pushed = 1;
+    C.qlen = pc->qlen; C.pos = pc->pos0; C.passes = pc->passes; C.in_pass = pc->pos0 ? 1u : 0u; C.changed = pc->changed0;
+    C.n_out = pc->n_out;
+    C.pairs = pc->pairs; C.scanned = pc->scanned;
+    if (pc->pos0) { C.scanned += C.qlen + pc->extra0; C.pairs += C.qlen + pc->extra0; }    // the pass is already under way
+    return C;
+}
+static __device__ __forceinline__ void late_cursor_commit(PairChain* pc, const LateCursor& C)
+{
+    pc->pos0 = 0; pc->changed0 = 0; pc->extra0 = 0;
+    pc->qlen = C.qlen; pc->has_anchor = C.has_anchor; pc->passes = C.passes; pc->n_out = C.n_out;
+    pc->pairs = C.pairs; pc->scanned = C.scanned;
+}
+
+// What the waves count (PairChain.dbg[PD_*], PairChain.tested).
+struct LateDiag {
+    uint32_t stale = 0, inv = 0, slowsucc = 0, compact = 0, fixed = 0, clk = 0, wall = 0, wrapc = 0;
+    unsigned long long tst = 0;      // candidates this wave's scans were tested against
+};
+
+static __device__ __forceinline__ uint32_t late_anchor_key(const LateLds& S, uint32_t a_idx)
+{
+    return a_idx == PL_EXT ? S.ext[3] : (S.key[a_idx] & ~PK_DEAD);
+}
+
+// ---- load the chain: bitmap, keys with dead flags, nxg from nx16 ----
+static __device__ __forceinline__ void late_load(const PairParams& P, const PairChain* pc, LateLds& S, uint32_t m, uint32_t g, size_t po, int tid)
+{
+    const uint32_t nwords = (m + 31u) >> 5;
+    for (uint32_t i = tid; i < PL_WORDS + 64u; i += PL_THREADS)
+        S.bits[i] = i < nwords ? P.bits[pc->buf][(size_t)g * P.bits_stride + i] : 0u;
+    const uint32_t* const key = P.key[pc->buf] + po;
+    __syncthreads();
+    for (uint32_t i = tid; i < m; i += PL_THREADS) S.key[i] = key[i] | (l_alive(S.bits, i) ? 0u : PK_DEAD);
+    if (tid == 0) {
+        S.event = EV_NONE; S.m = m; S.head = 0; S.tail = 0; S.killed = 0; S.aidx = PK_NO; S.buf = pc->buf;
+        S.ext[0] = pc->a_slot; S.ext[1] = (uint32_t)pc->a_rating; S.ext[2] = pc->a_cons;
+        S.ext[3] = pc->a_key; S.ext[4] = pc->a_team;
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < PL_MAX; i += PL_THREADS) {
+        uint32_t t = LNX_NONE, gi = PL_S;
+        if (i < m) {
+            const uint32_t o = P.nx16[pc->buf][po + i];
+            t = o == NX_NONE ? LNX_NONE : (o == NX_INV || o == NX_FAR) ? LNX_INV : i + o;
+            if (t < LNX_INV) gi = lane_succ(S.bits, t + 1u, nwords);
+        }
+        S.nxg[i] = nxg_make(t, gi);
+    }
+    __syncthreads();
+}
+
+// ---- blind chase: x -> g[x], PL_SPEC times from the anchor, every word met into S.path ----
+static __device__ __forceinline__ void late_blind_chase(LateLds& S, uint32_t a_idx, int lane)
+{
+    uint32_t x4 = a_idx << 2;
+    for (uint32_t k0 = 0; k0 < PL_SPEC; k0 += 8u) {
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            const uint32_t r = lds_ld((const uint32_t*)((const char*)S.nxg + x4));
+            S.path[k0 + k] = r;
+            x4 = r >> 16;
+        }
+        if (uni(x4) == (PL_S << 2)) {          // parked: the rest of the block is the sentinel
+            for (uint32_t k = k0 + 8u + (uint32_t)lane; k < PL_SPEC; k += 64u) S.path[k] = nxg_make(LNX_NONE, PL_S);
+            break;
+        }
+    }
+}
+
+// ---- check the 64 steps at once; the confirmed prefix goes to the consumer.  Confirmed steps. ----
+static __device__ __forceinline__ uint32_t late_blind_check(LateLds& S, LateCursor& C, LateRing& R, uint32_t pass, int lane)
+{
+    const uint32_t r = S.path[lane];
+    const uint32_t rp = lane ? S.path[lane - 1] : 0u;
+    const uint32_t ia = lane ? (rp >> 18) : C.a_idx;      // anchor of step `lane`
+    const uint32_t it = r & 0xFFFFu, ig = r >> 18;
+    bool ok = ia != PL_S && it < LNX_INV && ig != PL_S;
+    if (ok) ok = l_alive(S.bits, it) && l_alive(S.bits, ig);
+    const unsigned long long good = __ballot(ok);
+    const uint32_t ns = good == ~0ull ? 64u : (uint32_t)__ffsll(~good) - 1u;
+    if (ns) {
+        R.push_block(ns, ia, it, pass);
+        // every step: partner leaves the queue, the next player opens a lobby
+        C.qlen -= 2u * ns; C.pairs -= ns; C.n_out += ns; C.changed = 1;
+        C.a_idx = lane_get(ig, (int)ns - 1);
+        C.a_pushed = 0;
+    }
+    return ns;
+}
+
+// ---- one careful step for the anchor C.a_idx; t: its partner when the caller knows it, or PK_NO.
+// false: the pass ends here (nobody fits the anchor until the end, or the pass ran off the queue) ----
+static __device__ __forceinline__ bool late_careful_step(LateLds& S, LateCursor& C, LateRing& R, LateDiag& D, uint32_t t, uint32_t m, uint32_t w,
+                                                         uint32_t pass, int lane)
+{
+    const uint32_t a_key = late_anchor_key(S, C.a_idx);
+    if (t == PK_NO) {
+        const uint32_t cnx = uni(lds_ld(S.nxg + C.a_idx)) & 0xFFFFu;
+        if (cnx == LNX_NONE) return false;                  // nobody fits until the end
+        if (cnx < LNX_INV && l_alive(S.bits, cnx)) t = cnx;
+        else {
+            if (cnx == LNX_INV) ++D.inv; else ++D.stale;
+            const uint32_t from = cnx == LNX_INV ? C.a_idx + 1u : cnx + 1u;
+            t = uni(l_scan_fit(S.key, a_key, from, m, w, lane));
+            D.tst += (t == PK_NO ? m : t) - from;
+            if (t == PK_NO) return false;
+        }
+    }
+    // is_filled (search/worker.ex:313-319): hand the step to the consumer
+    R.push(C.a_idx, t, pass);
+    --C.qlen; C.changed = 1; C.has_anchor = 0; C.pos = t + 1u; ++C.n_out;
+    ++D.slowsucc;
+    const uint32_t a2 = uni(l_succ(S.bits, t + 1u, m, lane));
+    if (a2 == PK_NO) return false;                          // pass ran off the queue
+    C.open_lobby(a2);
+    return true;
+}
+
+// ---- wave 0: the cursor walk (MATCH_CHECK.md §3, §4), until the queue is quiescent or wants a compaction ----
+static __device__ __forceinline__ void late_chase(LateLds& S, LateCursor& C, LateRing& R, LateDiag& D, uint32_t m, uint32_t w, uint32_t pass0,
+                                                  int lane)
+{
+    __builtin_amdgcn_s_setprio(3);
+    uint32_t ev = EV_NONE;
+    const long long tc0 = clock64(), tw0 = wall_clock64();
+    for (;;) {
+        if (!C.in_pass) {
+            R.drain();                              // a new pass reads the bitmap from the head
+            if (C.qlen == 0u) { ev = EV_DONE; break; }                 // while (len > 0)
+            if (m > PL_COMPACT_MIN && C.qlen * 2u < m) { ev = EV_COMPACT; break; }
+            C.in_pass = 1; C.pos = 0; C.changed = 0;
+            C.scanned += C.qlen;
+            C.pairs += C.qlen;
+        }
+        uint32_t t = PK_NO;
+        if (!C.has_anchor) {
+            const uint32_t a = uni(l_succ(S.bits, C.pos, m, lane));
+            if (a == PK_NO) {                                       // pass ran off the queue
+                if (C.end_pass()) continue;
+                ev = EV_DONE; break;
+            }
+            C.open_lobby(a);
+        } else {
+            // anchor carried into this pass: first fit from the head of the queue
+            const long long ts = clock64();
+            t = uni(l_scan_fit(S.key, late_anchor_key(S, C.a_idx), C.pos, m, w, lane));
+            D.tst += (t == PK_NO ? m : t) - C.pos;
+            D.wrapc += (uint32_t)(clock64() - ts);
+            if (t == PK_NO) {                                       // nobody fits: pass without change?
+                if (C.end_pass()) continue;
+                ev = EV_DONE; break;
+            }
+        }
+        // Inside one pass.  Nothing here writes the bitmap: the consumer wave does,
+        // and the cursor never looks back.
+        const uint32_t pass = C.passes - pass0;
+        for (;;) {
+            // (round 5: a look at the anchor's own word first — every pass ENDS on an anchor without a partner, and the blind
+            // chase used to find that out with a block of eight dependent reads and a 64-lane check that confirmed nothing,
+            // ~1.4k cycles where one read says it; likewise after every careful step that lands on such an anchor)
+            bool blind = t == PK_NO && C.a_idx != PL_EXT;
+            if (blind) {
+                const uint32_t r0 = uni(lds_ld(S.nxg + C.a_idx));
+                blind = (r0 & 0xFFFFu) < LNX_INV && (r0 >> 18) != PL_S;
+            }
+            if (blind) {
+                late_blind_chase(S, C.a_idx, lane);
+                if (late_blind_check(S, C, R, pass, lane) == PL_SPEC) continue;
+            }
+            if (!late_careful_step(S, C, R, D, t, m, w, pass, lane)) break;
+            t = PK_NO;
+        }
+        if (C.has_anchor && !C.a_pushed) { R.push(C.a_idx, PL_NOPART, pass); C.a_pushed = 1; }   // seated, stays
+        if (!C.end_pass()) { ev = EV_DONE; break; }
+    }
+    D.clk += (uint32_t)(clock64() - tc0);
+    D.wall += (uint32_t)(wall_clock64() - tw0);
+    if (lane == 0) { S.aidx = C.has_anchor ? C.a_idx : PK_NO; S.nout = C.n_out; lds_st(&S.event, ev); }
+    __builtin_amdgcn_s_setprio(0);
+}
+
+// ---- wave 1: consumer, first half: the steps' players leave the queue (LDS only) ----
+// Kept apart from the emission (wave 2) since round 3: the chaser opens every pass by waiting until all
+// pushed steps are in the bitmap, and with one consumer wave the kills of the last steps of a pass sat behind
+// the emission loads of the steps before them (two dependent loads from HBM: 0.48M of the 2.94M cycles of the
+// longest chain's walking wave were spent in that wait).
+static __device__ __forceinline__ void late_kill(LateLds& S, const LateRing& R, int lane)
+{
+    uint32_t ktail = uni(lds_ld(&S.killed));
+    for (;;) {
+        uint32_t head = uni(lds_ld(&S.head));
+        if (head == ktail) {
+            if (lds_ld(&S.event) != EV_NONE) {
+                head = uni(lds_ld(&S.head));
+                if (head == ktail) break;
+            } else { __builtin_amdgcn_s_sleep(1); continue; }
+        }
+        const uint32_t nb = dev_min_u32(64u, head - ktail);
+        if ((uint32_t)lane < nb) {
+            const uint32_t e = R.step(ktail + (uint32_t)lane);
+            const uint32_t a = e & 0xFFFFu, t = e >> 16;
+            if (a != PL_EXT) { atomicAnd(&S.bits[a >> 5], ~(1u << (a & 31u))); atomicOr(&S.key[a], PK_DEAD); }
+            if (t != PL_NOPART) { atomicAnd(&S.bits[t >> 5], ~(1u << (t & 31u))); atomicOr(&S.key[t], PK_DEAD); }
+        }
+        wave_lockstep();
+        ktail += nb;
+        if (lane == 0) lds_st(&S.killed, ktail);            // the chaser only waits for this
+    }
+}
+
+// ---- wave 2: consumer, second half: the lobbies of the steps that are in the bitmap, 64 at a time ----
+static __device__ __forceinline__ void late_emit(const PairParams& P, LateLds& S, const LateRing& R, uint32_t& emit_idx, uint32_t g, size_t qo,
+                                                 size_t po, uint32_t pass0, int lane)
+{
+    uint32_t* const os = P.out_slots + (size_t)g * P.out_slot_stride;
+    float* const osc = P.out_score + (size_t)g * P.out_rec_stride;
+    uint32_t* const opass = P.out_pass + (size_t)g * P.out_rec_stride;
+    uint32_t tail = uni(lds_ld(&S.tail));
+    const uint32_t* const oidx = P.oidx[uni(lds_ld(&S.buf))] + po;
+    for (;;) {
+        const uint32_t killed = uni(lds_ld(&S.killed));
+        if (killed == tail) {
+            if (lds_ld(&S.event) != EV_NONE && uni(lds_ld(&S.head)) == tail && uni(lds_ld(&S.killed)) == tail) break;
+            __builtin_amdgcn_s_sleep(2);
+            continue;
+        }
+        const uint32_t nb = dev_min_u32(64u, killed - tail);
+        const bool mine = (uint32_t)lane < nb;
+        const uint32_t e = mine ? R.step(tail + (uint32_t)lane) : 0xFFFFFFFFu;
+        const uint32_t a = e & 0xFFFFu, t = e >> 16;
+        const bool is_match = mine && t != PL_NOPART;
+        const unsigned long long mm = __ballot(is_match);
+        if (is_match) {
+            const uint32_t k = emit_idx + (uint32_t)__popcll(mm & ((1ull << lane) - 1ull));
+            const uint32_t ka = a == PL_EXT ? S.ext[3] : S.key[a];
+            const uint32_t kt = S.key[t];
+            const uint32_t ra = pk_rating(ka), rt = pk_rating(kt);
+            const uint32_t team = a == PL_EXT ? S.ext[4] : 0u;
+            os[2u * k + team] = a == PL_EXT ? S.ext[0] : P.q_slot[qo + oidx[a]];
+            os[2u * k + (1u - team)] = P.q_slot[qo + oidx[t]];
+            osc[k] = (float)(int32_t)(ra > rt ? ra - rt : rt - ra);
+            opass[k] = pass0 + R.pass_of(tail + (uint32_t)lane);
+        }
+        emit_idx += (uint32_t)__popcll(mm);
+        tail += nb;
+        wave_lockstep();
+        if (lane == 0) lds_st(&S.tail, tail);               // the ring slots are free again
+    }
+}
+
+// ---- waves 3..15: repair nxg behind the cursor ----
+static __device__ __forceinline__ void late_repair(LateLds& S, LateDiag& D, uint32_t m, uint32_t w, uint32_t fix_waves, uint32_t fix_sleep,
+                                                   int wave, int lane)
+{
+    const uint32_t nwords = (m + 31u) >> 5;
+    const uint32_t fw = (uint32_t)wave - 3u;
+    const uint32_t nchunks = fw < fix_waves ? (m + 63u) >> 6 : 0u;
+    uint32_t chunk = fw;
+    uint32_t idle = 0;
+    // (Round 5, measured and taken out: the sweeps starting over at the head of the queue whenever the cursor begins a
+    // pass — "what the cursor meets was made stale by the pass before, so a sweep that stays ahead of it hands it fresh
+    // entries".  They never finish the chain's tail then: 254 stale hits a tick against 100, kp_late 1.60 against 1.20 ms.)
+    while (lds_ld(&S.event) == EV_NONE) {
+        if (chunk >= nchunks) {
+            chunk = fw;
+            if (idle) __builtin_amdgcn_s_sleep(32);
+            idle = 1;
+            if (chunk >= nchunks) { __builtin_amdgcn_s_sleep(64); continue; }
+        }
+        if (fix_sleep & 1u) __builtin_amdgcn_s_sleep(1);
+        if (fix_sleep & 2u) __builtin_amdgcn_s_sleep(2);
+        if (fix_sleep & 4u) __builtin_amdgcn_s_sleep(4);
+        if (fix_sleep & 8u) __builtin_amdgcn_s_sleep(8);
+        if (fix_sleep & 16u) __builtin_amdgcn_s_sleep(16);
+        if (fix_sleep & 32u) __builtin_amdgcn_s_sleep(32);
+        const uint32_t i = (chunk << 6) + (uint32_t)lane;
+        bool need = false, need_g = false;
+        uint32_t from = 0, t = LNX_NONE;
+        if (i < m && l_alive(S.bits, i)) {
+            const uint32_t r = lds_ld(S.nxg + i);
+            t = r & 0xFFFFu;
+            const uint32_t gi = r >> 18;
+            if (t == LNX_INV) { need = true; from = i + 1u; }
+            else if (t != LNX_NONE) {
+                // (both probes in one trip to LDS)
+                const uint32_t at = l_alive(S.bits, t), ag = l_alive(S.bits, gi == PL_S ? t : gi);
+                if (!at) { need = true; from = t + 1u; }
+                else if (gi == PL_S || !ag) need_g = true;
+            }
+        }
+        unsigned long long todo = __ballot(need);
+        while (todo) {
+            const int l = __ffsll(todo) - 1;
+            todo &= todo - 1ull;
+            const uint32_t ai = (uint32_t)__shfl((int)i, l), af = (uint32_t)__shfl((int)from, l);
+            const uint32_t j = l_scan_fit_ev(S.key, S.key[ai] & ~PK_DEAD, af, m, w, lane, &S.event);
+            if (j == PK_ABORT) { todo = 0; need = false; need_g = false; break; }
+            D.tst += (j == PK_NO ? m : j) - af;
+            if (lane == l) { t = j == PK_NO ? LNX_NONE : j; need_g = true; }
+            idle = 0;
+            ++D.fixed;
+        }
+        if (need_g) {                       // one 32-bit store: next[] and g[] stay a consistent pair
+            const uint32_t gi = t < LNX_INV ? lane_succ(S.bits, t + 1u, nwords) : PL_S;
+            lds_st(S.nxg + i, nxg_make(t, gi));
+        }
+        chunk += fix_waves;
+    }
+}
+
+// ---- an anchor that is still an index leaves the index space by value (the walk is over, or a compaction renumbers) ----
+static __device__ __forceinline__ void late_anchor_by_value(const PairParams& P, LateLds& S, LateCursor& C, size_t qo, size_t po, int tid)
+{
+    if (tid == 0 && S.aidx != PK_NO && S.aidx != PL_EXT) {
+        const uint32_t oi = P.oidx[S.buf][po + S.aidx];
+        S.ext[0] = P.q_slot[qo + oi];
+        S.ext[1] = (uint32_t)P.q_rating[qo + oi];
+        S.ext[2] = P.q_cons[qo + oi];
+        S.ext[3] = S.key[S.aidx] & ~PK_DEAD;
+        S.ext[4] = 0;
+    }
+    __syncthreads();
+    if (S.aidx != PK_NO) { C.a_idx = PL_EXT; C.a_pushed = 1; }
+}
+
+// compaction: the new index of the queued player i = queued players before it
+static __device__ __forceinline__ uint32_t late_rank(const LateLds& S, uint32_t i)
+{
+    return S.wpre[i >> 5] + (uint32_t)__popc(S.bits[i >> 5] & ((1u << (i & 31u)) - 1u));
+}
+
+// ---- compaction: drop everybody who left the queue.  The new index-space length. ----
+static __device__ __forceinline__ uint32_t late_compact(const PairParams& P, LateLds& S, uint32_t m, size_t po, int tid, int lane, int wave)
+{
+    const uint32_t nwords = (m + 31u) >> 5;
+    const uint32_t cur = S.buf;
+    // exclusive prefix of the per-word populations
+    const uint32_t pcw = (uint32_t)tid < nwords ? (uint32_t)__popc(S.bits[tid]) : 0u;
+    const uint32_t incl = wave_incl_scan(pcw, lane);
+    if (lane == 63) S.wtot[wave] = incl;
+    __syncthreads();
+    if ((uint32_t)tid < PL_WORDS) {
+        uint32_t off = 0;
+        for (int x = 0; x < wave; ++x) off += S.wtot[x];
+        S.wpre[tid] = (uint16_t)(off + incl - pcw);
+    }
+    __syncthreads();
+    const uint32_t* const oidx = P.oidx[cur] + po;
+    uint32_t* const oidx_new = P.oidx[cur ^ 1u] + po;
+    // chunks in ascending order: a chunk's survivors land at or below their source
+    for (uint32_t base = 0; base < m; base += PL_THREADS) {
+        const uint32_t i = base + (uint32_t)tid;
+        uint32_t r = PK_NO, nk = 0, nv = 0, no = 0;
+        if (i < m && l_alive(S.bits, i)) {
+            r = late_rank(S, i);
+            nk = S.key[i];
+            const uint32_t v = S.nxg[i];
+            uint32_t t = v & 0xFFFFu, gi = v >> 18;
+            if (t < LNX_INV) {
+                if (l_alive(S.bits, t)) {
+                    t = late_rank(S, t);
+                    if (gi != PL_S && l_alive(S.bits, gi)) gi = late_rank(S, gi);
+                    else gi = PL_S;
+                } else { t = LNX_INV; gi = PL_S; }
+            } else gi = PL_S;
+            nv = nxg_make(t, gi);
+            no = oidx[i];
+        }
+        __syncthreads();
+        if (r != PK_NO) { S.key[r] = nk; S.nxg[r] = nv; oidx_new[r] = no; }
+        __syncthreads();
+    }
+    const uint32_t nm = (uint32_t)S.wpre[nwords - 1u] + (uint32_t)__popc(S.bits[nwords - 1u]);
+    __syncthreads();
+    for (uint32_t i = tid; i < PL_WORDS; i += PL_THREADS) {
+        const uint32_t lo = i << 5;
+        S.bits[i] = lo + 32u <= nm ? 0xFFFFFFFFu : (lo < nm ? (1u << (nm - lo)) - 1u : 0u);
+    }
+    for (uint32_t i = nm + (uint32_t)tid; i < m; i += PL_THREADS) S.nxg[i] = nxg_make(LNX_NONE, PL_S);
+    if (tid == 0) { S.m = nm; S.buf = cur ^ 1u; S.event = EV_NONE; S.aidx = PK_NO; }
+    __syncthreads();
+    return S.m;
+}
+
+// ---- store the chain back ----
+static __device__ __forceinline__ void late_store(const PairParams& P, PairChain* pc, const LateLds& S, const LateCursor& C, const LateDiag& D,
+                                                  uint32_t emit_idx, uint32_t m, uint32_t g, int tid, int lane)
+{
+    const uint32_t nwords = (m + 31u) >> 5;
+    for (uint32_t i = tid; i < nwords; i += PL_THREADS) P.bits[S.buf][(size_t)g * P.bits_stride + i] = S.bits[i];
+    if (tid == 0) {
+        pc->stage = PS_DONE;
+        pc->m = m;
+        pc->buf = S.buf;
+        late_cursor_commit(pc, C);
+        if (C.has_anchor) {
+            pc->a_key = S.ext[3];
+            pc->a_slot = S.ext[0];
+            pc->a_cons = S.ext[2];
+            pc->a_team = S.ext[4];
+            pc->a_rating = (int32_t)S.ext[1];
+        }
+        pc->dbg[PD_STALE] = D.stale;
+        pc->dbg[PD_INV] = D.inv;
+        pc->dbg[PD_SLOWSUCC] = D.slowsucc;
+        pc->dbg[PD_COMPACT] = D.compact;
+        pc->dbg[PD_CLK] = D.clk;
+        pc->dbg[PD_WALL] = D.wall;
+        pc->dbg[PD_WRAPC] = D.wrapc;
+    }
+    if (tid == 128 && emit_idx != S.nout) atomicOr(&pc->err, MM_ERRF_SEAT_INVARIANT);
+    if (tid == 192) pc->dbg[PD_FIXED] = D.fixed;     // repairs done by wave 3
+    if ((P.tune & 0x2000u) && lane == 0 && D.tst) atomicAdd(&pc->tested, D.tst);
+}
+
 __global__ __launch_bounds__(PL_THREADS) void kp_late(PairParams P)
 {
-    __shared__ uint32_t s_path[PL_SPEC];       // first in LDS: the chase addresses it with immediates
-    __shared__ uint32_t s_nxg[PL_MAX];
-    __shared__ uint32_t s_key[PL_MAX];
-    __shared__ uint32_t s_bits[PL_WORDS + 64]; // zero padded: 64 words can be read past the end
-    __shared__ uint16_t s_wpre[PL_WORDS];      // compaction: queued players before the word
-    __shared__ uint32_t s_ring[PL_RING];       // anchor | partner << 16
-    __shared__ uint16_t s_ringp[PL_RING];      // pass of the step, relative to the kernel's first
-    __shared__ uint32_t s_wtot[16];
-    __shared__ uint32_t s_event, s_m, s_head, s_tail, s_killed, s_aidx, s_buf, s_nout;
-    __shared__ uint32_t s_ext[5];              // anchor by value: slot, rating, cons, key, team
+    __shared__ LateLds S;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t g = blockIdx.x;
@@ -629,424 +1122,31 @@ __global__ __launch_bounds__(PL_THREADS) void kp_late(PairParams P)
     const uint32_t c = P.mode * P.n_groups + g;
     const size_t qo = (size_t)c * P.capacity, po = (size_t)g * P.pstride;
     const uint32_t w = P.window;
-    uint32_t* const os = P.out_slots + (size_t)g * P.out_slot_stride;
-    float* const osc = P.out_score + (size_t)g * P.out_rec_stride;
-    uint32_t* const opass = P.out_pass + (size_t)g * P.out_rec_stride;
-    uint32_t* const vbits = s_bits;
-    uint32_t* const vev = &s_event;
 
-    // ---- load the chain ----
     uint32_t m = pc->m;
     const uint32_t pass0 = pc->passes;
-    {
-        const uint32_t nwords = (m + 31u) >> 5;
-        for (uint32_t i = tid; i < PL_WORDS + 64u; i += PL_THREADS)
-            s_bits[i] = i < nwords ? P.bits[pc->buf][(size_t)g * P.bits_stride + i] : 0u;
-        const uint32_t* const key = P.key[pc->buf] + po;
-        __syncthreads();
-        for (uint32_t i = tid; i < m; i += PL_THREADS) s_key[i] = key[i] | (l_alive(s_bits, i) ? 0u : PK_DEAD);
-        if (tid == 0) {
-            s_event = EV_NONE; s_m = m; s_head = 0; s_tail = 0; s_killed = 0; s_aidx = PK_NO; s_buf = pc->buf;
-            s_ext[0] = pc->a_slot; s_ext[1] = (uint32_t)pc->a_rating; s_ext[2] = pc->a_cons;
-            s_ext[3] = pc->a_key; s_ext[4] = pc->a_team;
-        }
-        __syncthreads();
-        for (uint32_t i = tid; i < PL_MAX; i += PL_THREADS) {
-            uint32_t t = LNX_NONE, gi = PL_S;
-            if (i < m) {
-                const uint32_t o = P.nx16[pc->buf][po + i];
-                t = o == NX_NONE ? LNX_NONE : (o == NX_INV || o == NX_FAR) ? LNX_INV : i + o;
-                if (t < LNX_INV) gi = lane_succ(s_bits, t + 1u, nwords);
-            }
-            s_nxg[i] = nxg_make(t, gi);
-        }
-    }
-    __syncthreads();
+    late_load(P, pc, S, m, g, po, tid);
 
-    // chaser state (wave 0; uniform across its lanes).  a_idx: index of the anchor, or PL_EXT
-    // when it is held by value (carried in from an earlier tick / over a compaction).
-    uint32_t has_anchor = pc->has_anchor, a_idx = PL_EXT, a_pushed = 1;
-    uint32_t qlen = pc->qlen, pos = pc->pos0, passes = pc->passes, in_pass = pc->pos0 ? 1u : 0u, changed = pc->changed0;
-    uint32_t n_out = pc->n_out;
-    unsigned long long pairs = pc->pairs, scanned = pc->scanned;
-    if (pc->pos0) { scanned += qlen + pc->extra0; pairs += qlen + pc->extra0; }    // the pass is already under way
-    uint32_t rk = 0, rtail = 0;                                   // ring: pushed, consumer's tail as last seen
+    LateCursor C = late_cursor_open(pc);                          // wave 0
+    LateRing R(S, lane);
     uint32_t emit_idx = pc->n_out;                                // consumer (wave 2)
-    uint32_t d_stale = 0, d_inv = 0, d_slowsucc = 0, d_compact = 0, d_fixed = 0, d_clk = 0, d_wall = 0, d_wrapc = 0;
-    unsigned long long d_tst = 0;                                 // candidates this wave's scans were tested against
+    LateDiag D;
     const uint32_t fix_waves = 13u - dev_min_u32(P.tune & 15u, 13u);   // repair waves actually working (waves 3..15)
     const uint32_t fix_sleep = (P.tune >> 4) & 0xFFu;
 
-#define RING_ROOM(N)                                                                        \
-    do {                                                                                    \
-        if (rk - rtail + (N) > PL_RING) {                                                   \
-            rtail = uni(lds_ld(&s_tail));                                                   \
-            while (rk - rtail + (N) > PL_RING) { __builtin_amdgcn_s_sleep(2); rtail = uni(lds_ld(&s_tail)); } \
-        }                                                                                   \
-    } while (0)
-// one step of the walk handed to the consumer: it drops both players from the queue bitmap
-// and, when there is a partner, emits the lobby
-#define RING_PUSH(A, T)                                                                     \
-    do {                                                                                    \
-        RING_ROOM(1u);                                                                      \
-        if (lane == 0) {                                                                    \
-            s_ring[rk % PL_RING] = (A) | ((T) << 16);                                       \
-            s_ringp[rk % PL_RING] = (uint16_t)(passes - pass0);                             \
-        }                                                                                   \
-        ++rk;                                                                               \
-        if (lane == 0) lds_st(&s_head, rk);                                                 \
-    } while (0)
-#define RING_DRAIN()   /* until every pushed step is in the bitmap (emission may still be under way) */ \
-    do {                                                                                    \
-        uint32_t kd = uni(lds_ld(&s_killed));                                               \
-        while (kd != rk) { __builtin_amdgcn_s_sleep(1); kd = uni(lds_ld(&s_killed)); }      \
-    } while (0)
-
     for (;;) {
-        if (wave == 0) {
-            // ---------------- the cursor walk (MATCH_CHECK.md §3, §4) ----------------
-            __builtin_amdgcn_s_setprio(3);
-            uint32_t ev = EV_NONE;
-            const long long tc0 = clock64(), tw0 = wall_clock64();
-            for (;;) {
-                if (!in_pass) {
-                    RING_DRAIN();                           // a new pass reads the bitmap from the head
-                    if (qlen == 0u) { ev = EV_DONE; break; }                 // while (len > 0)
-                    if (m > PL_COMPACT_MIN && qlen * 2u < m) { ev = EV_COMPACT; break; }
-                    in_pass = 1; pos = 0; changed = 0;
-                    scanned += qlen;
-                    pairs += qlen;
-                }
-                uint32_t t = PK_NO;
-                if (!has_anchor) {
-                    const uint32_t a = uni(l_succ(vbits, pos, m, lane));
-                    if (a == PK_NO) {                                       // pass ran off the queue
-                        ++passes; in_pass = 0;
-                        if (!changed) { ev = EV_DONE; break; }
-                        continue;
-                    }
-                    // empty lobby: the popped player opens it (no pair evaluation)
-                    --qlen; --pairs; changed = 1; has_anchor = 1; a_idx = a; a_pushed = 0;
-                    pos = a + 1u;
-                } else {
-                    // anchor carried into this pass: first fit from the head of the queue
-                    const long long ts = clock64();
-                    const uint32_t a_key = a_idx == PL_EXT ? s_ext[3] : (s_key[a_idx] & ~PK_DEAD);
-                    t = uni(l_scan_fit(s_key, a_key, pos, m, w, lane, nullptr));
-                    d_tst += (t == PK_NO ? m : t) - pos;
-                    d_wrapc += (uint32_t)(clock64() - ts);
-                    if (t == PK_NO) {                                       // nobody fits: pass without change?
-                        ++passes; in_pass = 0;
-                        if (!changed) { ev = EV_DONE; break; }
-                        continue;
-                    }
-                }
-                // Inside one pass.  Nothing here writes the bitmap: the consumer wave does,
-                // and the cursor never looks back.
-                for (;;) {
-                    // (round 5: a look at the anchor's own word first — every pass ENDS on an anchor without a partner, and the blind
-                    // chase used to find that out with a block of eight dependent reads and a 64-lane check that confirmed nothing,
-                    // ~1.4k cycles where one read says it; likewise after every careful step that lands on such an anchor)
-                    bool blind = t == PK_NO && a_idx != PL_EXT;
-                    if (blind) {
-                        const uint32_t r0 = uni(lds_ld(s_nxg + a_idx));
-                        blind = (r0 & 0xFFFFu) < LNX_INV && (r0 >> 18) != PL_S;
-                    }
-                    if (blind) {
-                        // ---- blind chase: x -> g[x], PL_SPEC times ----
-                        uint32_t x4 = a_idx << 2;
-                        for (uint32_t k0 = 0; k0 < PL_SPEC; k0 += 8u) {
-#pragma unroll
-                            for (uint32_t k = 0; k < 8u; ++k) {
-                                const uint32_t r = lds_ld((const uint32_t*)((const char*)s_nxg + x4));
-                                s_path[k0 + k] = r;
-                                x4 = r >> 16;
-                            }
-                            if (uni(x4) == (PL_S << 2)) {          // parked: the rest of the block is the sentinel
-                                for (uint32_t k = k0 + 8u + (uint32_t)lane; k < PL_SPEC; k += 64u) s_path[k] = nxg_make(LNX_NONE, PL_S);
-                                break;
-                            }
-                        }
-                        // ---- check the 64 steps at once ----
-                        const uint32_t r = s_path[lane];
-                        const uint32_t rp = lane ? s_path[lane - 1] : 0u;
-                        const uint32_t ia = lane ? (rp >> 18) : a_idx;      // anchor of step `lane`
-                        const uint32_t it = r & 0xFFFFu, ig = r >> 18;
-                        bool ok = ia != PL_S && it < LNX_INV && ig != PL_S;
-                        if (ok) ok = l_alive(vbits, it) && l_alive(vbits, ig);
-                        const unsigned long long good = __ballot(ok);
-                        const uint32_t ns = good == ~0ull ? 64u : (uint32_t)__ffsll(~good) - 1u;   // confirmed steps
-                        if (ns) {
-                            RING_ROOM(ns);
-                            if ((uint32_t)lane < ns) {
-                                s_ring[(rk + (uint32_t)lane) % PL_RING] = ia | (it << 16);
-                                s_ringp[(rk + (uint32_t)lane) % PL_RING] = (uint16_t)(passes - pass0);
-                            }
-                            rk += ns;
-                            if (lane == 0) lds_st(&s_head, rk);
-                            // every step: partner leaves the queue, the next player opens a lobby
-                            qlen -= 2u * ns; pairs -= ns; n_out += ns; changed = 1;
-                            a_idx = lane_get(ig, (int)ns - 1);
-                            a_pushed = 0;
-                        }
-                        if (ns == PL_SPEC) continue;
-                    }
-                    // ---- one careful step for the anchor a_idx ----
-                    const uint32_t a_key = a_idx == PL_EXT ? s_ext[3] : (s_key[a_idx] & ~PK_DEAD);
-                    if (t == PK_NO) {
-                        const uint32_t cnx = uni(lds_ld(s_nxg + a_idx)) & 0xFFFFu;
-                        if (cnx == LNX_NONE) break;                         // nobody fits until the end
-                        if (cnx < LNX_INV && l_alive(vbits, cnx)) t = cnx;
-                        else {
-                            if (cnx == LNX_INV) ++d_inv; else ++d_stale;
-                            t = uni(l_scan_fit(s_key, a_key, cnx == LNX_INV ? a_idx + 1u : cnx + 1u, m, w, lane, nullptr));
-                            d_tst += (t == PK_NO ? m : t) - (cnx == LNX_INV ? a_idx + 1u : cnx + 1u);
-                            if (t == PK_NO) break;
-                        }
-                    }
-                    // is_filled (search/worker.ex:313-319): hand the step to the consumer
-                    RING_PUSH(a_idx, t);
-                    --qlen; changed = 1; has_anchor = 0; pos = t + 1u; ++n_out;
-                    ++d_slowsucc;
-                    const uint32_t a2 = uni(l_succ(vbits, t + 1u, m, lane));
-                    if (a2 == PK_NO) break;                                 // pass ran off the queue
-                    --qlen; --pairs; has_anchor = 1; a_idx = a2; a_pushed = 0;
-                    pos = a2 + 1u;
-                    t = PK_NO;
-                }
-                if (has_anchor && !a_pushed) { RING_PUSH(a_idx, PL_NOPART); a_pushed = 1; }   // seated, stays
-                ++passes; in_pass = 0;                                      // end of the pass
-                if (!changed) { ev = EV_DONE; break; }
-            }
-            d_clk += (uint32_t)(clock64() - tc0);
-            d_wall += (uint32_t)(wall_clock64() - tw0);
-            if (lane == 0) { s_aidx = has_anchor ? a_idx : PK_NO; s_nout = n_out; lds_st(vev, ev); }
-            __builtin_amdgcn_s_setprio(0);
-        } else if (wave == 1) {
-            // ---------------- consumer, first half: the steps' players leave the queue (LDS only) ----------------
-            // Kept apart from the emission (wave 2) since round 3: the chaser opens every pass by waiting until all
-            // pushed steps are in the bitmap, and with one consumer wave the kills of the last steps of a pass sat behind
-            // the emission loads of the steps before them (two dependent loads from HBM: 0.48M of the 2.94M cycles of the
-            // longest chain's walking wave were spent in that wait).
-            uint32_t ktail = uni(lds_ld(&s_killed));
-            for (;;) {
-                uint32_t head = uni(lds_ld(&s_head));
-                if (head == ktail) {
-                    if (lds_ld(vev) != EV_NONE) {
-                        head = uni(lds_ld(&s_head));
-                        if (head == ktail) break;
-                    } else { __builtin_amdgcn_s_sleep(1); continue; }
-                }
-                const uint32_t nb = dev_min_u32(64u, head - ktail);
-                if ((uint32_t)lane < nb) {
-                    const uint32_t e = s_ring[(ktail + (uint32_t)lane) % PL_RING];
-                    const uint32_t a = e & 0xFFFFu, t = e >> 16;
-                    if (a != PL_EXT) { atomicAnd(&s_bits[a >> 5], ~(1u << (a & 31u))); atomicOr(&s_key[a], PK_DEAD); }
-                    if (t != PL_NOPART) { atomicAnd(&s_bits[t >> 5], ~(1u << (t & 31u))); atomicOr(&s_key[t], PK_DEAD); }
-                }
-                wave_lockstep();
-                ktail += nb;
-                if (lane == 0) lds_st(&s_killed, ktail);            // the chaser only waits for this
-            }
-        } else if (wave == 2) {
-            // ---------------- consumer, second half: the lobbies of the steps that are in the bitmap, 64 at a time ----------------
-            uint32_t tail = uni(lds_ld(&s_tail));
-            const uint32_t* const oidx = P.oidx[uni(lds_ld(&s_buf))] + po;
-            for (;;) {
-                const uint32_t killed = uni(lds_ld(&s_killed));
-                if (killed == tail) {
-                    if (lds_ld(vev) != EV_NONE && uni(lds_ld(&s_head)) == tail && uni(lds_ld(&s_killed)) == tail) break;
-                    __builtin_amdgcn_s_sleep(2);
-                    continue;
-                }
-                const uint32_t nb = dev_min_u32(64u, killed - tail);
-                const bool mine = (uint32_t)lane < nb;
-                const uint32_t slotr = (tail + (uint32_t)lane) % PL_RING;
-                const uint32_t e = mine ? s_ring[slotr] : 0xFFFFFFFFu;
-                const uint32_t a = e & 0xFFFFu, t = e >> 16;
-                const bool is_match = mine && t != PL_NOPART;
-                const unsigned long long mm = __ballot(is_match);
-                if (is_match) {
-                    const uint32_t k = emit_idx + (uint32_t)__popcll(mm & ((1ull << lane) - 1ull));
-                    const uint32_t ka = a == PL_EXT ? s_ext[3] : s_key[a];
-                    const uint32_t kt = s_key[t];
-                    const uint32_t ra = pk_rating(ka), rt = pk_rating(kt);
-                    const uint32_t team = a == PL_EXT ? s_ext[4] : 0u;
-                    os[2u * k + team] = a == PL_EXT ? s_ext[0] : P.q_slot[qo + oidx[a]];
-                    os[2u * k + (1u - team)] = P.q_slot[qo + oidx[t]];
-                    osc[k] = (float)(int32_t)(ra > rt ? ra - rt : rt - ra);
-                    opass[k] = pass0 + s_ringp[slotr];
-                }
-                emit_idx += (uint32_t)__popcll(mm);
-                tail += nb;
-                wave_lockstep();
-                if (lane == 0) lds_st(&s_tail, tail);               // the ring slots are free again
-            }
-        } else {
-            // ---------------- repair nxg behind the cursor ----------------
-            const uint32_t nwords = (m + 31u) >> 5;
-            const uint32_t fw = (uint32_t)wave - 3u;
-            const uint32_t nchunks = fw < fix_waves ? (m + 63u) >> 6 : 0u;
-            uint32_t chunk = fw;
-            uint32_t idle = 0;
-            // (Round 5, measured and taken out: the sweeps starting over at the head of the queue whenever the cursor begins a
-            // pass — "what the cursor meets was made stale by the pass before, so a sweep that stays ahead of it hands it fresh
-            // entries".  They never finish the chain's tail then: 254 stale hits a tick against 100, kp_late 1.60 against 1.20 ms.)
-            while (lds_ld(vev) == EV_NONE) {
-                if (chunk >= nchunks) {
-                    chunk = fw;
-                    if (idle) __builtin_amdgcn_s_sleep(32);
-                    idle = 1;
-                    if (chunk >= nchunks) { __builtin_amdgcn_s_sleep(64); continue; }
-                }
-                if (fix_sleep & 1u) __builtin_amdgcn_s_sleep(1);
-                if (fix_sleep & 2u) __builtin_amdgcn_s_sleep(2);
-                if (fix_sleep & 4u) __builtin_amdgcn_s_sleep(4);
-                if (fix_sleep & 8u) __builtin_amdgcn_s_sleep(8);
-                if (fix_sleep & 16u) __builtin_amdgcn_s_sleep(16);
-                if (fix_sleep & 32u) __builtin_amdgcn_s_sleep(32);
-                const uint32_t i = (chunk << 6) + (uint32_t)lane;
-                bool need = false, need_g = false;
-                uint32_t from = 0, t = LNX_NONE;
-                if (i < m && l_alive(vbits, i)) {
-                    const uint32_t r = lds_ld(s_nxg + i);
-                    t = r & 0xFFFFu;
-                    const uint32_t gi = r >> 18;
-                    if (t == LNX_INV) { need = true; from = i + 1u; }
-                    else if (t != LNX_NONE) {
-                        // (both probes in one trip to LDS)
-                        const uint32_t at = l_alive(vbits, t), ag = l_alive(vbits, gi == PL_S ? t : gi);
-                        if (!at) { need = true; from = t + 1u; }
-                        else if (gi == PL_S || !ag) need_g = true;
-                    }
-                }
-                unsigned long long todo = __ballot(need);
-                while (todo) {
-                    const int l = __ffsll(todo) - 1;
-                    todo &= todo - 1ull;
-                    const uint32_t ai = (uint32_t)__shfl((int)i, l), af = (uint32_t)__shfl((int)from, l);
-                    const uint32_t j = l_scan_fit(s_key, s_key[ai] & ~PK_DEAD, af, m, w, lane, vev);
-                    if (j == PK_ABORT) { todo = 0; need = false; need_g = false; break; }
-                    d_tst += (j == PK_NO ? m : j) - af;
-                    if (lane == l) { t = j == PK_NO ? LNX_NONE : j; need_g = true; }
-                    idle = 0;
-                    ++d_fixed;
-                }
-                if (need_g) {                       // one 32-bit store: next[] and g[] stay a consistent pair
-                    const uint32_t gi = t < LNX_INV ? lane_succ(vbits, t + 1u, nwords) : PL_S;
-                    lds_st(s_nxg + i, nxg_make(t, gi));
-                }
-                chunk += fix_waves;
-            }
-        }
+        if (wave == 0) late_chase(S, C, R, D, m, w, pass0, lane);
+        else if (wave == 1) late_kill(S, R, lane);
+        else if (wave == 2) late_emit(P, S, R, emit_idx, g, qo, po, pass0, lane);
+        else late_repair(S, D, m, w, fix_waves, fix_sleep, wave, lane);
         __syncthreads();
-        const uint32_t ev = s_event;
-        const uint32_t cur = s_buf;
-        const uint32_t* const oidx = P.oidx[cur] + po;
-        // an anchor that is still an index leaves the index space by value
-        if (tid == 0 && s_aidx != PK_NO && s_aidx != PL_EXT) {
-            const uint32_t oi = oidx[s_aidx];
-            s_ext[0] = P.q_slot[qo + oi];
-            s_ext[1] = (uint32_t)P.q_rating[qo + oi];
-            s_ext[2] = P.q_cons[qo + oi];
-            s_ext[3] = s_key[s_aidx] & ~PK_DEAD;
-            s_ext[4] = 0;
-        }
-        __syncthreads();
-        if (s_aidx != PK_NO) { a_idx = PL_EXT; a_pushed = 1; }
+        const uint32_t ev = S.event;
+        late_anchor_by_value(P, S, C, qo, po, tid);
         if (ev == EV_DONE) break;
-
-        // ---------------- compaction: drop everybody who left the queue ----------------
-        {
-            const uint32_t nwords = (m + 31u) >> 5;
-            // exclusive prefix of the per-word populations
-            const uint32_t pcw = (uint32_t)tid < nwords ? (uint32_t)__popc(s_bits[tid]) : 0u;
-            const uint32_t incl = wave_incl_scan(pcw, lane);
-            if (lane == 63) s_wtot[wave] = incl;
-            __syncthreads();
-            if ((uint32_t)tid < PL_WORDS) {
-                uint32_t off = 0;
-                for (int x = 0; x < wave; ++x) off += s_wtot[x];
-                s_wpre[tid] = (uint16_t)(off + incl - pcw);
-            }
-            __syncthreads();
-            uint32_t* const oidx_new = P.oidx[cur ^ 1u] + po;
-            // chunks in ascending order: a chunk's survivors land at or below their source
-            for (uint32_t base = 0; base < m; base += PL_THREADS) {
-                const uint32_t i = base + (uint32_t)tid;
-                uint32_t r = PK_NO, nk = 0, nv = 0, no = 0;
-                if (i < m && l_alive(s_bits, i)) {
-                    const uint32_t bw = s_bits[i >> 5];
-                    r = s_wpre[i >> 5] + (uint32_t)__popc(bw & ((1u << (i & 31u)) - 1u));
-                    nk = s_key[i];
-                    const uint32_t v = s_nxg[i];
-                    uint32_t t = v & 0xFFFFu, gi = v >> 18;
-                    if (t < LNX_INV) {
-                        if (l_alive(s_bits, t)) {
-                            t = s_wpre[t >> 5] + (uint32_t)__popc(s_bits[t >> 5] & ((1u << (t & 31u)) - 1u));
-                            if (gi != PL_S && l_alive(s_bits, gi))
-                                gi = s_wpre[gi >> 5] + (uint32_t)__popc(s_bits[gi >> 5] & ((1u << (gi & 31u)) - 1u));
-                            else gi = PL_S;
-                        } else { t = LNX_INV; gi = PL_S; }
-                    } else gi = PL_S;
-                    nv = nxg_make(t, gi);
-                    no = oidx[i];
-                }
-                __syncthreads();
-                if (r != PK_NO) { s_key[r] = nk; s_nxg[r] = nv; oidx_new[r] = no; }
-                __syncthreads();
-            }
-            const uint32_t nm = (uint32_t)s_wpre[nwords - 1u] + (uint32_t)__popc(s_bits[nwords - 1u]);
-            __syncthreads();
-            for (uint32_t i = tid; i < PL_WORDS; i += PL_THREADS) {
-                const uint32_t lo = i << 5;
-                s_bits[i] = lo + 32u <= nm ? 0xFFFFFFFFu : (lo < nm ? (1u << (nm - lo)) - 1u : 0u);
-            }
-            for (uint32_t i = nm + (uint32_t)tid; i < m; i += PL_THREADS) s_nxg[i] = nxg_make(LNX_NONE, PL_S);
-            if (tid == 0) { s_m = nm; s_buf = cur ^ 1u; s_event = EV_NONE; s_aidx = PK_NO; }
-            __syncthreads();
-            m = s_m;
-            ++d_compact;
-        }
+        m = late_compact(P, S, m, po, tid, lane, wave);
+        ++D.compact;
     }
-#undef RING_ROOM
-#undef RING_PUSH
-#undef RING_DRAIN
-
-    // ---- store the chain back ----
-    {
-        const uint32_t nwords = (m + 31u) >> 5;
-        for (uint32_t i = tid; i < nwords; i += PL_THREADS) P.bits[s_buf][(size_t)g * P.bits_stride + i] = s_bits[i];
-        if (tid == 0) {
-            pc->stage = PS_DONE;
-            pc->pos0 = 0; pc->changed0 = 0; pc->extra0 = 0;
-            pc->m = m;
-            pc->qlen = qlen;
-            pc->buf = s_buf;
-            pc->has_anchor = has_anchor;
-            if (has_anchor) {
-                pc->a_key = s_ext[3];
-                pc->a_slot = s_ext[0];
-                pc->a_cons = s_ext[2];
-                pc->a_team = s_ext[4];
-                pc->a_rating = (int32_t)s_ext[1];
-            }
-            pc->passes = passes;
-            pc->n_out = n_out;
-            pc->pairs = pairs;
-            pc->scanned = scanned;
-            pc->dbg[0] = d_stale;
-            pc->dbg[1] = d_inv;
-            pc->dbg[2] = d_slowsucc;
-            pc->dbg[3] = d_compact;
-            pc->dbg[5] = d_clk;
-            pc->dbg[6] = d_wall;
-            pc->dbg[7] = d_wrapc;
-        }
-        if (tid == 128 && emit_idx != s_nout) atomicOr(&pc->err, MM_ERRF_SEAT_INVARIANT);
-        if (tid == 192) pc->dbg[4] = d_fixed;     // repairs done by wave 3
-        if ((P.tune & 0x2000u) && lane == 0 && d_tst) atomicAdd(&pc->tested, d_tst);
-    }
+    late_store(P, pc, S, C, D, emit_idx, m, g, tid, lane);
 }
 
 // ------------------------------------------------------------------------------------

@@ -253,6 +253,21 @@ def blocked_head(n, then):
     return Case("blocked_head", {"n": n, "then": then}, PAIR, steps)
 
 
+def carried_head(n):
+    """One player alone, then n (even) more of his rating.
+    Tick 1: he opens the lobby and the queue is empty: one pass, no lobby, he is stored.
+    Tick 2: player 0 meets the stored lobby and fits (one pair, one lobby, nobody opened it in this pass); players
+        1 .. n-1 pair up in order, (n - 2) / 2 lobbies, and player n-1 opens a lobby and stays in it: one pass, n / 2
+        lobbies, n / 2 opened, the queue empty.
+    What it is for: the LDS-resident walk hands its steps to the consumer through a ring of 512 (mm_pair.inc PL_RING, the
+    same in every geometry).  The carried anchor's step is the ring's first, so the blocks of 64 steps that follow lie at
+    1 + 64 j: n / 2 > 512 makes one of them wrap around the ring's end and the producer wait for room."""
+    assert n % 2 == 0 and n >= 2
+    steps = [("enqueue", np.full(1, 1000, np.int32), cons(1)), ("tick", Expect([(1, 1, 0)], stored=1)),
+             ("enqueue", np.full(n, 1000, np.int32), cons(n)), ("tick", Expect([(n, n // 2, n // 2)], stored=1))]
+    return Case("carried_head", {"n": n}, PAIR, steps)
+
+
 DENSE = ("1v1", 10 ** 6, False)     # everybody fits everybody: the survivors of the cancels pair up in order
 
 

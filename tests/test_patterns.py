@@ -186,6 +186,7 @@ def pair_cases(geo, k_nested, levels_long, one_tile_too=True):
     out += [P.runs(1, 6), P.runs(63, 3), P.runs(64, 3), P.runs(65, 3), P.runs(T - 1, levels_long), P.runs(T + 1, levels_long)]
     out += [P.interleaved(R, max(1, 2 * T // R)) for R in (2, 64, 255, 256)]
     out += [P.blocked_head(PL + 64, "partner"), P.blocked_head(PL + 64, "cancel"), P.blocked_head(2 * G.WAVE, "cancel")]
+    out += [P.carried_head(1200)]     # 600 steps through kp_late's ring of 512; 1201 players: below PL_MAX in every geometry
     out += P.dead_variants(4 * T, T)
     # the alive share after pass 0 at, one below and one above the two compaction rules (mm_pair.inc: `qlen * 4 < m * 3`
     # on the tiled path — chains from PL_MAX on — and `m > PL_COMPACT_MIN && qlen * 2 < m` in the LDS-resident walk)
