@@ -63,6 +63,12 @@
  * player would first have a partner.  It applies the existing predicate to a question, matches nobody
  * and changes nothing; the witness is numpy over the oracle's lists.
  *
+ * What a chain looks like as a whole is mm_partner_stats: mm_partners' count and gap for EVERY waiting player of a mode,
+ * aggregated per rating group — how many have nobody inside the window, how many have nobody of their region at all, the
+ * histogram of gaps a window is chosen from.  Asking mm_partners about everybody costs pool x group length; this call
+ * sorts in_mode's waiting players on the device once (a radix sort of one 64-bit key each) and answers every player
+ * with binary searches.  Same predicate, same witness, nothing changes.
+ *
  * Acting on that answer is mm_expire_if, mm_move_if and mm_move_out_if: the plain call's selection by age, kept only
  * where the player's partner count lies in a range the owner names (mm_partner_rule).  Age alone is the wrong rule for
  * a first-fit chain: an old player with forty partners inside its window leaves a queue that would have seated it in
@@ -305,6 +311,45 @@ int mm_locate(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, ui
  * Reference: none.  Search.Worker.status/0 (lib/search/worker.ex:115-117, :326-334) sees the depth only. */
 int mm_partners(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags, uint32_t n,
                 const uint32_t* slots, uint32_t* partners, uint32_t* by_role, uint32_t* gap);
+
+#define MM_PARTNER_HIST 33u /* bucket 0: value 0; bucket 1 + floor(log2(value)) otherwise, as MM_WAIT_HIST */
+
+/* mm_partners' two words over every waiting player of one chain (mode, rating group), aggregated. */
+typedef struct mm_partner_group {      /* 304 bytes */
+    uint32_t waiting;                  /* the queries: waiting players of chain (mode, g)                       */
+    uint32_t candidates;               /* waiting players of chain (in_mode, g)                                 */
+    uint32_t alone;                    /* queries with partners == 0                                            */
+    uint32_t unreachable;              /* queries with gap == MM_NO_SLOT: no candidate passes the flag filters  */
+    uint64_t partners_sum;             /* sum of partners over the queries                                      */
+    uint64_t gap_sum;                  /* sum of gap over the queries that have one                             */
+    uint32_t partners_max;
+    uint32_t gap_max;                  /* 0 when no query has a gap                                             */
+    uint32_t partners_hist[MM_PARTNER_HIST];  /* every query, by its partners                                   */
+    uint32_t gap_hist[MM_PARTNER_HIST];       /* the queries that have a gap, by it; sums to waiting - unreachable */
+} mm_partner_group;
+
+/* per_group[cfg.n_groups]: what a chain looks like as a whole.  For every rating group g the queries are the waiting
+ * players of chain (mode, g) in mm_wait_group's sense — the LIVE queue entries plus the LIVE seats of the stored lobby; a
+ * MARKED player is neither a query nor a candidate — and for each query p, partners(p) and gap(p) are exactly the two
+ * words mm_partners(e, mode, in_mode, window, flags, 1, &p.slot, &partners, NULL, &gap) returns on the same pool: p is
+ * never its own partner, differences are exact for any two int32 ratings, `window` is a full uint32_t, gap saturates at
+ * 0xFFFFFFFE, rating and constraint word are the ones the engine holds, a player placed by the `group` override belongs
+ * to the chain it sits in.  The record of g is the aggregate of those words over the queries of g.
+ * Read-only, exactly as mm_locate and mm_partners: nothing of the pool, the host mirrors or the lists of mm_expired /
+ * mm_moved / mm_moved_rows changes, a snapshot taken after the call is byte for byte the one taken before it; it works
+ * with the clock off; results never depend on mm_tuning.  An engine that never calls it allocates and launches nothing
+ * for it.  Nobody waiting: MM_OK and zeroed records.
+ * MM_ERR_INVALID_ARG: e == NULL, per_group == NULL, no such mode or in_mode, a `flags` bit outside the two MM_MODE_*
+ * filters.  MM_ERR_STATE: the engine is poisoned by a failed tick.  MM_ERR_HIP / MM_ERR_OOM do NOT poison the engine;
+ * the call's scratch is released and the next call starts afresh.
+ * Cost: no step is queries x group length.  Two streams of in_mode's queues write one 64-bit key per waiting candidate
+ * (rating group | the fields the filters compare | rating in unsigned order), an LSD radix sort of the keys on the
+ * device — four passes for the rating, one more for each filter set and one when there is more than one rating group,
+ * three launches a pass — then one stream of mode's queues with four binary searches per waiting player; 16 bytes of
+ * scratch per key, grown to the longest call so far; one wait on the stream.
+ * Reference: none.  Search.Worker.status/0 (lib/search/worker.ex:115-117, :326-334) sees the depth only. */
+int mm_partner_stats(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags,
+                     mm_partner_group* per_group);
 
 /* Which of the players old enough a rule call selects: those whose partner count lies in a range. */
 typedef struct mm_partner_rule {

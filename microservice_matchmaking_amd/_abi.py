@@ -105,6 +105,22 @@ class MMWaitGroup(C.Structure):
                 "hist": np.asarray(self.hist[:], dtype=np.uint32)}
 
 
+MM_PARTNER_HIST = 33
+
+
+class MMPartnerGroup(C.Structure):
+    """include/mm_wait.h mm_partner_group: mm_partners' count and gap over the waiting players of one (mode, rating group)."""
+    _fields_ = [("waiting", C.c_uint32), ("candidates", C.c_uint32), ("alone", C.c_uint32), ("unreachable", C.c_uint32),
+                ("partners_sum", C.c_uint64), ("gap_sum", C.c_uint64), ("partners_max", C.c_uint32), ("gap_max", C.c_uint32),
+                ("partners_hist", C.c_uint32 * MM_PARTNER_HIST), ("gap_hist", C.c_uint32 * MM_PARTNER_HIST)]
+
+    def as_dict(self):
+        out = {n: int(getattr(self, n)) for n, _ in self._fields_[:8]}
+        out["partners_hist"] = np.asarray(self.partners_hist[:], dtype=np.uint32)
+        out["gap_hist"] = np.asarray(self.gap_hist[:], dtype=np.uint32)
+        return out
+
+
 class MMPartnerRule(C.Structure):
     _fields_ = [("in_mode", C.c_uint32), ("window", C.c_uint32), ("flags", C.c_uint32),
                 ("min_partners", C.c_uint32), ("max_partners", C.c_uint32)]
@@ -263,6 +279,9 @@ def bind(lib, prefix):
     if hasattr(lib, prefix + "partners"):                 # include/mm_wait.h: how many waiting players fit a player
         f("partners").argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p] * 4
         f("partners").restype = C.c_int
+    if hasattr(lib, prefix + "partner_stats"):            # include/mm_wait.h: partner counts of a whole mode, from a device sort
+        f("partner_stats").argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.POINTER(MMPartnerGroup)]
+        f("partner_stats").restype = C.c_int
     if hasattr(lib, prefix + "move_if"):                  # include/mm_wait.h: expiry and moves that select by partner count
         rulep = C.POINTER(MMPartnerRule)
         f("expire_if").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, rulep, u32p]
@@ -648,6 +667,20 @@ class EngineBase:
         self._check(self._fn("partners")(self._h, mode, in_mode, int(window or 0) & 0xFFFFFFFF, int(flags or 0) & 0xFFFFFFFF, n,
                                          _ptr(slots), _ptr(count), _ptr(roles), _ptr(near)), "partners")
         return count, roles, near
+
+    def partner_stats(self, mode, in_mode=None, window=None, flags=None):
+        """mm_partner_stats: `partners`' count and gap for every waiting player of `mode` against the waiting players of
+        `in_mode` (default: `mode`) at `window` and `flags` (default: in_mode's configuration), aggregated — one dict per
+        rating group (waiting, candidates, alone, unreachable, partners_sum, gap_sum, partners_max, gap_max,
+        partners_hist[33], gap_hist[33]).  Read-only."""
+        in_mode = mode if in_mode is None else in_mode
+        if 0 <= in_mode < self.cfg.n_modes:
+            window = self.cfg.modes[in_mode].window if window is None else window
+            flags = self.cfg.modes[in_mode].flags if flags is None else flags
+        out = (MMPartnerGroup * MM_MAX_GROUPS)()
+        self._check(self._fn("partner_stats")(self._h, mode, in_mode, int(window or 0) & 0xFFFFFFFF,
+                                              int(flags or 0) & 0xFFFFFFFF, out), "partner_stats")
+        return [out[g].as_dict() for g in range(self.cfg.n_groups)]
 
     def enqueue_stamped(self, rating, cons, stamp, group=None):
         """mm_enqueue_stamped: `enqueue`, every accepted player stamped stamp[i] instead of the clock.  -> slots."""

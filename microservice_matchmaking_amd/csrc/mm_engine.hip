@@ -418,6 +418,9 @@ __global__ __launch_bounds__(256) void k_reset(uint32_t n_chains, ChainDev* __re
 #define WT_SEATS (MM_MAX_TEAMS * 8)           // seats a LobbyDev has room for
 #define PAR_QTILE 512                         // query records a workgroup of k_par_count* stages in LDS at a time (mm_partners)
 #define SEL_TILE 256                          // candidates per workgroup of k_sel_count / k_sel_scatter*, one per thread (mm_*_if)
+#if !defined(FIT_TILE)
+#define FIT_TILE 2048                         // keys a workgroup of k_fit_hist / k_fit_scatter handles per radix pass (mm_partner_stats)
+#endif
 #include "mm_wait.inc"
 
 // ------------------------------------------------------------------------------------
@@ -1171,6 +1174,12 @@ struct mm_engine {
     uint4* d_par_rec;          // [par_cap] the query records: rating | constraint word | rating group | slot
     uint32_t* d_par_out;       // partners[par_cap] | gap[par_cap] | by_role[par_cap][MM_MAX_ROLES]
     uint32_t par_cap;          // queries the two have room for (they grow)
+    // mm_partner_stats (include/mm_wait.h): nothing below is allocated, and no kernel of it runs, before the first mm_partner_stats
+    uint32_t* d_fit_rows;      // [wait_max_chunks][WT_ROWS] + 1: d_wt_rows' layout; the total behind the rows is the table's length
+    FitGroupDev* d_fit_stats;  // [MM_MAX_GROUPS]
+    unsigned long long* d_fit_keys;   // [2][fit_cap] the table and the other half of a radix pass
+    uint32_t* d_fit_hist;      // [256][tiles of fit_cap] + [256]: a pass's digit counts / offsets, the digits' totals
+    uint32_t fit_cap;          // keys each half has room for (they grow)
 };
 
 // Named ranges for a profiler's timeline (the reference logs nothing per attempt).  MM_ROCTX=1 makes
@@ -3879,6 +3888,123 @@ extern "C" int mm_partners(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32
             (void)hipStreamSynchronize(e->stream);
             loc_release(e);
             par_release(e);
+        }
+        return rc;
+    });
+}
+
+// mm_partner_stats (include/mm_wait.h).  Its scratch: the rows and the records at the first call, the two halves of the key
+// table and a pass's digit counts grown to the longest table so far.
+static_assert(sizeof(FitGroupDev) == sizeof(mm_partner_group) && sizeof(mm_partner_group) == 304u &&
+              offsetof(FitGroupDev, partners_sum) == offsetof(mm_partner_group, partners_sum) &&
+              offsetof(FitGroupDev, gap_sum) == offsetof(mm_partner_group, gap_sum) &&
+              offsetof(FitGroupDev, partners_max) == offsetof(mm_partner_group, partners_max) &&
+              offsetof(FitGroupDev, partners_hist) == offsetof(mm_partner_group, partners_hist) &&
+              offsetof(FitGroupDev, gap_hist) == offsetof(mm_partner_group, gap_hist) && MM_PARTNER_HIST == 33u,
+              "FitGroupDev is mm_partner_group");
+static_assert(FIT_TILE % (WT_WAVES * 64) == 0 && FIT_TILE % WT_THREADS == 0 && MM_MAX_GROUPS <= 256, "a tile is whole rows of every wave; the group is one digit");
+
+static void fit_release(mm_engine* e)
+{
+    mem_release(e, e->d_fit_rows); mem_release(e, e->d_fit_stats); mem_release(e, e->d_fit_keys); mem_release(e, e->d_fit_hist);
+    e->fit_cap = 0;
+}
+
+static uint32_t fit_tiles_of(uint32_t n) { return (n + FIT_TILE - 1u) / FIT_TILE; }
+
+static int fit_alloc(mm_engine* e, uint32_t n)
+{
+    const size_t cap = e->cfg.capacity;
+    return guarded([&]() -> int {
+        if (!e->d_fit_stats) {
+            MMTRY(dev_alloc(e, e->d_fit_rows, ((size_t)wait_max_chunks(e) * WT_ROWS + 1u) * sizeof(uint32_t)));   // as wait_alloc sizes d_wt_rows
+            MMTRY(dev_alloc(e, e->d_fit_stats, MM_MAX_GROUPS * sizeof(FitGroupDev)));
+        }
+        if (n > e->fit_cap) {
+            uint32_t want = 1024u;
+            while (want < n) want <<= 1;                       // (n <= capacity, as in loc_alloc)
+            if (want > cap) want = (uint32_t)cap;
+            mem_release(e, e->d_fit_keys); mem_release(e, e->d_fit_hist);
+            e->fit_cap = 0;
+            MMTRY(dev_alloc(e, e->d_fit_keys, 2u * (size_t)want * sizeof(unsigned long long)));
+            MMTRY(dev_alloc(e, e->d_fit_hist, (size_t)FIT_DIGITS * (fit_tiles_of(want) + 1u) * sizeof(uint32_t)));
+            e->fit_cap = want;
+        }
+        return MM_OK;
+    });
+}
+
+static int partner_stats_impl(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags, mm_partner_group* per_group)
+{
+    const uint32_t G = e->cfg.n_groups, cap = e->cfg.capacity;
+    // the table holds waiting players of one mode: never more than are queued in all of them, never more than there are slots
+    const uint32_t bound = (uint32_t)(e->live_upper < cap ? e->live_upper : cap);
+    MMTRY(fit_alloc(e, bound));
+    WaitParams C = wait_params(e, in_mode, 0u);                // the candidates' walk
+    C.stamp = NULL;
+    C.rows = e->d_fit_rows;                                    // rows of the call's own: the clock's and the lookup's may not exist
+    C.out_slot = NULL; C.out_group = NULL; C.out_age = NULL; C.stats = NULL;
+    WaitParams Q = C;                                          // the queries' walk
+    Q.mode = mode;
+    Q.teams = e->cfg.modes[mode].teams;
+    FitParams F;
+    memset(&F, 0, sizeof(F));
+    F.window = window;
+    F.eqmask = ((flags & MM_MODE_REGION_FILTER) ? (0xFFu << 4) : 0u) | ((flags & MM_MODE_PARTY_FILTER) ? (0xFu << 12) : 0u);   // as partners_impl
+    F.self = in_mode == mode ? 1u : 0u;
+    F.key_cap = e->fit_cap;
+    F.q_rating = e->d_q_rating;
+    F.q_cons = e->d_q_cons;
+    F.n_keys = e->d_fit_rows + (size_t)C.max_chunks * WT_ROWS;
+    F.hist = e->d_fit_hist;
+    F.stats = e->d_fit_stats;
+    unsigned long long* half[2] = { e->d_fit_keys, e->d_fit_keys + e->fit_cap };
+    const uint32_t grid = wait_grid(e), tiles = fit_tiles_of(bound);
+    const dim3 wg(WT_THREADS), sg(tiles < 1024u ? tiles : 1024u);
+    HIPCHK(e, hipMemsetAsync(e->d_fit_stats, 0, G * sizeof(FitGroupDev), e->stream));
+    hipLaunchKernelGGL(k_fit_count, dim3(grid), wg, 0, e->stream, C);
+    hipLaunchKernelGGL(k_wait_scan, dim3(1), wg, 0, e->stream, C);
+    F.keys_out = half[0];
+    hipLaunchKernelGGL(k_fit_keys, dim3(grid), wg, 0, e->stream, C, F);
+    // the passes, least significant byte first: the rating's four, then the bytes that are not zero in every key
+    uint32_t shifts[7], n_pass = 0, at = 0;
+    for (uint32_t s = 0; s < 32u; s += 8u) shifts[n_pass++] = s;
+    if (flags & MM_MODE_REGION_FILTER) shifts[n_pass++] = 32u;
+    if (flags & MM_MODE_PARTY_FILTER) shifts[n_pass++] = 40u;
+    if (G > 1u) shifts[n_pass++] = 48u;
+    for (uint32_t p = 0; p < n_pass; ++p, at ^= 1u) {
+        F.shift = shifts[p];
+        F.keys = half[at];
+        F.keys_out = half[at ^ 1u];
+        hipLaunchKernelGGL(k_fit_hist, sg, wg, 0, e->stream, F);
+        hipLaunchKernelGGL(k_fit_scan, dim3(FIT_DIGITS / WT_WAVES), wg, 0, e->stream, F);
+        hipLaunchKernelGGL(k_fit_scatter, sg, wg, 0, e->stream, F);
+    }
+    F.keys = half[at];
+    F.keys_out = NULL;
+    hipLaunchKernelGGL(k_fit_search, dim3(grid), wg, 0, e->stream, Q, F);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(per_group, e->d_fit_stats, G * sizeof(mm_partner_group), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return MM_OK;
+}
+
+extern "C" int mm_partner_stats(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags, mm_partner_group* per_group)
+{
+    return guarded([&]() -> int {
+        if (!e || !per_group || mode >= e->cfg.n_modes || in_mode >= e->cfg.n_modes || (flags & ~(MM_MODE_REGION_FILTER | MM_MODE_PARTY_FILTER)))
+            return MM_ERR_INVALID_ARG;
+        if (e->poisoned) return MM_ERR_STATE;
+        if (e->live_upper == 0) {                              // nobody waits in any mode: zeroed records, nothing is launched
+            memset(per_group, 0, e->cfg.n_groups * sizeof(mm_partner_group));
+            return MM_OK;
+        }
+        ON_ENGINE_DEVICE(e);
+        RoctxRange rr("mm_partner_stats");
+        const int rc = guarded([&]() -> int { return partner_stats_impl(e, mode, in_mode, window, flags, per_group); });
+        if (rc != MM_OK) {                                     // as in mm_locate: nothing of the pool was written, the engine stays usable
+            (void)hipStreamSynchronize(e->stream);
+            fit_release(e);
         }
         return rc;
     });

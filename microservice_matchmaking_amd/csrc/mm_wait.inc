@@ -857,3 +857,404 @@ __global__ __launch_bounds__(WT_THREADS) void k_par_count(WaitParams P, ParParam
 __global__ __launch_bounds__(WT_THREADS) void k_par_count_role(WaitParams P, ParParams Q) { par_count_body<true, false>(P, Q); }
 __global__ __launch_bounds__(WT_THREADS) void k_par_count_gap(WaitParams P, ParParams Q) { par_count_body<false, true>(P, Q); }
 __global__ __launch_bounds__(WT_THREADS) void k_par_count_all(WaitParams P, ParParams Q) { par_count_body<true, true>(P, Q); }
+
+// mm_partner_stats (include/mm_wait.h): mm_partners' two words for EVERY waiting player of a mode, aggregated per rating
+// group — from a sorted table of in_mode's waiting players instead of queries x group length predicate tests.  Read-only.
+//   k_fit_count    in_mode's walk, k_loc_count's shape: the LIVE entries per wave, and the LIVE seats in the seats' row; the
+//                  unchanged k_wait_scan turns the rows into ranks with the total — the table's length — behind them;
+//   k_fit_keys     the same walk: one 64-bit key per waiting candidate at its rank (a stable compaction: the table's first
+//                  order is the walk's) — rating group << 48 | the constraint-word fields the filters compare << 32 (region
+//                  in bits 32..39, party in 40..43, zero where a filter is off) | rating ^ 2^31, unsigned order;
+//   k_fit_hist / k_fit_scan / k_fit_scatter   one LSD radix pass over one byte of the key, FIT_TILE keys a workgroup: the
+//                  tile's digit histogram into hist[digit][tile], an exclusive scan along every digit's row (a wave a
+//                  digit) with the 256 totals behind the table, then every key to the start of its digit (the scan of the
+//                  totals, done by every scatter workgroup for itself) + hist[digit][tile] + its rank among the tile's
+//                  keys of that digit.  The rank is stable: a tile is cut
+//                  into waves and rows in index order, a key's rank is the count of its digit in the rows before it (an
+//                  LDS counter per wave and digit, the waves before it added afterwards) plus the lanes below it in its own
+//                  row (eight ballots give the lanes of the same digit).  Three launches a pass, no workgroup waits for
+//                  another; the host leaves out the passes whose byte is zero in every key;
+//   k_fit_search   mode's walk: per waiting player two binary searches for rating -+ window (in 64 bits, clamped to int32)
+//                  with the player's own group and filter fields in front — keys of another segment compare below or
+//                  above the pair, so the searches need no segment bounds — and two more inside that range for the run
+//                  of equal ratings; the run, or else the table's neighbours of the same segment, give the gap.  With
+//                  in_mode == mode the player itself is in the table exactly once: 1 comes off both counts.  Then
+//                  k_wait_stats' aggregation: registers, wave, LDS, one global atomic per touched word of the record.
+#if !defined(FIT_TILE)
+#error "mm_wait.inc: define FIT_TILE beside the WT_* chunk geometry before including this file (mm_engine.hip does)"
+#endif
+#define FIT_PER_WAVE (FIT_TILE / WT_WAVES)
+#define FIT_ITERS (FIT_PER_WAVE / 64)
+#define FIT_DIGITS 256u
+
+struct FitGroupDev {                          // mm_partner_group (include/mm_wait.h) with types atomicAdd takes
+    uint32_t waiting, candidates, alone, unreachable;
+    unsigned long long partners_sum, gap_sum;
+    uint32_t partners_max, gap_max;
+    uint32_t partners_hist[33];
+    uint32_t gap_hist[33];
+};
+
+struct FitParams {
+    uint32_t window, eqmask;                  // mm_partners' predicate
+    uint32_t self;                            // 1: in_mode == mode, every query is in the table once
+    uint32_t key_cap;                         // keys each half of `keys` has room for
+    uint32_t shift;                           // the pass's byte of the key
+    const int32_t* q_rating;
+    const uint32_t* q_cons;
+    const uint32_t* n_keys;                   // the table's length: the total behind the rows of k_fit_count
+    const unsigned long long* keys;           // what a pass reads; the sorted table for k_fit_search
+    unsigned long long* keys_out;             // what k_fit_keys and a pass write
+    uint32_t* hist;                           // [FIT_DIGITS][tiles]; the digits' totals from [FIT_DIGITS * tiles of key_cap] on
+    FitGroupDev* stats;                       // [n_groups], zeroed by the host
+};
+
+static __device__ __forceinline__ uint32_t fit_tiles(uint32_t n) { return (n + FIT_TILE - 1u) / FIT_TILE; }
+
+static __device__ __forceinline__ unsigned long long fit_prefix(uint32_t g, uint32_t cons, uint32_t eqmask)
+{
+    return ((unsigned long long)g << 48) | ((unsigned long long)((cons & eqmask) >> 4) << 32);
+}
+
+static __device__ __forceinline__ uint32_t fit_bias(int32_t rating) { return (uint32_t)rating ^ 0x80000000u; }
+
+__global__ __launch_bounds__(WT_THREADS) void k_fit_count(WaitParams P)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        uint32_t cnt = 0;
+        if (w0 < len) {
+            uint32_t sl[WT_ITERS], tg[WT_ITERS];
+            const uint32_t live = loc_load<false>(P, nullptr, qo, w0, len, lane, sl, tg);
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) cnt += (uint32_t)__popcll(__ballot((live >> r) & 1u));
+        }
+        if (lane == 0) P.rows[(size_t)b * WT_ROWS + 1u + wave] = cnt;
+        if (wave == 0) {
+            const uint32_t sl = k == 0u && (uint32_t)lane < WT_SEATS ? wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane) : MM_NO_SLOT;
+            const unsigned long long m = __ballot(sl < P.capacity && P.state[sl] == MM_ST_LIVE);
+            if (lane == 0) P.rows[(size_t)b * WT_ROWS] = (uint32_t)__popcll(m);
+        }
+    }
+}
+
+// P: the walk's parameters for in_mode, the rows scanned.
+__global__ __launch_bounds__(WT_THREADS) void k_fit_keys(WaitParams P, FitParams F)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        uint32_t base = P.rows[(size_t)b * WT_ROWS + 1u + wave], mine = 0u;
+        if (w0 < len) {
+            uint32_t sl[WT_ITERS], cn[WT_ITERS];
+            int32_t rt[WT_ITERS];
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) {
+                const uint32_t i = w0 + r * 64 + lane;
+                const bool in = i < len;
+                sl[r] = in ? P.q_slot[qo + i] : MM_NO_SLOT;
+                rt[r] = in ? F.q_rating[qo + i] : 0;
+                cn[r] = in ? F.q_cons[qo + i] : 0u;
+            }
+            uint8_t st[WT_ITERS];
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) st[r] = sl[r] < P.capacity ? P.state[sl[r]] : (uint8_t)MM_ST_FREE;
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) {
+                const bool lv = st[r] == MM_ST_LIVE;
+                const unsigned long long m = __ballot(lv);
+                const uint32_t at = base + (uint32_t)__popcll(m & lt);
+                if (lv && at < F.key_cap) F.keys_out[at] = fit_prefix(g, cn[r], F.eqmask) | fit_bias(rt[r]);
+                base += (uint32_t)__popcll(m);
+                mine += (uint32_t)__popcll(m);
+            }
+        }
+        if (wave == 0) {
+            const LobbyDev& lb = P.chains[P.mode * P.n_groups + g].lobby;
+            uint32_t sl = MM_NO_SLOT, t = 0, i = 0;
+            if (k == 0u && (uint32_t)lane < WT_SEATS && wait_seat_at(lb, P.teams, (uint32_t)lane, t, i)) sl = lb.slot[t][i];
+            const bool lv = sl < P.capacity && P.state[sl] == MM_ST_LIVE;
+            const unsigned long long m = __ballot(lv);
+            const uint32_t at = P.rows[(size_t)b * WT_ROWS] + (uint32_t)__popcll(m & lt);
+            if (lv && at < F.key_cap) F.keys_out[at] = fit_prefix(g, lb.cons[t][i], F.eqmask) | fit_bias(lb.rating[t][i]);
+            mine += (uint32_t)__popcll(m);
+        }
+        if (lane == 0 && mine) atomicAdd(&F.stats[g].candidates, mine);
+    }
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_fit_hist(FitParams F)
+{
+    __shared__ uint32_t s_h[FIT_DIGITS];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t n = dev_min_u32(*F.n_keys, F.key_cap), tiles = fit_tiles(n);
+    for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        for (uint32_t d = tid; d < FIT_DIGITS; d += WT_THREADS) s_h[d] = 0u;
+        __syncthreads();
+#pragma unroll
+        for (uint32_t r = 0; r < FIT_TILE / WT_THREADS; ++r) {
+            const uint32_t i = t * FIT_TILE + r * WT_THREADS + tid;
+            if (i < n) atomicAdd(&s_h[(uint32_t)(F.keys[i] >> F.shift) & (FIT_DIGITS - 1u)], 1u);
+        }
+        __syncthreads();
+        for (uint32_t d = tid; d < FIT_DIGITS; d += WT_THREADS) F.hist[(size_t)d * tiles + t] = s_h[d];
+        __syncthreads();
+    }
+}
+
+// A wave per digit: the exclusive scan along hist[digit][0 .. tiles) in place — the keys of the digit in the tiles in front —
+// 64 tiles a step, and the digit's total behind the table.  FIT_DIGITS / WT_WAVES workgroups, no wave looks at another's
+// row and there is no barrier; the scan ACROSS the digits, 256 totals, is done by every workgroup of k_fit_scatter for itself.
+__global__ __launch_bounds__(WT_THREADS) void k_fit_scan(FitParams F)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t tiles = fit_tiles(dev_min_u32(*F.n_keys, F.key_cap)), d = blockIdx.x * WT_WAVES + (uint32_t)wave;
+    if (d >= FIT_DIGITS) return;
+    uint32_t* const row = F.hist + (size_t)d * tiles;
+    uint32_t run = 0u;
+    for (uint32_t base = 0; base < tiles; base += 64u) {
+        const uint32_t i = base + (uint32_t)lane, v = i < tiles ? row[i] : 0u, incl = wave_incl_scan(v, lane);
+        if (i < tiles) row[i] = run + incl - v;
+        run += (uint32_t)__shfl((int)incl, 63);
+    }
+    if (lane == 0) F.hist[(size_t)FIT_DIGITS * fit_tiles(F.key_cap) + d] = run;
+}
+
+__global__ __launch_bounds__(WT_THREADS) void k_fit_scatter(FitParams F)
+{
+    __shared__ uint32_t s_cnt[WT_WAVES][FIT_DIGITS];      // keys of a digit per wave; then where the wave's first one goes
+    __shared__ uint32_t s_dig[FIT_DIGITS], s_wtot[WT_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const uint32_t n = dev_min_u32(*F.n_keys, F.key_cap), tiles = fit_tiles(n);
+    {   // where a digit's keys start in the output: the exclusive scan of k_fit_scan's 256 totals, a thread per digit
+        static_assert(WT_THREADS == FIT_DIGITS, "a thread per digit");
+        const uint32_t v = F.hist[(size_t)FIT_DIGITS * fit_tiles(F.key_cap) + (uint32_t)tid], incl = wave_incl_scan(v, lane);
+        if (lane == 63) s_wtot[wave] = incl;
+        __syncthreads();
+        uint32_t run = incl - v;
+        for (int w = 0; w < wave; ++w) run += s_wtot[w];
+        s_dig[tid] = run;
+        __syncthreads();
+    }
+    for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        for (uint32_t d = (uint32_t)tid; d < WT_WAVES * FIT_DIGITS; d += WT_THREADS) s_cnt[d / FIT_DIGITS][d % FIT_DIGITS] = 0u;
+        __syncthreads();
+        const uint32_t w0 = t * FIT_TILE + (uint32_t)wave * FIT_PER_WAVE;
+        unsigned long long key[FIT_ITERS];
+        uint32_t rank[FIT_ITERS];
+#pragma unroll
+        for (uint32_t r = 0; r < FIT_ITERS; ++r) {
+            const uint32_t i = w0 + r * 64 + lane;
+            key[r] = i < n ? F.keys[i] : ~0ull;
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < FIT_ITERS; ++r) {
+            const bool in = w0 + r * 64 + lane < n;
+            const uint32_t d = (uint32_t)(key[r] >> F.shift) & (FIT_DIGITS - 1u);
+            unsigned long long same = __ballot(in);       // the lanes of this row that hold my digit
+#pragma unroll
+            for (uint32_t bit = 0; bit < 8u; ++bit) {
+                const bool one = (d >> bit) & 1u;
+                const unsigned long long m = __ballot(one);
+                same &= one ? m : ~m;
+            }
+            // the lowest lane of a digit counts for all of them; what the counter held before is the rows in front
+            const int lead = in ? __popcll((same & (0ull - same)) - 1ull) : lane;
+            uint32_t before = 0u;
+            if (in && lane == lead) {                     // (no atomic: the counter is this wave's alone, and one lane per digit of the row is here)
+                before = s_cnt[wave][d];
+                s_cnt[wave][d] = before + (uint32_t)__popcll(same);
+            }
+            before = (uint32_t)__shfl((int)before, lead);
+            rank[r] = before + (uint32_t)__popcll(same & lt);
+        }
+        __syncthreads();
+        for (uint32_t d = (uint32_t)tid; d < FIT_DIGITS; d += WT_THREADS) {
+            uint32_t run = s_dig[d] + F.hist[(size_t)d * tiles + t];
+            for (uint32_t w = 0; w < WT_WAVES; ++w) {
+                const uint32_t c = s_cnt[w][d];
+                s_cnt[w][d] = run;
+                run += c;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t r = 0; r < FIT_ITERS; ++r) {
+            if (w0 + r * 64 + lane >= n) continue;
+            const uint32_t at = s_cnt[wave][(uint32_t)(key[r] >> F.shift) & (FIT_DIGITS - 1u)] + rank[r];
+            if (at < F.key_cap) F.keys_out[at] = key[r];
+        }
+        __syncthreads();
+    }
+}
+
+// The first index in [lo, hi) whose key is not below k (OVER: is above k); hi when there is none.
+template <bool OVER>
+static __device__ __forceinline__ uint32_t fit_bound(const unsigned long long* __restrict__ keys, uint32_t lo, uint32_t hi, unsigned long long k)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        const unsigned long long v = keys[mid];
+        if (OVER ? v <= k : v < k) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// mm_partners' `partners` and `gap` of one waiting player of rating group g, from the sorted table of n keys.
+static __device__ __forceinline__ void fit_one(const FitParams& F, uint32_t n, uint32_t g, int32_t rating, uint32_t cons,
+                                               uint32_t& partners, uint32_t& gap)
+{
+    const unsigned long long pre = fit_prefix(g, cons, F.eqmask);
+    long long lo = (long long)rating - (long long)F.window, hi = (long long)rating + (long long)F.window;
+    if (lo < -2147483648ll) lo = -2147483648ll;
+    if (hi > 2147483647ll) hi = 2147483647ll;
+    const uint32_t mine = fit_bias(rating);
+    const uint32_t a = fit_bound<false>(F.keys, 0u, n, pre | fit_bias((int32_t)lo));
+    const uint32_t b = fit_bound<true>(F.keys, a, n, pre | fit_bias((int32_t)hi));
+    partners = b - a - F.self;
+    const uint32_t e = fit_bound<false>(F.keys, a, b, pre | mine);
+    const uint32_t f = fit_bound<true>(F.keys, e, b, pre | mine);
+    gap = MM_NO_SLOT;
+    if (f - e > F.self) { gap = 0u; return; }
+    if (e > 0u) {
+        const unsigned long long v = F.keys[e - 1u];
+        if ((v >> 32) == (pre >> 32)) gap = dev_min_u32(mine - (uint32_t)v, 0xFFFFFFFEu);
+    }
+    if (f < n) {
+        const unsigned long long v = F.keys[f];
+        if ((v >> 32) == (pre >> 32)) gap = dev_min_u32(gap, dev_min_u32((uint32_t)v - mine, 0xFFFFFFFEu));
+    }
+}
+
+// MM_PARTNER_HIST's bucket: 0 for 0, else the value's bit length (wait_bucket's rule).  Not wait_bucket itself, and nothing
+// here calls __clzll: with one more caller of that header function the compiler folds it differently inside k_wait_stats,
+// whose instructions are to stay the ones they were.
+static __device__ __forceinline__ uint32_t fit_bucket(uint32_t v) { return v ? 32u - (uint32_t)__builtin_clz(v) : 0u; }
+
+static __device__ __forceinline__ uint32_t fit_wave_sum(uint32_t v, int lane)
+{
+    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl((int)v, lane ^ d);
+    return v;
+}
+
+static __device__ __forceinline__ uint32_t fit_wave_max(uint32_t v, int lane)
+{
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t o = (uint32_t)__shfl((int)v, lane ^ d);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+static __device__ __forceinline__ unsigned long long fit_wave_sum64(unsigned long long v, int lane)
+{
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane ^ d), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane ^ d);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+// P: the walk's parameters for `mode`; F.keys the sorted table.
+__global__ __launch_bounds__(WT_THREADS) void k_fit_search(WaitParams P, FitParams F)
+{
+    __shared__ uint32_t s_ph[33], s_gh[33];
+    __shared__ uint32_t s_cnt, s_alone, s_unr, s_pmax, s_gmax;
+    __shared__ unsigned long long s_psum, s_gsum;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t n = dev_min_u32(*F.n_keys, F.key_cap);
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        uint32_t g, k, len;
+        if (!wait_chunk(P, b, g, k, len)) return;
+        if (tid < 33) { s_ph[tid] = 0; s_gh[tid] = 0; }
+        if (tid == 0) { s_cnt = 0; s_alone = 0; s_unr = 0; s_pmax = 0; s_gmax = 0; s_psum = 0; s_gsum = 0; }
+        __syncthreads();
+        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
+        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        uint32_t cnt = 0, alone = 0, unr = 0, pmax = 0, gmax = 0;
+        unsigned long long psum = 0, gsum = 0;
+        uint32_t sl[WT_ITERS + 1], cn[WT_ITERS + 1];      // the wave's queue rows; behind them the seats' row (wave 0 of the group's first chunk)
+        int32_t rt[WT_ITERS + 1];
+        uint32_t live = 0;
+        if (w0 < len) {
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r) {
+                const uint32_t i = w0 + r * 64 + lane;
+                const bool in = i < len;
+                sl[r] = in ? P.q_slot[qo + i] : MM_NO_SLOT;
+                rt[r] = in ? F.q_rating[qo + i] : 0;
+                cn[r] = in ? F.q_cons[qo + i] : 0u;
+            }
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r)
+                if (sl[r] < P.capacity && P.state[sl[r]] == MM_ST_LIVE) live |= 1u << r;
+        }
+        if (wave == 0 && k == 0u && (uint32_t)lane < WT_SEATS) {
+            const LobbyDev& lb = P.chains[P.mode * P.n_groups + g].lobby;
+            uint32_t t = 0, i = 0;
+            if (wait_seat_at(lb, P.teams, (uint32_t)lane, t, i)) {
+                sl[WT_ITERS] = lb.slot[t][i];
+                rt[WT_ITERS] = lb.rating[t][i];
+                cn[WT_ITERS] = lb.cons[t][i];
+                if (sl[WT_ITERS] < P.capacity && P.state[sl[WT_ITERS]] == MM_ST_LIVE) live |= 1u << WT_ITERS;
+            }
+        }
+#pragma unroll
+        for (uint32_t r = 0; r <= WT_ITERS; ++r)
+            if ((live >> r) & 1u) {
+                uint32_t partners, gap;
+                fit_one(F, n, g, rt[r], cn[r], partners, gap);
+                ++cnt;
+                psum += partners;
+                pmax = partners > pmax ? partners : pmax;
+                alone += partners == 0u;
+                atomicAdd(&s_ph[fit_bucket(partners)], 1u);
+                if (gap == MM_NO_SLOT) ++unr;
+                else {
+                    gsum += gap;
+                    gmax = gap > gmax ? gap : gmax;
+                    atomicAdd(&s_gh[fit_bucket(gap)], 1u);
+                }
+            }
+        cnt = fit_wave_sum(cnt, lane);
+        alone = fit_wave_sum(alone, lane);
+        unr = fit_wave_sum(unr, lane);
+        pmax = fit_wave_max(pmax, lane);
+        gmax = fit_wave_max(gmax, lane);
+        psum = fit_wave_sum64(psum, lane);
+        gsum = fit_wave_sum64(gsum, lane);
+        if (lane == 0 && cnt) {
+            atomicAdd(&s_cnt, cnt);
+            atomicAdd(&s_alone, alone);
+            atomicAdd(&s_unr, unr);
+            atomicMax(&s_pmax, pmax);
+            atomicMax(&s_gmax, gmax);
+            atomicAdd(&s_psum, psum);
+            atomicAdd(&s_gsum, gsum);
+        }
+        __syncthreads();
+        FitGroupDev* const out = F.stats + g;
+        if (tid < 33 && s_ph[tid]) atomicAdd(&out->partners_hist[tid], s_ph[tid]);
+        if (tid >= 64 && tid < 64 + 33 && s_gh[tid - 64]) atomicAdd(&out->gap_hist[tid - 64], s_gh[tid - 64]);
+        if (tid == 128 && s_cnt) {
+            atomicAdd(&out->waiting, s_cnt);
+            if (s_alone) atomicAdd(&out->alone, s_alone);
+            if (s_unr) atomicAdd(&out->unreachable, s_unr);
+            if (s_psum) atomicAdd(&out->partners_sum, s_psum);
+            if (s_gsum) atomicAdd(&out->gap_sum, s_gsum);
+            if (s_pmax) atomicMax(&out->partners_max, s_pmax);
+            if (s_gmax) atomicMax(&out->gap_max, s_gmax);
+        }
+        __syncthreads();
+    }
+}

@@ -283,6 +283,17 @@ class ShardedSearch:
                                       % (mode, in_mode))
         return self.engine.partners(mode, slots, None, window, flags, by_role, gap)
 
+    def partner_stats(self, mode, in_mode=None, window=None, flags=None):
+        """mm_partner_stats (include/mm_wait.h) for in_mode == mode.  Chain-local, as `partners`: a rank's records are valid
+        for the rating groups it owns (the others read as this rank's engine holds them: nobody waiting), and there is no
+        collective.  With in_mode != mode the chains (mode, g) and (in_mode, g) may have different owners and the key table
+        would have to travel between ranks: not built, NotImplementedError on every rank.  -> one dict per rating group."""
+        if in_mode is not None and in_mode != mode:
+            raise NotImplementedError("ShardedSearch.partner_stats with in_mode != mode: chain (mode %d, g) and chain (in_mode %d, g) "
+                                      "may have different owners, and carrying the sorted table between ranks is not built"
+                                      % (mode, in_mode))
+        return self.engine.partner_stats(mode, None, window, flags)
+
     def tick(self, mode=0):
         return self.engine.tick(mode)
 

@@ -44,13 +44,21 @@ with a wider 1v1 mode as the fallback, all of the pool waiting and 1 000 entries
 beside plain mm_move at the same share and the host route — the owner's stamp table, mm_partners on the old slots, a numpy
 filter, mm_cancel, mm_enqueue_stamped — in turns on the same engine; the host route must hand out the same new slots.
 
+--partner-stats adds mm_partner_stats on the same waiting pool (all of it queued, 1 000 entries cancelled), at the mode's own
+window and flags, beside the two routes to the same records that exist without it, in turns on the same engine: mm_partners
+over every waiting slot (partners and gap) plus the numpy bucketing per rating group, and the host route of --partners
+extended to every waiting player plus the same bucketing.  All three must produce the same records, every step.  The
+kernel-by-kernel split (key build, each radix pass, the search) comes from a kernel trace of --partner-stats-trace-run,
+handed in with --partner-stats-trace.
+
 Usage (GPU box, repo root):  python tools/bench_wait.py [--steps 30] [--players 1000000] > profiles/wait_1m.json
                              python tools/bench_wait.py --move > profiles/wait_move_1m.json
                              python tools/bench_wait.py --carry > profiles/wait_carry_1m.json
                              python tools/bench_wait.py --rotate > profiles/wait_rotate_1m.json
                              python tools/bench_wait.py --locate > profiles/wait_locate_1m.json
                              python tools/bench_wait.py --partners > profiles/wait_partners_1m.json
-                             python tools/bench_wait.py --move-if > profiles/wait_move_if_1m.json"""
+                             python tools/bench_wait.py --move-if > profiles/wait_move_if_1m.json
+                             python tools/bench_wait.py --partner-stats > profiles/wait_partner_stats_1m.json"""
 import argparse
 import json
 import os
@@ -516,6 +524,156 @@ def measure_move_if(args, rating, cons, d_rating, d_cons, now):
     return out
 
 
+def bucket_records(partners, gap, group, candidates):
+    """mm_partner_group (include/mm_wait.h) per rating group, in numpy, from mm_partners' two columns over the waiting players
+    and each player's rating group."""
+    pow2 = 1 << np.arange(33, dtype=np.uint64)
+    bits = lambda v: np.bincount(np.searchsorted(pow2, v, side="right").astype(np.int64), minlength=33)[:33].tolist()
+    out = []
+    for g, cand in enumerate(candidates):
+        p, d = partners[group == g].astype(np.uint64), gap[group == g].astype(np.uint64)
+        has = d != 0xFFFFFFFF
+        out.append({"waiting": int(p.size), "candidates": int(cand), "alone": int((p == 0).sum()), "unreachable": int((~has).sum()),
+                    "partners_sum": int(p.sum()), "gap_sum": int(d[has].sum()), "partners_max": int(p.max()) if p.size else 0,
+                    "gap_max": int(d[has].max()) if has.any() else 0, "partners_hist": bits(p), "gap_hist": bits(d[has])})
+    return out
+
+
+def plain_records(recs):
+    return [{k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in r.items()} for r in recs]
+
+
+FIT_SEQUENCE = ("k_fit_count", "k_wait_scan", "k_fit_keys")
+
+
+def trace_split(path):
+    """The kernels of mm_partner_stats out of a kernel trace (rocprofv3 --kernel-trace, its *_kernel_trace.csv) of
+    `--partner-stats-trace-run`: a call is k_fit_count, k_wait_scan, k_fit_keys, then k_fit_hist / k_fit_scan / k_fit_scatter
+    once per radix pass, then k_fit_search.  Medians over the calls, in microseconds."""
+    import csv
+    rows = []
+    with open(path, newline="") as f:
+        for r in csv.DictReader(f):
+            name = r.get("Kernel_Name", "")
+            short = next((k for k in FIT_SEQUENCE + ("k_fit_hist", "k_fit_scan", "k_fit_scatter", "k_fit_search") if name.startswith(k)), None)
+            if short:
+                rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short))
+    rows.sort()
+    calls, cur = [], None
+    for t0, t1, k in rows:
+        if k == "k_fit_count":
+            cur = {"key_build": 0.0, "passes": [], "search": 0.0, "first": t0}
+            calls.append(cur)
+        if cur is None:
+            continue
+        us = (t1 - t0) / 1e3
+        if k in FIT_SEQUENCE:
+            cur["key_build"] += us
+        elif k == "k_fit_hist":
+            cur["passes"].append({"hist": us, "scan": 0.0, "scatter": 0.0})
+        elif k in ("k_fit_scan", "k_fit_scatter") and cur["passes"]:
+            cur["passes"][-1][k[6:]] += us
+        elif k == "k_fit_search":
+            cur["search"] = us
+            cur["span"] = (t1 - cur["first"]) / 1e3
+    calls = [c for c in calls if "span" in c]
+    if not calls:
+        return None
+    n_pass = max(len(c["passes"]) for c in calls)
+    calls = [c for c in calls if len(c["passes"]) == n_pass]
+    return {"calls": len(calls), "unit": "us, medians over the calls of the trace",
+            "key_build_count_scan_keys": med([c["key_build"] for c in calls]),
+            "radix_passes": [{k: med([c["passes"][p][k] for c in calls]) for k in ("hist", "scan", "scatter")} for p in range(n_pass)],
+            "search": med([c["search"] for c in calls]),
+            "first_start_to_last_end": med([c["span"] for c in calls])}
+
+
+def partner_stats_pool(args, d_rating, d_cons, now):
+    """cfg-2's pool as --partners sets it up: all of it waiting, 1 000 entries cancelled."""
+    from microservice_matchmaking_amd import Engine, make_config, mode_1v1
+    n = args.players
+    cap = 1 << (n - 1).bit_length()
+    cfg = make_config([mode_1v1(window=25, region_filter=True)], capacity=cap, timing=True)
+    eng = Engine(cfg)
+    eng.clock_set(now)
+    eng.enqueue_device(d_rating, d_cons)                           # nobody ticks: all of them wait
+    gone = np.zeros(cap, bool)
+    gone[np.random.default_rng(3).choice(n, size=min(1000, n), replace=False)] = True
+    eng.cancel(np.flatnonzero(gone).astype(np.uint32))
+    return eng, cfg, gone
+
+
+def measure_partner_stats(args, rating, cons, d_rating, d_cons, now):
+    """mm_partner_stats, mm_partners over every waiting slot plus the numpy bucketing, and the host's sorted tables plus the
+    same bucketing, in turns on one engine over the same waiting pool, at the mode's own window and flags: the same records."""
+    from microservice_matchmaking_amd.sharding import rating_groups
+    n = args.players
+    eng, cfg, gone = partner_stats_pool(args, d_rating, d_cons, now)
+    cap, G = int(cfg.capacity), int(cfg.n_groups)
+    table_r, table_c = np.zeros(cap, np.int32), np.zeros(cap, np.uint32)
+    table_r[:n], table_c[:n] = rating, cons                        # slot i holds player i: the owner's tables
+    waiting = np.flatnonzero(~gone[:n]).astype(np.uint32)
+    group = rating_groups(cfg, rating)[waiting]
+    candidates = np.bincount(group, minlength=G)
+    routes = ("stats", "device", "host")
+    t = {r: [] for r in routes}
+    t["drain"], t["device_call"], t["host_tables"] = [], [], []
+    got = {}
+    with eng:
+        for k in range(args.warmup + args.steps):
+            for route in routes[k % 3:] + routes[:k % 3]:
+                t0 = time.perf_counter()
+                if route == "stats":
+                    got[route] = plain_records(eng.partner_stats(0))
+                elif route == "device":
+                    p, _, d = eng.partners(0, waiting, by_role=False)
+                    ta = time.perf_counter()
+                    got[route] = bucket_records(p, d, group, candidates)
+                else:
+                    p, _, d = host_partners(eng, 0, gone, table_r, table_c, waiting, 25)
+                    ta = time.perf_counter()
+                    got[route] = bucket_records(p, d, group, candidates)
+                t1 = time.perf_counter()
+                if route == "host":                                # (as --partners: the first GPU call after the host route, on its own)
+                    eng.locate(0, waiting[:1])
+                    t2 = time.perf_counter()
+                    if k >= args.warmup:
+                        t["drain"].append((t2 - t1) * 1e3)
+                if k >= args.warmup:
+                    t[route].append((t1 - t0) * 1e3)
+                    if route != "stats":
+                        t["device_call" if route == "device" else "host_tables"].append((ta - t0) * 1e3)
+            assert got["stats"] == got["device"], "mm_partner_stats and mm_partners over every slot differ"
+            assert got["stats"] == got["host"], "mm_partner_stats and the host route differ"
+    m = {r: med(t[r]) for r in routes}
+    print("partner_stats: %s" % {r: round(v, 3) for r, v in m.items()}, file=sys.stderr, flush=True)
+    out = {"waiting": int(waiting.size), "groups": G, "window": 25, "flags": "region filter",
+           "partner_stats_call_ms": spread(t["stats"]), "partners_every_slot_route_ms": spread(t["device"]),
+           "partners_every_slot_call_ms": spread(t["device_call"]), "host_route_ms": spread(t["host"]),
+           "host_route_tables_ms": spread(t["host_tables"]), "after_host_drain_ms": spread(t["drain"]),
+           "partner_stats_over_partners_route": m["stats"] / m["device"], "partner_stats_over_host_route": m["stats"] / m["host"],
+           "partner_stats_beats_both": bool(m["stats"] < m["device"] and m["stats"] < m["host"]),
+           "records": got["stats"],
+           "note": "host time around the calls, the wrapper's numpy buffers included; %d players waiting in %d queues, %d cancelled "
+                   "and not yet purged, capacity %d; all three routes produce the same records (checked every step); both other "
+                   "routes include the numpy bucketing of a million (partners, gap) pairs" % (int(waiting.size), G, int(gone.sum()), cap)}
+    if args.partner_stats_trace:
+        out["kernels"] = trace_split(args.partner_stats_trace)
+    return out
+
+
+def partner_stats_trace_run(args):
+    """Nothing but --steps calls of mm_partner_stats on the pool of --partner-stats: what a kernel trace is taken of."""
+    import torch
+    from microservice_matchmaking_amd.synth import make_pool
+    rating, cons = make_pool(args.players, seed=1)
+    eng, _, _ = partner_stats_pool(args, torch.from_numpy(rating).cuda(), torch.from_numpy(cons.view(np.int32)).cuda(), 1)
+    with eng:
+        for _ in range(args.steps):
+            recs = eng.partner_stats(0)
+    print(json.dumps({"calls": args.steps, "waiting": sum(r["waiting"] for r in recs)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
@@ -538,10 +696,20 @@ def main():
     ap.add_argument("--move-if", action="store_true",
                     help="also measure mm_move_if and mm_expire_if beside plain mm_move and the host route they replace (the owner's "
                          "stamp table, mm_partners, a numpy filter, mm_cancel, mm_enqueue_stamped)")
+    ap.add_argument("--partner-stats", action="store_true",
+                    help="also measure mm_partner_stats beside mm_partners over every waiting slot and the host's sorted tables, "
+                         "each with the numpy bucketing it needs")
+    ap.add_argument("--partner-stats-trace", metavar="CSV", default=None,
+                    help="with --partner-stats: the kernel trace (rocprofv3 --kernel-trace, *_kernel_trace.csv) of a "
+                         "--partner-stats-trace-run, for the kernel-by-kernel split of the call")
+    ap.add_argument("--partner-stats-trace-run", action="store_true",
+                    help="only call mm_partner_stats --steps times on the pool of --partner-stats and exit: the run to trace")
     args = ap.parse_args()
     assert args.steps >= 20, "medians of at least 20 steps"
     import torch
     assert torch.cuda.is_available(), "needs a GPU; there is no CPU path"
+    if args.partner_stats_trace_run:
+        return partner_stats_trace_run(args)
     from bench import kernel_source_hash
     from microservice_matchmaking_amd import Engine, make_config, mode_1v1
     from microservice_matchmaking_amd.synth import make_pool
@@ -623,6 +791,7 @@ def main():
     locate = measure_locate(args, d_rating, d_cons, now) if args.locate else None
     partners = measure_partners(args, rating, cons, d_rating, d_cons, now) if args.partners else None
     move_if = measure_move_if(args, rating, cons, d_rating, d_cons, now) if args.move_if else None
+    partner_stats = measure_partner_stats(args, rating, cons, d_rating, d_cons, now) if args.partner_stats else None
 
     bucket = med(rows["off"]["bucket_ms"])
     out = {
@@ -656,6 +825,8 @@ def main():
         out["partners"] = partners
     if move_if is not None:
         out["move_if"] = move_if
+    if partner_stats is not None:
+        out["partner_stats"] = partner_stats
     print(json.dumps(out, indent=1))
     off.close()
     on.close()
