@@ -3484,13 +3484,17 @@ static_assert(sizeof(WaitGroupDev) == sizeof(mm_wait_group) && offsetof(WaitGrou
 // the lookup (d_loc_rows) are sized by it.
 static uint32_t wait_max_chunks(const mm_engine* e) { return (uint32_t)(e->cfg.capacity / WT_CHUNK + e->cfg.n_groups + 1u); }
 
+// A walk's rows — WT_ROWS counters per chunk and, behind them, the total k_wait_scan leaves (wait_total): the bytes of the
+// buffer (d_wt_rows, d_loc_rows and d_fit_rows alike).
+static size_t wait_rows_bytes(const mm_engine* e) { return ((size_t)wait_max_chunks(e) * WT_ROWS + 1u) * sizeof(uint32_t); }
+
 // The device arrays of the feature, at the first mm_clock_set (or a version-2 mm_restore): all six, or none.
 static int wait_alloc(mm_engine* e)
 {
     if (e->d_stamp) return MM_OK;
     const size_t cap = e->cfg.capacity;
     const int rc = guarded([&]() -> int {          // (also a bad_alloc of the registry ends in the clean-up below)
-        MMTRY(dev_alloc(e, e->d_wt_rows, ((size_t)wait_max_chunks(e) * WT_ROWS + 1u) * sizeof(uint32_t)));
+        MMTRY(dev_alloc(e, e->d_wt_rows, wait_rows_bytes(e)));
         MMTRY(dev_alloc(e, e->d_wt_out, 3u * cap * sizeof(uint32_t)));
         MMTRY(dev_alloc(e, e->d_wt_stats, MM_MAX_GROUPS * sizeof(WaitGroupDev)));
         MMTRY(dev_alloc(e, e->d_wt_matched, (cap + (size_t)MM_MAX_LOBBY * MM_MAX_GROUPS + 64u) * sizeof(uint32_t)));
@@ -3525,6 +3529,54 @@ static WaitParams wait_params(const mm_engine* e, uint32_t mode, uint32_t max_ag
     P.out_age = e->d_wt_out + 2u * (size_t)e->cfg.capacity;
     P.stats = e->d_wt_stats;
     return P;
+}
+
+// Where k_wait_scan leaves the total of P's rows.
+static uint32_t* wait_total(const WaitParams& P) { return P.rows + (size_t)P.max_chunks * WT_ROWS; }
+
+// The walk of a read-only query over `mode` (mm_locate, mm_partners, mm_partner_stats): rows of the call's own — the
+// clock's may not exist — no list, no statistics.  `stamp` is the clock's column while the clock is on and NULL while it
+// is off (every age reads 0) — for every such walk, whether its kernels read ages (k_loc_scatter) or not (k_fit_*).
+static WaitParams walk_params(const mm_engine* e, uint32_t mode, uint32_t* rows)
+{
+    WaitParams P = wait_params(e, mode, 0u);
+    P.stamp = e->clock_on ? e->d_stamp : NULL;
+    P.rows = rows;
+    P.out_slot = NULL; P.out_group = NULL; P.out_age = NULL; P.stats = NULL;
+    return P;
+}
+
+// The same walk over another mode's chains.
+static WaitParams walk_over(const mm_engine* e, WaitParams P, uint32_t mode)
+{
+    P.mode = mode;
+    P.teams = e->cfg.modes[mode].teams;
+    return P;
+}
+
+// The constraint-word bits two players must agree in under the filters of a flags word (mm_partners' predicate).
+static uint32_t filter_eqmask(uint32_t flags)
+{
+    return ((flags & MM_MODE_REGION_FILTER) ? (0xFFu << 4) : 0u) | ((flags & MM_MODE_PARTY_FILTER) ? (0xFu << 12) : 0u);
+}
+
+// Per-call scratch that grows with the longest query so far: two buffers a and b, good for `cap` rows.  A call with
+// n <= cap allocates nothing; a longer one gets 1024 rows doubled until n fits, never more than the pool has slots
+// (n <= capacity, and a capacity fits a queue's 32-bit index) — the old buffers are released BEFORE the new ones are
+// allocated, and cap reads 0 in between, so a failure half way leaves nothing that looks usable.
+template <class A, class B>
+static int scratch_grow(mm_engine* e, uint32_t n, uint32_t& cap, A*& a, size_t (*bytes_a)(size_t rows), B*& b, size_t (*bytes_b)(size_t rows))
+{
+    if (n <= cap) return MM_OK;
+    uint32_t want = 1024u;
+    while (want < n) want <<= 1;
+    if (want > e->cfg.capacity) want = e->cfg.capacity;
+    mem_release(e, a); mem_release(e, b);
+    cap = 0;
+    MMTRY(dev_alloc(e, a, bytes_a(want)));
+    MMTRY(dev_alloc(e, b, bytes_b(want)));
+    cap = want;
+    return MM_OK;
 }
 
 // Workgroups for a pass over the mode's chunks, the clock's calls and the lookup's alike: enough for everybody who can be
@@ -3598,6 +3650,23 @@ static int marking_call(mm_engine* e, const char* name, std::initializer_list<ui
     return rc;
 }
 
+// The entry of a read-only query (mm_locate, mm_partners, mm_partner_stats), behind its own argument checks, its
+// MM_ERR_STATE check and the early returns that launch nothing: `body()` runs under `guarded`.  Nothing of the pool is
+// written, so after a failure the engine stays usable; but the call's scratch may be half written (a tag left standing):
+// the stream is waited for and `release()` frees that scratch — the next call starts from zeroed buffers.
+template <class Body, class Release>
+static int query_call(mm_engine* e, const char* name, Body&& body, Release&& release)
+{
+    ON_ENGINE_DEVICE(e);
+    RoctxRange rr(name);
+    const int rc = guarded(body);
+    if (rc != MM_OK) {
+        (void)hipStreamSynchronize(e->stream);
+        release();
+    }
+    return rc;
+}
+
 // How many a count selected: the word at d_total, behind ONE wait on the stream.
 static int read_selected(mm_engine* e, const uint32_t* d_total, uint32_t* k)
 {
@@ -3621,7 +3690,7 @@ static int wait_select(mm_engine* e, const WaitParams& P, uint32_t grid, uint32_
         hipLaunchKernelGGL(k_wait_scatter, dim3(grid), dim3(WT_THREADS), 0, e->stream, P);
         HIPCHK(e, hipGetLastError());
     }
-    return read_selected(e, P.rows + (size_t)P.max_chunks * WT_ROWS, k);
+    return read_selected(e, wait_total(P), k);
 }
 
 // The list of k players on its way to the host, queued: slot, rating group and age from d_wt_out (every scatter writes
@@ -3706,7 +3775,7 @@ static int loc_alloc(mm_engine* e, uint32_t n)
     const size_t cap = e->cfg.capacity;
     return guarded([&]() -> int {
         if (!e->d_loc_tag) {
-            MMTRY(dev_alloc(e, e->d_loc_rows, ((size_t)wait_max_chunks(e) * WT_ROWS + 1u) * sizeof(uint32_t)));   // as wait_alloc sizes d_wt_rows
+            MMTRY(dev_alloc(e, e->d_loc_rows, wait_rows_bytes(e)));
             uint32_t* tag = NULL;
             MMTRY(dev_alloc(e, tag, cap * sizeof(uint32_t)));
             const hipError_t rc = hipMemsetAsync(tag, 0, cap * sizeof(uint32_t), e->stream);
@@ -3717,17 +3786,8 @@ static int loc_alloc(mm_engine* e, uint32_t n)
             }
             e->d_loc_tag = tag;                                // last: its presence says the tags are there and zero
         }
-        if (n > e->loc_cap) {
-            uint32_t want = 1024u;
-            while (want < n) want <<= 1;                       // (n <= capacity, and a capacity fits a queue's 32-bit index)
-            if (want > cap) want = (uint32_t)cap;
-            mem_release(e, e->d_loc_q); mem_release(e, e->d_loc_out);
-            e->loc_cap = 0;
-            MMTRY(dev_alloc(e, e->d_loc_q, (size_t)want * sizeof(uint32_t)));
-            MMTRY(dev_alloc(e, e->d_loc_out, 5u * (size_t)want * sizeof(uint32_t)));
-            e->loc_cap = want;
-        }
-        return MM_OK;
+        return scratch_grow(e, n, e->loc_cap, e->d_loc_q, [](size_t rows) { return rows * sizeof(uint32_t); },
+                            e->d_loc_out, [](size_t rows) { return 5u * rows * sizeof(uint32_t); });
     });
 }
 
@@ -3739,10 +3799,7 @@ static int loc_alloc(mm_engine* e, uint32_t n)
 static int loc_launch(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, bool want_ahead, WaitParams* walk)
 {
     const uint32_t cap = e->cfg.capacity;
-    WaitParams P = wait_params(e, mode, 0u);                   // (stamp == NULL while the clock is off: every age reads 0)
-    P.stamp = e->clock_on ? e->d_stamp : NULL;
-    P.rows = e->d_loc_rows;                                    // the lookup's own rows: the clock's may not exist
-    P.out_slot = NULL; P.out_group = NULL; P.out_age = NULL; P.stats = NULL;
+    const WaitParams P = walk_params(e, mode, e->d_loc_rows);
     LocParams L;
     L.n = n;
     L.stride = e->loc_cap;
@@ -3788,16 +3845,8 @@ extern "C" int mm_locate(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t
         if (!e || mode >= e->cfg.n_modes || (n > 0u && !slots) || n > e->cfg.capacity) return MM_ERR_INVALID_ARG;
         if (e->poisoned) return MM_ERR_STATE;
         if (n == 0u) return MM_OK;
-        ON_ENGINE_DEVICE(e);
-        RoctxRange rr("mm_locate");
-        const int rc = guarded([&]() -> int { return locate_impl(e, mode, n, slots, where, group, position, ahead, age); });
-        if (rc != MM_OK) {
-            // nothing of the pool was written, so the engine stays usable; but a tag may be left standing: the scratch goes,
-            // and the next call starts from zeroed buffers
-            (void)hipStreamSynchronize(e->stream);
-            loc_release(e);
-        }
-        return rc;
+        return query_call(e, "mm_locate", [&]() -> int { return locate_impl(e, mode, n, slots, where, group, position, ahead, age); },
+                          [&]() { loc_release(e); });
     });
 }
 
@@ -3810,18 +3859,32 @@ static void par_release(mm_engine* e)
 
 static int par_alloc(mm_engine* e, uint32_t n)
 {
-    if (n <= e->par_cap) return MM_OK;
-    const size_t cap = e->cfg.capacity;
     return guarded([&]() -> int {
-        uint32_t want = 1024u;
-        while (want < n) want <<= 1;                           // (n <= capacity, as in loc_alloc)
-        if (want > cap) want = (uint32_t)cap;
-        par_release(e);
-        MMTRY(dev_alloc(e, e->d_par_rec, (size_t)want * sizeof(uint4)));
-        MMTRY(dev_alloc(e, e->d_par_out, (2u + MM_MAX_ROLES) * (size_t)want * sizeof(uint32_t)));
-        e->par_cap = want;
-        return MM_OK;
+        return scratch_grow(e, n, e->par_cap, e->d_par_rec, [](size_t rows) { return rows * sizeof(uint4); },
+                            e->d_par_out, [](size_t rows) { return (2u + MM_MAX_ROLES) * rows * sizeof(uint32_t); });
     });
+}
+
+// What mm_partners and the rule calls hand k_par_count*: n query records in d_par_rec counted into d_par_out (par_alloc's,
+// par_cap rows) under the predicate of `window` and `flags`; the lookup's fields are the caller's.  *count_grid: `grid`
+// workgroups stride over the chunks, and as many times that over the query tiles as keeps the whole near 2048 workgroups
+// — a short queue with many queries spreads over the tiles, a long one keeps its registers.
+static ParParams par_params(const mm_engine* e, uint32_t n, uint32_t window, uint32_t flags, uint32_t grid, uint32_t* count_grid)
+{
+    ParParams Q;
+    memset(&Q, 0, sizeof(Q));
+    Q.n = n;
+    Q.stride = e->par_cap;
+    Q.gx = grid;
+    Q.window = window;
+    Q.eqmask = filter_eqmask(flags);
+    Q.q_rating = e->d_q_rating;
+    Q.q_cons = e->d_q_cons;
+    Q.rec = e->d_par_rec;
+    Q.out = e->d_par_out;
+    const uint32_t n_tiles = (n + PAR_QTILE - 1u) / PAR_QTILE, room = 2048u / grid ? 2048u / grid : 1u;
+    *count_grid = grid * (n_tiles < room ? n_tiles : room);
+    return Q;
 }
 
 static int partners_impl(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags, uint32_t n,
@@ -3831,28 +3894,13 @@ static int partners_impl(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t
     MMTRY(par_alloc(e, n));
     WaitParams P;                                              // the lookup: mm_locate's passes, `ahead` off
     MMTRY(loc_launch(e, mode, n, slots, false, &P));
-    WaitParams C = P;                                          // the count: the same walk over in_mode's chains
-    C.mode = in_mode;
-    C.teams = e->cfg.modes[in_mode].teams;
-    ParParams Q;
-    Q.n = n;
-    Q.stride = e->par_cap;
-    Q.window = window;
-    Q.eqmask = ((flags & MM_MODE_REGION_FILTER) ? (0xFFu << 4) : 0u) | ((flags & MM_MODE_PARTY_FILTER) ? (0xFu << 12) : 0u);
+    const WaitParams C = walk_over(e, P, in_mode);             // the count: the same walk over in_mode's chains
+    uint32_t count_grid = 0;
+    ParParams Q = par_params(e, n, window, flags, wait_grid(e), &count_grid);
     Q.loc_stride = e->loc_cap;
     Q.q = e->d_loc_q;
     Q.loc = e->d_loc_out;
-    Q.q_rating = e->d_q_rating;
-    Q.q_cons = e->d_q_cons;
-    Q.rec = e->d_par_rec;
-    Q.out = e->d_par_out;
-    const uint32_t grid = wait_grid(e);
-    // the count's grid: `grid` workgroups stride over the chunks, and as many times that over the query tiles as keeps the
-    // whole near 2048 workgroups — a short queue with many queries spreads over the tiles, a long one keeps its registers
-    const uint32_t n_tiles = (n + PAR_QTILE - 1u) / PAR_QTILE, room = 2048u / grid ? 2048u / grid : 1u;
-    Q.gx = grid;
-    const uint32_t gy = n_tiles < room ? n_tiles : room;
-    const dim3 per_query((n + WT_THREADS - 1u) / WT_THREADS), wg(WT_THREADS), cg(grid * gy);
+    const dim3 per_query((n + WT_THREADS - 1u) / WT_THREADS), wg(WT_THREADS), cg(count_grid);
     hipLaunchKernelGGL(k_par_gather, per_query, wg, 0, e->stream, P, Q);
     if (by_role && gap) hipLaunchKernelGGL(k_par_count_all, cg, wg, 0, e->stream, C, Q);
     else if (by_role) hipLaunchKernelGGL(k_par_count_role, cg, wg, 0, e->stream, C, Q);
@@ -3879,17 +3927,9 @@ extern "C" int mm_partners(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32
             return MM_ERR_INVALID_ARG;
         if (e->poisoned) return MM_ERR_STATE;
         if (n == 0u || (!partners && !by_role && !gap)) return MM_OK;   // nothing asked for: nothing is launched
-        ON_ENGINE_DEVICE(e);
-        RoctxRange rr("mm_partners");
-        const int rc = guarded([&]() -> int { return partners_impl(e, mode, in_mode, window, flags, n, slots, partners, by_role, gap); });
-        if (rc != MM_OK) {
-            // as in mm_locate: nothing of the pool was written, the engine stays usable; a tag may be left standing, so the
-            // lookup's scratch goes with this call's buffers and the next call starts afresh
-            (void)hipStreamSynchronize(e->stream);
-            loc_release(e);
-            par_release(e);
-        }
-        return rc;
+        return query_call(e, "mm_partners",
+                          [&]() -> int { return partners_impl(e, mode, in_mode, window, flags, n, slots, partners, by_role, gap); },
+                          [&]() { loc_release(e); par_release(e); });   // (the lookup's scratch goes with this call's buffers)
     });
 }
 
@@ -3914,23 +3954,13 @@ static uint32_t fit_tiles_of(uint32_t n) { return (n + FIT_TILE - 1u) / FIT_TILE
 
 static int fit_alloc(mm_engine* e, uint32_t n)
 {
-    const size_t cap = e->cfg.capacity;
     return guarded([&]() -> int {
         if (!e->d_fit_stats) {
-            MMTRY(dev_alloc(e, e->d_fit_rows, ((size_t)wait_max_chunks(e) * WT_ROWS + 1u) * sizeof(uint32_t)));   // as wait_alloc sizes d_wt_rows
+            MMTRY(dev_alloc(e, e->d_fit_rows, wait_rows_bytes(e)));
             MMTRY(dev_alloc(e, e->d_fit_stats, MM_MAX_GROUPS * sizeof(FitGroupDev)));
         }
-        if (n > e->fit_cap) {
-            uint32_t want = 1024u;
-            while (want < n) want <<= 1;                       // (n <= capacity, as in loc_alloc)
-            if (want > cap) want = (uint32_t)cap;
-            mem_release(e, e->d_fit_keys); mem_release(e, e->d_fit_hist);
-            e->fit_cap = 0;
-            MMTRY(dev_alloc(e, e->d_fit_keys, 2u * (size_t)want * sizeof(unsigned long long)));
-            MMTRY(dev_alloc(e, e->d_fit_hist, (size_t)FIT_DIGITS * (fit_tiles_of(want) + 1u) * sizeof(uint32_t)));
-            e->fit_cap = want;
-        }
-        return MM_OK;
+        return scratch_grow(e, n, e->fit_cap, e->d_fit_keys, [](size_t rows) { return 2u * rows * sizeof(unsigned long long); },
+                            e->d_fit_hist, [](size_t rows) { return (size_t)FIT_DIGITS * (fit_tiles_of((uint32_t)rows) + 1u) * sizeof(uint32_t); });
     });
 }
 
@@ -3940,22 +3970,17 @@ static int partner_stats_impl(mm_engine* e, uint32_t mode, uint32_t in_mode, uin
     // the table holds waiting players of one mode: never more than are queued in all of them, never more than there are slots
     const uint32_t bound = (uint32_t)(e->live_upper < cap ? e->live_upper : cap);
     MMTRY(fit_alloc(e, bound));
-    WaitParams C = wait_params(e, in_mode, 0u);                // the candidates' walk
-    C.stamp = NULL;
-    C.rows = e->d_fit_rows;                                    // rows of the call's own: the clock's and the lookup's may not exist
-    C.out_slot = NULL; C.out_group = NULL; C.out_age = NULL; C.stats = NULL;
-    WaitParams Q = C;                                          // the queries' walk
-    Q.mode = mode;
-    Q.teams = e->cfg.modes[mode].teams;
+    const WaitParams C = walk_params(e, in_mode, e->d_fit_rows);   // the candidates' walk (rows of the call's own: the lookup's may not exist either)
+    const WaitParams Q = walk_over(e, C, mode);                // the queries' walk
     FitParams F;
     memset(&F, 0, sizeof(F));
     F.window = window;
-    F.eqmask = ((flags & MM_MODE_REGION_FILTER) ? (0xFFu << 4) : 0u) | ((flags & MM_MODE_PARTY_FILTER) ? (0xFu << 12) : 0u);   // as partners_impl
+    F.eqmask = filter_eqmask(flags);
     F.self = in_mode == mode ? 1u : 0u;
     F.key_cap = e->fit_cap;
     F.q_rating = e->d_q_rating;
     F.q_cons = e->d_q_cons;
-    F.n_keys = e->d_fit_rows + (size_t)C.max_chunks * WT_ROWS;
+    F.n_keys = wait_total(C);
     F.hist = e->d_fit_hist;
     F.stats = e->d_fit_stats;
     unsigned long long* half[2] = { e->d_fit_keys, e->d_fit_keys + e->fit_cap };
@@ -3999,14 +4024,8 @@ extern "C" int mm_partner_stats(mm_engine* e, uint32_t mode, uint32_t in_mode, u
             memset(per_group, 0, e->cfg.n_groups * sizeof(mm_partner_group));
             return MM_OK;
         }
-        ON_ENGINE_DEVICE(e);
-        RoctxRange rr("mm_partner_stats");
-        const int rc = guarded([&]() -> int { return partner_stats_impl(e, mode, in_mode, window, flags, per_group); });
-        if (rc != MM_OK) {                                     // as in mm_locate: nothing of the pool was written, the engine stays usable
-            (void)hipStreamSynchronize(e->stream);
-            fit_release(e);
-        }
-        return rc;
+        return query_call(e, "mm_partner_stats", [&]() -> int { return partner_stats_impl(e, mode, in_mode, window, flags, per_group); },
+                          [&]() { fit_release(e); });
     });
 }
 
@@ -4199,22 +4218,9 @@ static int rule_rank(mm_engine* e, const WaitParams& P, uint32_t grid, uint32_t 
     C.cnt = e->d_par_out;
     C.age = e->d_par_out + stride;
     C.n = k1;
-    WaitParams W = P;                                          // the count: the same walk over in_mode's chains
-    W.mode = rule.in_mode;
-    W.teams = e->cfg.modes[rule.in_mode].teams;
-    ParParams Q;
-    memset(&Q, 0, sizeof(Q));
-    Q.n = k1;
-    Q.stride = e->par_cap;
-    Q.window = rule.window;
-    Q.eqmask = ((rule.flags & MM_MODE_REGION_FILTER) ? (0xFFu << 4) : 0u) | ((rule.flags & MM_MODE_PARTY_FILTER) ? (0xFu << 12) : 0u);
-    Q.q_rating = e->d_q_rating;
-    Q.q_cons = e->d_q_cons;
-    Q.rec = e->d_par_rec;
-    Q.out = e->d_par_out;
-    const uint32_t n_tiles = (k1 + PAR_QTILE - 1u) / PAR_QTILE, room = 2048u / grid ? 2048u / grid : 1u;   // as partners_impl
-    Q.gx = grid;
-    const uint32_t gy = n_tiles < room ? n_tiles : room;
+    const WaitParams W = walk_over(e, P, rule.in_mode);        // the count: the same walk over in_mode's chains
+    uint32_t count_grid = 0;
+    const ParParams Q = par_params(e, k1, rule.window, rule.flags, grid, &count_grid);
     memset(S, 0, sizeof(*S));
     S->n = k1;
     S->capacity = e->cfg.capacity;
@@ -4231,7 +4237,7 @@ static int rule_rank(mm_engine* e, const WaitParams& P, uint32_t grid, uint32_t 
     S->out_age = P.out_age;
     const dim3 wg(WT_THREADS), per_cand((k1 + SEL_TILE - 1u) / SEL_TILE), tile(SEL_TILE);
     hipLaunchKernelGGL(k_cand_scatter, dim3(grid), wg, 0, e->stream, P, src, C);
-    hipLaunchKernelGGL(k_par_count, dim3(grid * gy), wg, 0, e->stream, W, Q);
+    hipLaunchKernelGGL(k_par_count, dim3(count_grid), wg, 0, e->stream, W, Q);
     hipLaunchKernelGGL(k_sel_count, per_cand, tile, 0, e->stream, *S);
     hipLaunchKernelGGL(k_sel_scan, dim3(1), wg, 0, e->stream, *S);
     HIPCHK(e, hipGetLastError());

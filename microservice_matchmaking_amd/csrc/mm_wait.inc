@@ -1,13 +1,21 @@
 // mm_wait.inc — the clock of include/mm_wait.h on the device: expiry selection as a stable stream compaction over a
 // mode's queues, the same selection gathering the rows of a move into another mode (mm_move), the rotation of blocked
-// lobbies' seats to their queues' tails (mm_rotate), wait statistics, a slot's place in its queue (mm_locate, k_loc_* at the end).  Included by mm_engine.hip (ChainDev, LobbyDev, dev_min_u32, wave_incl_scan, the WT_* chunk geometry); the host
-// functions that launch these kernels (wait_alloc .. mm_wait_stats) are there, like the pair and team host loops.
-// k_wait_matched sits beside k_pack_results in mm_engine.hip, whose PackArgs it shares.  DESIGN.md §4.6.
+// lobbies' seats to their queues' tails (mm_rotate), wait statistics, a slot's place in its queue (mm_locate), the partner
+// counts of mm_partners and mm_partner_stats.  Included by mm_engine.hip (ChainDev, LobbyDev, dev_min_u32, wave_incl_scan,
+// the WT_* chunk geometry); the host functions that launch these kernels (wait_alloc .. mm_wait_stats) are there, like the
+// pair and team host loops.  k_wait_matched sits beside k_pack_results in mm_engine.hip, whose PackArgs it shares.  DESIGN.md §4.6.
 //
 // The waiting players of a mode are walked in ONE order by every kernel here — rating group ascending; within a group
 // the stored lobby's seats as mm_lobby_state lists them, then the queue from head to tail — cut into chunks of WT_CHUNK
 // queue entries, one workgroup per chunk (a chain of 300 000 players is 147 workgroups, not k_purge's one).  A group
 // has at least one chunk: an empty queue may still have a stored lobby, and the group's first chunk carries its seats.
+// The walk is written once, in the first part of this file, and every kernel that walks is made of its pieces:
+//   WaitChunk / wait_chunk   where a workgroup's chunk lies: group, queue, the chunk's rows;
+//   wait_load<COLS>          a wave's WT_PER_WAVE queue entries into registers: the streamed columns, then the gathers;
+//   wait_seat, wait_live     the lane's seat of the stored lobby (wave 0 of a group's first chunk), and "does it wait?";
+//   wait_count_body          per-wave counts into the chunk's rows (k_wait_count, k_loc_count, k_fit_count);
+//   wait_rank                a selected lane's place behind the wave's base — the stable compactions;
+//   wait_wave_sum / wait_wave_max / wait_wave_sum64, wait_bucket   what the two statistics kernels reduce with.
 // mm_expire is count / scan / scatter over that order, the shape of k_bucket_*: per-wave counts, one exclusive scan
 // down the (chunk, wave) rows, then every wave writes its selected entries at base + wave-ballot rank — a stable
 // compaction, so the list is in queue order.  Per entry: q_slot streamed, stamp[slot] and state[slot] gathered.
@@ -44,58 +52,203 @@ struct WaitParams {
 
 static __device__ __forceinline__ uint32_t wait_chunks_of(uint32_t len) { return len ? (len + WT_CHUNK - 1u) / WT_CHUNK : 1u; }
 
-// Chunk b of the mode -> its rating group, the chunk's number inside the group and the queue's length.  false: past the
-// last chunk.  The same for every thread of a workgroup.
-static __device__ __forceinline__ bool wait_chunk(const WaitParams& P, uint32_t b, uint32_t& g, uint32_t& k, uint32_t& len)
+// ---- the walk's pieces ----
+
+// Where chunk b of the mode lies: four words, the same for all threads of the workgroup (scalar registers).  The addresses
+// are derived from them where they are used and not kept: held across a kernel's inner loops they cost k_par_count_all
+// two spilled SGPRs and k_fit_search its eighth wave.
+struct WaitChunk {
+    uint32_t b, g, k, len;                    // the chunk; its rating group, its number inside the group, the queue's length
+    // the queue's first entry in q_slot / q_rating / q_cons
+    __device__ __forceinline__ size_t qo(const WaitParams& P) const { return (size_t)(P.mode * P.n_groups + g) * P.capacity; }
+    // the chunk's counters: [0] the seats', [1 + wave] a wave's; and those of the group's first chunk
+    __device__ __forceinline__ uint32_t* row(const WaitParams& P) const { return P.rows + (size_t)b * WT_ROWS; }
+    __device__ __forceinline__ const uint32_t* group_row(const WaitParams& P) const { return P.rows + (size_t)(b - k) * WT_ROWS; }
+    // the group's stored lobby
+    __device__ __forceinline__ const LobbyDev& lobby(const WaitParams& P) const { return P.chains[P.mode * P.n_groups + g].lobby; }
+    // the wave's first entry; does the wave carry the seats' row?
+    __device__ __forceinline__ uint32_t first(int wave) const { return k * WT_CHUNK + (uint32_t)wave * WT_PER_WAVE; }
+    __device__ __forceinline__ bool seats(int wave) const { return wave == 0 && k == 0u; }
+};
+
+// The wave's number as a scalar: its first entry, its row and whether it carries the seats then cost no vector register
+// and no lane mask.
+static __device__ __forceinline__ int wait_wave() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+// false: b is past the mode's last chunk.
+static __device__ __forceinline__ bool wait_chunk(const WaitParams& P, uint32_t b, WaitChunk& c)
 {
     if (b >= P.max_chunks) return false;
     uint32_t base = 0;
-    for (g = 0; g < P.n_groups; ++g) {
-        len = dev_min_u32(P.chains[P.mode * P.n_groups + g].len, P.capacity);
-        const uint32_t nb = wait_chunks_of(len);
-        if (b < base + nb) { k = b - base; return true; }
+    c.b = b;
+    for (c.g = 0; c.g < P.n_groups; ++c.g) {
+        c.len = dev_min_u32(P.chains[P.mode * P.n_groups + c.g].len, P.capacity);
+        const uint32_t nb = wait_chunks_of(c.len);
+        if (b < base + nb) { c.k = b - base; return true; }
         base += nb;
     }
     return false;
 }
 
-// The idx-th seated player of a stored lobby in mm_lobby_state's order (team by team), MM_NO_SLOT past the last.
-static __device__ __forceinline__ uint32_t wait_seat(const LobbyDev& lb, uint32_t teams, uint32_t idx)
+// The (team, seat) of the idx-th seated player of a stored lobby in mm_lobby_state's order (team by team); false past the last.
+static __device__ __forceinline__ bool wait_seat_at(const LobbyDev& lb, uint32_t teams, uint32_t idx, uint32_t& t, uint32_t& i)
 {
-    for (uint32_t t = 0; t < teams && t < MM_MAX_TEAMS; ++t) {
+    for (t = 0; t < teams && t < MM_MAX_TEAMS; ++t) {
         const uint32_t c = dev_min_u32(lb.cnt[t], 8u);
-        if (idx < c) return lb.slot[t][idx];
+        if (idx < c) { i = idx; return true; }
         idx -= c;
     }
-    return MM_NO_SLOT;
+    return false;
 }
 
-// Is the player in `sl` waiting (LIVE: not cancelled, not expired before), and for how long?
+// Lane `lane`'s seat of the chunk's stored lobby as the LobbyDev record holds it: slot, rating, constraint word.  MM_NO_SLOT
+// in a chunk that is not its group's first and past the last seat (a lobby seats at most WT_SEATS).  What a caller does
+// not read is not loaded.
+struct WaitSeat {
+    uint32_t sl, cn;
+    int32_t rt;
+};
+
+static __device__ __forceinline__ WaitSeat wait_seat(const WaitParams& P, const WaitChunk& c, int lane)
+{
+    WaitSeat s;
+    s.sl = MM_NO_SLOT; s.cn = 0u; s.rt = 0;
+    uint32_t t = 0, i = 0;
+    if (c.k == 0u && (uint32_t)lane < WT_SEATS && wait_seat_at(c.lobby(P), P.teams, (uint32_t)lane, t, i)) {
+        s.sl = c.lobby(P).slot[t][i];
+        s.rt = c.lobby(P).rating[t][i];
+        s.cn = c.lobby(P).cons[t][i];
+    }
+    return s;
+}
+
+// Is the player in `sl` waiting (LIVE: not cancelled, not expired before) ...
+static __device__ __forceinline__ bool wait_live(const WaitParams& P, uint32_t sl) { return sl < P.capacity && P.state[sl] == MM_ST_LIVE; }
+
+// ... and for how long?
 static __device__ __forceinline__ bool wait_age(const WaitParams& P, uint32_t sl, uint32_t& age)
 {
-    if (sl >= P.capacity || P.state[sl] != MM_ST_LIVE) return false;
+    if (!wait_live(P, sl)) return false;
     age = P.now - P.stamp[sl];
     return true;
 }
 
-// A wave's WT_PER_WAVE queue entries from w0 on: the slots, then their ages — every load of a level issued before the
-// first one is used (the gathers are latency, not bandwidth).  Bit r of the result: this lane's entry r is waiting.
+// The selection by age, of the count and of every scatter: strictly older than the threshold.
+static __device__ __forceinline__ bool wait_older(const WaitParams& P, uint32_t age) { return age > P.max_age; }
+
+// A wave's WT_PER_WAVE queue entries from w0 on, in registers.  COLS says what is read beside the slots: WL_ROW streams the
+// entry's rating and constraint word with them (q_rating, q_cons), WL_AGE gathers stamp[slot] (age = now - stamp; it means
+// something for a LIVE entry only), WL_TAG gathers tag[slot]; a column left out reads 0.  state[slot] is always gathered.
+// Two levels — the streamed columns, then the gathers — and every load of a level is issued before the first one is used
+// (the gathers are latency, not bandwidth).  Bit r of the result: this lane's entry r is LIVE.  Row WT_ITERS of the
+// streamed columns is nobody's entry: k_fit_search keeps the seat there.
 #define WT_ITERS (WT_PER_WAVE / 64)
-static __device__ __forceinline__ uint32_t wait_load(const WaitParams& P, size_t qo, uint32_t w0, uint32_t len, int lane,
-                                                     uint32_t (&sl)[WT_ITERS], uint32_t (&age)[WT_ITERS])
+#define WL_ROW 1u
+#define WL_AGE 2u
+#define WL_TAG 4u
+struct WaitRows {
+    uint32_t sl[WT_ITERS + 1], cn[WT_ITERS + 1];
+    int32_t rt[WT_ITERS + 1];
+    uint32_t age[WT_ITERS], tg[WT_ITERS];
+};
+
+template <uint32_t COLS>
+static __device__ __forceinline__ uint32_t wait_load(const WaitParams& P, const WaitChunk& c, uint32_t w0, int lane, WaitRows& R,
+                                                     const int32_t* __restrict__ q_rating = nullptr,
+                                                     const uint32_t* __restrict__ q_cons = nullptr,
+                                                     const uint32_t* __restrict__ tag = nullptr)
 {
-    uint32_t live = 0;
+    const size_t qo = c.qo(P);
 #pragma unroll
     for (uint32_t r = 0; r < WT_ITERS; ++r) {
         const uint32_t i = w0 + r * 64 + lane;
-        sl[r] = i < len ? P.q_slot[qo + i] : MM_NO_SLOT;
+        const bool in = i < c.len;
+        R.sl[r] = in ? P.q_slot[qo + i] : MM_NO_SLOT;
+        R.rt[r] = (COLS & WL_ROW) && in ? q_rating[qo + i] : 0;
+        R.cn[r] = (COLS & WL_ROW) && in ? q_cons[qo + i] : 0u;
     }
+    uint8_t st[WT_ITERS];
 #pragma unroll
     for (uint32_t r = 0; r < WT_ITERS; ++r) {
-        age[r] = 0;
-        if (wait_age(P, sl[r], age[r])) live |= 1u << r;
+        const bool in = R.sl[r] < P.capacity;
+        st[r] = in ? P.state[R.sl[r]] : (uint8_t)MM_ST_FREE;
+        R.age[r] = (COLS & WL_AGE) && in ? P.stamp[R.sl[r]] : P.now;
+        R.tg[r] = (COLS & WL_TAG) && in ? tag[R.sl[r]] : 0u;
+    }
+    uint32_t live = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < WT_ITERS; ++r) {
+        if (st[r] == MM_ST_LIVE) live |= 1u << r;
+        R.age[r] = P.now - R.age[r];
     }
     return live;
+}
+
+// Where a selected lane writes in a stable compaction: `base` plus the selected lanes below it (lt: the lanes below this
+// one); base moves on behind the wave's selected.  Every lane of the wave must call it (ballot).
+static __device__ __forceinline__ uint32_t wait_rank(bool sel, unsigned long long lt, uint32_t& base)
+{
+    const unsigned long long m = __ballot(sel);
+    const uint32_t at = base + (uint32_t)__popcll(m & lt);
+    base += (uint32_t)__popcll(m);
+    return at;
+}
+
+// A value over the wave, in every lane: a butterfly of shuffles.
+static __device__ __forceinline__ uint32_t wait_wave_sum(uint32_t v, int lane)
+{
+    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl((int)v, lane ^ d);
+    return v;
+}
+
+static __device__ __forceinline__ uint32_t wait_wave_max(uint32_t v, int lane)
+{
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t o = (uint32_t)__shfl((int)v, lane ^ d);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+static __device__ __forceinline__ unsigned long long wait_wave_sum64(unsigned long long v, int lane)
+{
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane ^ d), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane ^ d);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+// The bucket of MM_WAIT_HIST and MM_PARTNER_HIST: 0 for 0, else the value's bit length.
+static __device__ __forceinline__ uint32_t wait_bucket(uint32_t v) { return v ? 32u - (uint32_t)__builtin_clz(v) : 0u; }
+
+// The count of a count / scan / scatter: how many of a wave's entries are selected into row[1 + wave], how many of the
+// seats into row[0].  Selected: LIVE, and (OLDER) older than P.max_age.  SEATS false: the seats' row counts 0.
+template <bool OLDER, bool SEATS>
+static __device__ __forceinline__ void wait_count_body(const WaitParams& P)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = wait_wave();
+    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
+        WaitChunk c;
+        if (!wait_chunk(P, b, c)) return;
+        const uint32_t w0 = c.first(wave);
+        uint32_t cnt = 0;
+        if (w0 < c.len) {
+            WaitRows R;
+            const uint32_t live = wait_load<OLDER ? WL_AGE : 0u>(P, c, w0, lane, R);
+#pragma unroll
+            for (uint32_t r = 0; r < WT_ITERS; ++r)
+                cnt += (uint32_t)__popcll(__ballot(((live >> r) & 1u) && (!OLDER || wait_older(P, R.age[r]))));
+        }
+        if (lane == 0) c.row(P)[1 + wave] = cnt;
+        if (wave == 0) {
+            uint32_t age = 0;
+            const uint32_t sl = SEATS ? wait_seat(P, c, lane).sl : MM_NO_SLOT;
+            const bool sel = OLDER ? wait_age(P, sl, age) && wait_older(P, age) : wait_live(P, sl);
+            const unsigned long long m = __ballot(sel);
+            if (lane == 0) c.row(P)[0] = (uint32_t)__popcll(m);
+        }
+    }
 }
 
 __global__ __launch_bounds__(WT_THREADS) void k_wait_fill(uint32_t n, uint32_t* __restrict__ stamp, uint32_t now)
@@ -104,32 +257,7 @@ __global__ __launch_bounds__(WT_THREADS) void k_wait_fill(uint32_t n, uint32_t* 
     if (i < n) stamp[i] = now;
 }
 
-__global__ __launch_bounds__(WT_THREADS) void k_wait_count(WaitParams P)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
-        uint32_t cnt = 0;
-        if (w0 < len) {
-            uint32_t sl[WT_ITERS], age[WT_ITERS];
-            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
-#pragma unroll
-            for (uint32_t r = 0; r < WT_ITERS; ++r)
-                cnt += (uint32_t)__popcll(__ballot(((live >> r) & 1u) && age[r] > P.max_age));
-        }
-        if (lane == 0) P.rows[(size_t)b * WT_ROWS + 1u + wave] = cnt;
-        if (wave == 0) {
-            uint32_t age = 0;
-            const bool sel = k == 0u && (uint32_t)lane < WT_SEATS &&
-                             wait_age(P, wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane), age) && age > P.max_age;
-            const unsigned long long m = __ballot(sel);
-            if (lane == 0) P.rows[(size_t)b * WT_ROWS] = (uint32_t)__popcll(m);
-        }
-    }
-}
+__global__ __launch_bounds__(WT_THREADS) void k_wait_count(WaitParams P) { wait_count_body<true, true>(P); }
 
 // Exclusive scan down n_rows counters, in place; the total goes to *total.  One workgroup; every thread must call it.
 static __device__ __forceinline__ void rows_scan_body(uint32_t* __restrict__ rows, uint32_t n_rows, uint32_t* __restrict__ total_out)
@@ -179,17 +307,6 @@ struct MoveCols {
     uint32_t keep, to_mode;
 };
 
-// The (team, seat) of the idx-th seated player of a stored lobby, in wait_seat's order; false past the last.
-static __device__ __forceinline__ bool wait_seat_at(const LobbyDev& lb, uint32_t teams, uint32_t idx, uint32_t& t, uint32_t& i)
-{
-    for (t = 0; t < teams && t < MM_MAX_TEAMS; ++t) {
-        const uint32_t c = dev_min_u32(lb.cnt[t], 8u);
-        if (idx < c) { i = idx; return true; }
-        idx -= c;
-    }
-    return false;
-}
-
 // What the non-marking scatter of the mm_*_if calls writes at a candidate's rank instead of the list: the query record
 // par_count_body stages (x rating | y constraint word, un-rewritten | z rating group | w slot), the age the selection
 // computed, and the partner count preset to 0.  n: the candidates the columns have room for.
@@ -203,89 +320,62 @@ struct CandCols {
 // Every selected player at its rank, and marked as k_cancel marks a slot.  A slot is in one queue or one lobby, once:
 // the mark a thread sets is read by nobody else, so the selection is the one k_wait_count counted.
 // GATHER (mm_move): the selected player's row goes along — a queue entry's rating and constraint word from the position
-// the wave streams anyway (loaded with the slots, before the gathers of wait_load are waited for), a lobby seat's from
-// the LobbyDev record; the stamp is the clock minus the age the selection computed.
+// the wave streams anyway (wait_load's WL_ROW), a lobby seat's from the LobbyDev record; the stamp is the clock minus the
+// age the selection computed.
 // CAND (mm_expire_if, mm_move_if, mm_move_out_if): the same selection at the same ranks, but NOTHING is marked and no
 // list is written — the row goes into C as a query record for the partner count; state[] is only read.
+// wait_scatter_put: one selected player of rating group g, from a queue or from a seat, to rank `at`.
+template <bool GATHER, bool CAND>
+static __device__ __forceinline__ void wait_scatter_put(const WaitParams& P, const MoveCols& M, const CandCols& C, uint32_t at, uint32_t g,
+                                                        uint32_t sl, int32_t rt, uint32_t cn, uint32_t age)
+{
+    if (CAND) {
+        if (at >= C.n) return;
+        C.rec[at] = make_uint4((uint32_t)rt, cn, g, sl);
+        C.age[at] = age;
+        C.cnt[at] = 0u;
+        return;
+    }
+    if (at >= P.capacity) return;
+    P.out_slot[at] = sl;
+    P.out_group[at] = g;
+    P.out_age[at] = age;
+    if (GATHER) {
+        M.rating[at] = rt;
+        M.cons[at] = (cn & M.keep) | M.to_mode;
+        M.group[at] = (uint8_t)g;
+        M.stamp[at] = P.now - age;
+    }
+    P.state[sl] = MM_ST_CANCELLED;
+}
+
 template <bool GATHER, bool CAND>
 static __device__ __forceinline__ void wait_scatter_body(const WaitParams& P, const MoveCols& M, const CandCols& C)
 {
-    constexpr bool ROWS = GATHER || CAND;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr uint32_t COLS = GATHER || CAND ? WL_AGE | WL_ROW : WL_AGE;
+    const int tid = threadIdx.x, lane = tid & 63, wave = wait_wave();
     const unsigned long long lt = (1ull << lane) - 1ull;
     for (uint32_t b = blockIdx.x;; b += gridDim.x) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
-        uint32_t base = P.rows[(size_t)b * WT_ROWS + 1u + wave];
-        if (w0 < len) {
-            uint32_t sl[WT_ITERS], age[WT_ITERS];
-            int32_t rt[WT_ITERS];
-            uint32_t cn[WT_ITERS];
-            if (ROWS) {
-#pragma unroll
-                for (uint32_t r = 0; r < WT_ITERS; ++r) {
-                    const uint32_t i = w0 + r * 64 + lane;
-                    rt[r] = i < len ? M.q_rating[qo + i] : 0;
-                    cn[r] = i < len ? M.q_cons[qo + i] : 0u;
-                }
-            }
-            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
+        WaitChunk c;
+        if (!wait_chunk(P, b, c)) return;
+        const uint32_t w0 = c.first(wave);
+        uint32_t base = c.row(P)[1 + wave];
+        if (w0 < c.len) {
+            WaitRows R;
+            const uint32_t live = wait_load<COLS>(P, c, w0, lane, R, M.q_rating, M.q_cons);
 #pragma unroll
             for (uint32_t r = 0; r < WT_ITERS; ++r) {
-                const bool sel = ((live >> r) & 1u) && age[r] > P.max_age;
-                const unsigned long long m = __ballot(sel);
-                const uint32_t at = base + (uint32_t)__popcll(m & lt);
-                if (CAND) {
-                    if (sel && at < C.n) {
-                        C.rec[at] = make_uint4((uint32_t)rt[r], cn[r], g, sl[r]);
-                        C.age[at] = age[r];
-                        C.cnt[at] = 0u;
-                    }
-                } else if (sel && at < P.capacity) {
-                    P.out_slot[at] = sl[r];
-                    P.out_group[at] = g;
-                    P.out_age[at] = age[r];
-                    if (GATHER) {
-                        M.rating[at] = rt[r];
-                        M.cons[at] = (cn[r] & M.keep) | M.to_mode;
-                        M.group[at] = (uint8_t)g;
-                        M.stamp[at] = P.now - age[r];
-                    }
-                    P.state[sl[r]] = MM_ST_CANCELLED;
-                }
-                base += (uint32_t)__popcll(m);
+                const bool sel = ((live >> r) & 1u) && wait_older(P, R.age[r]);
+                const uint32_t at = wait_rank(sel, lt, base);
+                if (sel) wait_scatter_put<GATHER, CAND>(P, M, C, at, c.g, R.sl[r], R.rt[r], R.cn[r], R.age[r]);
             }
         }
         if (wave == 0) {
-            const LobbyDev& lb = P.chains[P.mode * P.n_groups + g].lobby;
-            uint32_t age = 0, sl = MM_NO_SLOT, t = 0, i = 0;
-            if (k == 0u && (uint32_t)lane < WT_SEATS) {
-                if (!ROWS) sl = wait_seat(lb, P.teams, (uint32_t)lane);
-                else if (wait_seat_at(lb, P.teams, (uint32_t)lane, t, i)) sl = lb.slot[t][i];
-            }
-            const bool sel = wait_age(P, sl, age) && age > P.max_age;
-            const unsigned long long m = __ballot(sel);
-            const uint32_t at = P.rows[(size_t)b * WT_ROWS] + (uint32_t)__popcll(m & lt);
-            if (CAND) {
-                if (sel && at < C.n) {
-                    C.rec[at] = make_uint4((uint32_t)lb.rating[t][i], lb.cons[t][i], g, sl);
-                    C.age[at] = age;
-                    C.cnt[at] = 0u;
-                }
-            } else if (sel && at < P.capacity) {
-                P.out_slot[at] = sl;
-                P.out_group[at] = g;
-                P.out_age[at] = age;
-                if (GATHER) {
-                    M.rating[at] = lb.rating[t][i];
-                    M.cons[at] = (lb.cons[t][i] & M.keep) | M.to_mode;
-                    M.group[at] = (uint8_t)g;
-                    M.stamp[at] = P.now - age;
-                }
-                P.state[sl] = MM_ST_CANCELLED;
-            }
+            const WaitSeat s = wait_seat(P, c, lane);
+            uint32_t age = 0, seat_base = c.row(P)[0];
+            const bool sel = wait_age(P, s.sl, age) && wait_older(P, age);
+            const uint32_t at = wait_rank(sel, lt, seat_base);
+            if (sel) wait_scatter_put<GATHER, CAND>(P, M, C, at, c.g, s.sl, s.rt, s.cn, age);
         }
     }
 }
@@ -378,7 +468,7 @@ __global__ __launch_bounds__(SEL_TILE) void k_sel_scatter_rows(SelParams S, Move
 // mm_rotate (include/mm_wait.h): the LIVE seats of the stored lobbies of one mode leave and rejoin their own queue's
 // tail.  No queue is streamed: a chain is selected by its LobbyDev record, state[] of its seats and ChainDev.len alone, so
 // both kernels are ONE workgroup — a wave per rating group (groups wave, wave + WT_WAVES, ...), a lane per seat in
-// wait_seat's order, at most MM_MAX_GROUPS x WT_SEATS gathers in all.
+// wait_seat_at's order, at most MM_MAX_GROUPS x WT_SEATS gathers in all.
 struct RotateParams {
     uint32_t mode, n_groups, capacity, teams;
     uint32_t max_seated, min_queue;
@@ -454,8 +544,6 @@ __global__ __launch_bounds__(WT_THREADS) void k_rotate_scatter(RotateParams P, u
     }
 }
 
-static __device__ __forceinline__ uint32_t wait_bucket(uint32_t age) { return age ? 64u - (uint32_t)__clzll((long long)age) : 0u; }
-
 // mm_wait_stats: one streaming pass over the same chunks.  Counts, sums and maxima in registers, reduced per wave; the
 // histogram in LDS; a workgroup merges its chunk into the group's record with one atomic per non-empty field.
 __global__ __launch_bounds__(WT_THREADS) void k_wait_stats(WaitParams P)
@@ -463,50 +551,45 @@ __global__ __launch_bounds__(WT_THREADS) void k_wait_stats(WaitParams P)
     __shared__ uint32_t s_hist[33];
     __shared__ uint32_t s_cnt, s_max;
     __shared__ unsigned long long s_sum;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = wait_wave();
     for (uint32_t b = blockIdx.x;; b += gridDim.x) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
+        WaitChunk c;
+        if (!wait_chunk(P, b, c)) return;
         if (tid < 33) s_hist[tid] = 0;
         if (tid == 0) { s_cnt = 0; s_max = 0; s_sum = 0; }
         __syncthreads();
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        const uint32_t w0 = c.first(wave);
         uint32_t cnt = 0, mx = 0;
         unsigned long long sum = 0;
-        if (wave == 0 && k == 0u && (uint32_t)lane < WT_SEATS) {
+        if (c.seats(wave)) {
             uint32_t age = 0;
-            if (wait_age(P, wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane), age)) {
+            if (wait_age(P, wait_seat(P, c, lane).sl, age)) {
                 cnt = 1; mx = age; sum = age;
                 atomicAdd(&s_hist[wait_bucket(age)], 1u);
             }
         }
-        if (w0 < len) {
-            uint32_t sl[WT_ITERS], age[WT_ITERS];
-            const uint32_t live = wait_load(P, qo, w0, len, lane, sl, age);
+        if (w0 < c.len) {
+            WaitRows R;
+            const uint32_t live = wait_load<WL_AGE>(P, c, w0, lane, R);
 #pragma unroll
             for (uint32_t r = 0; r < WT_ITERS; ++r)
                 if ((live >> r) & 1u) {
                     ++cnt;
-                    mx = age[r] > mx ? age[r] : mx;
-                    sum += age[r];
-                    atomicAdd(&s_hist[wait_bucket(age[r])], 1u);
+                    mx = R.age[r] > mx ? R.age[r] : mx;
+                    sum += R.age[r];
+                    atomicAdd(&s_hist[wait_bucket(R.age[r])], 1u);
                 }
         }
-        for (int d = 32; d >= 1; d >>= 1) {
-            const uint32_t c2 = (uint32_t)__shfl((int)cnt, lane ^ d), m2 = (uint32_t)__shfl((int)mx, lane ^ d);
-            const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)sum, lane ^ d), hi = (uint32_t)__shfl((int)(uint32_t)(sum >> 32), lane ^ d);
-            cnt += c2;
-            mx = m2 > mx ? m2 : mx;
-            sum += ((unsigned long long)hi << 32) | lo;
-        }
+        cnt = wait_wave_sum(cnt, lane);
+        mx = wait_wave_max(mx, lane);
+        sum = wait_wave_sum64(sum, lane);
         if (lane == 0 && cnt) {
             atomicAdd(&s_cnt, cnt);
             atomicMax(&s_max, mx);
             atomicAdd(&s_sum, sum);
         }
         __syncthreads();
-        WaitGroupDev* const out = P.stats + g;
+        WaitGroupDev* const out = P.stats + c.g;
         if (tid < 33 && s_hist[tid]) atomicAdd(&out->hist[tid], s_hist[tid]);
         if (tid == 64 && s_cnt) {
             atomicAdd(&out->waiting, s_cnt);
@@ -557,81 +640,36 @@ __global__ __launch_bounds__(WT_THREADS) void k_loc_mark(LocParams L, uint32_t c
     if (s < capacity) L.tag[s] = i + 1u;      // among duplicates any one winner will do (k_loc_collect)
 }
 
-// A wave's WT_PER_WAVE queue entries from w0 on, as wait_load reads them: the slots, then state[slot] and (TAGS) tag[slot] —
-// every load of a level issued before the first one is used.  Bit r of the result: this lane's entry r is LIVE.
-template <bool TAGS>
-static __device__ __forceinline__ uint32_t loc_load(const WaitParams& P, const uint32_t* __restrict__ tag, size_t qo, uint32_t w0,
-                                                    uint32_t len, int lane, uint32_t (&sl)[WT_ITERS], uint32_t (&tg)[WT_ITERS])
-{
-    uint8_t st[WT_ITERS];
-#pragma unroll
-    for (uint32_t r = 0; r < WT_ITERS; ++r) {
-        const uint32_t i = w0 + r * 64 + lane;
-        sl[r] = i < len ? P.q_slot[qo + i] : MM_NO_SLOT;
-    }
-#pragma unroll
-    for (uint32_t r = 0; r < WT_ITERS; ++r) {
-        const bool in = sl[r] < P.capacity;
-        st[r] = in ? P.state[sl[r]] : (uint8_t)MM_ST_FREE;
-        tg[r] = TAGS && in ? tag[sl[r]] : 0u;
-    }
-    uint32_t live = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < WT_ITERS; ++r)
-        if (st[r] == MM_ST_LIVE) live |= 1u << r;
-    return live;
-}
-
-// k_wait_count's shape with the predicate "LIVE" and no age; the seats row counts 0 (a seat has nobody ahead).
-__global__ __launch_bounds__(WT_THREADS) void k_loc_count(WaitParams P)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
-        uint32_t cnt = 0;
-        if (w0 < len) {
-            uint32_t sl[WT_ITERS], tg[WT_ITERS];
-            const uint32_t live = loc_load<false>(P, nullptr, qo, w0, len, lane, sl, tg);
-#pragma unroll
-            for (uint32_t r = 0; r < WT_ITERS; ++r) cnt += (uint32_t)__popcll(__ballot((live >> r) & 1u));
-        }
-        if (lane == 0) P.rows[(size_t)b * WT_ROWS + 1u + wave] = cnt;
-        if (tid == 0) P.rows[(size_t)b * WT_ROWS] = 0u;
-    }
-}
+// k_wait_count's body with the predicate "LIVE" and no age; the seats' row counts 0 (a seat has nobody ahead).
+__global__ __launch_bounds__(WT_THREADS) void k_loc_count(WaitParams P) { wait_count_body<false, false>(P); }
 
 __global__ __launch_bounds__(WT_THREADS) void k_loc_scatter(WaitParams P, LocParams L)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = wait_wave();
     const unsigned long long lt = (1ull << lane) - 1ull;
     for (uint32_t b = blockIdx.x;; b += gridDim.x) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
-        if (w0 < len) {
+        WaitChunk c;
+        if (!wait_chunk(P, b, c)) return;
+        const uint32_t w0 = c.first(wave);
+        if (w0 < c.len) {
             // LIVE entries of this queue in front of the wave: its scanned rank less the rank of the group's first queue row
-            uint32_t base = L.want_ahead ? P.rows[(size_t)b * WT_ROWS + 1u + wave] - P.rows[(size_t)(b - k) * WT_ROWS + 1u] : 0u;
-            uint32_t sl[WT_ITERS], tg[WT_ITERS];
-            const uint32_t live = loc_load<true>(P, L.tag, qo, w0, len, lane, sl, tg);
+            uint32_t base = L.want_ahead ? c.row(P)[1 + wave] - c.group_row(P)[1] : 0u;
+            WaitRows R;
+            const uint32_t live = wait_load<WL_TAG>(P, c, w0, lane, R, nullptr, nullptr, L.tag);
 #pragma unroll
             for (uint32_t r = 0; r < WT_ITERS; ++r) {
                 const bool lv = (live >> r) & 1u;
-                const unsigned long long m = __ballot(lv);
-                if (tg[r])
-                    loc_write(L, tg[r] - 1u, LOC_QUEUE | (lv ? 0u : LOC_MARKED), g, w0 + r * 64 + (uint32_t)lane,
-                              base + (uint32_t)__popcll(m & lt), P.stamp ? P.now - P.stamp[sl[r]] : 0u);
-                base += (uint32_t)__popcll(m);
+                const uint32_t ahead = wait_rank(lv, lt, base);
+                if (R.tg[r])
+                    loc_write(L, R.tg[r] - 1u, LOC_QUEUE | (lv ? 0u : LOC_MARKED), c.g, w0 + r * 64 + (uint32_t)lane, ahead,
+                              P.stamp ? P.now - P.stamp[R.sl[r]] : 0u);
             }
         }
-        if (wave == 0 && k == 0u && (uint32_t)lane < WT_SEATS) {
-            const uint32_t sl = wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane);
+        if (c.seats(wave)) {
+            const uint32_t sl = wait_seat(P, c, lane).sl;
             const uint32_t tg = sl < P.capacity ? L.tag[sl] : 0u;
             if (tg)
-                loc_write(L, tg - 1u, LOC_LOBBY | (P.state[sl] == MM_ST_LIVE ? 0u : LOC_MARKED), g, (uint32_t)lane, 0u,
+                loc_write(L, tg - 1u, LOC_LOBBY | (P.state[sl] == MM_ST_LIVE ? 0u : LOC_MARKED), c.g, (uint32_t)lane, 0u,
                           P.stamp ? P.now - P.stamp[sl] : 0u);
         }
     }
@@ -753,16 +791,18 @@ static __device__ __forceinline__ void par_count_body(const WaitParams& P, const
     __shared__ uint32_t s_role[ROLES ? PAR_QTILE * MM_MAX_ROLES : 1];
     __shared__ uint32_t s_nk;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: what depends on the wave alone costs no lane mask
+    const int wave = wait_wave();
     const uint32_t gx = Q.gx ? Q.gx : 1u, bx = blockIdx.x % gx, by = blockIdx.x / gx, gy = gridDim.x / gx;
     const uint32_t n_tiles = (Q.n + PAR_QTILE - 1u) / PAR_QTILE;
     if (by >= gy) return;
     for (uint32_t b = bx;; b += gx) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
-        const bool rows = w0 < len, seats = wave == 0 && k == 0u;
+        WaitChunk c;
+        if (!wait_chunk(P, b, c)) return;
+        const uint32_t w0 = c.first(wave), g = c.g;
+        const bool rows = w0 < c.len, seats = c.seats(wave);
+        // The load and the seats in lines of this body's own, not wait_load<WL_ROW> and wait_seat: through them k_par_count_gap
+        // measured 0.2 to 0.3 % above the parent in every set, at a spread of 0.04 % (profiles/wait_walk_refactor_check.txt).
+        const size_t qo = c.qo(P);
         uint32_t sl[WT_ITERS], cn[WT_ITERS];
         int32_t rt[WT_ITERS];
         uint32_t s_sl = MM_NO_SLOT, s_cn = PAR_DEAD;
@@ -771,7 +811,7 @@ static __device__ __forceinline__ void par_count_body(const WaitParams& P, const
 #pragma unroll
             for (uint32_t r = 0; r < WT_ITERS; ++r) {
                 const uint32_t i = w0 + r * 64 + lane;
-                const bool in = i < len;
+                const bool in = i < c.len;
                 sl[r] = in ? P.q_slot[qo + i] : MM_NO_SLOT;
                 rt[r] = in ? Q.q_rating[qo + i] : 0;
                 cn[r] = in ? Q.q_cons[qo + i] : 0u;
@@ -782,13 +822,13 @@ static __device__ __forceinline__ void par_count_body(const WaitParams& P, const
 #pragma unroll
             for (uint32_t r = 0; r < WT_ITERS; ++r) cn[r] = st[r] == MM_ST_LIVE ? cn[r] & ~PAR_DEAD : PAR_DEAD;
         }
-        if (seats) {                                      // the stored lobby's seats, as k_move_scatter reads them (at most WT_SEATS: a lane past the last finds none)
-            const LobbyDev& lb = P.chains[P.mode * P.n_groups + g].lobby;
+        if (seats) {                                      // the stored lobby's seats (at most WT_SEATS: a lane past the last finds none)
+            const LobbyDev& lb = c.lobby(P);
             uint32_t t = 0, i = 0;
             if (wait_seat_at(lb, P.teams, (uint32_t)lane, t, i)) {
                 s_sl = lb.slot[t][i];
                 s_rt = lb.rating[t][i];
-                s_cn = s_sl < P.capacity && P.state[s_sl] == MM_ST_LIVE ? lb.cons[t][i] & ~PAR_DEAD : PAR_DEAD;
+                s_cn = wait_live(P, s_sl) ? lb.cons[t][i] & ~PAR_DEAD : PAR_DEAD;
             }
         }
         for (uint32_t tile = by; tile < n_tiles; tile += gy) {
@@ -860,7 +900,7 @@ __global__ __launch_bounds__(WT_THREADS) void k_par_count_all(WaitParams P, ParP
 
 // mm_partner_stats (include/mm_wait.h): mm_partners' two words for EVERY waiting player of a mode, aggregated per rating
 // group — from a sorted table of in_mode's waiting players instead of queries x group length predicate tests.  Read-only.
-//   k_fit_count    in_mode's walk, k_loc_count's shape: the LIVE entries per wave, and the LIVE seats in the seats' row; the
+//   k_fit_count    in_mode's walk, wait_count_body: the LIVE entries per wave, and the LIVE seats in the seats' row; the
 //                  unchanged k_wait_scan turns the rows into ranks with the total — the table's length — behind them;
 //   k_fit_keys     the same walk: one 64-bit key per waiting candidate at its rank (a stable compaction: the table's first
 //                  order is the walk's) — rating group << 48 | the constraint-word fields the filters compare << 32 (region
@@ -918,48 +958,28 @@ static __device__ __forceinline__ unsigned long long fit_prefix(uint32_t g, uint
 
 static __device__ __forceinline__ uint32_t fit_bias(int32_t rating) { return (uint32_t)rating ^ 0x80000000u; }
 
-__global__ __launch_bounds__(WT_THREADS) void k_fit_count(WaitParams P)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (uint32_t b = blockIdx.x;; b += gridDim.x) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
-        uint32_t cnt = 0;
-        if (w0 < len) {
-            uint32_t sl[WT_ITERS], tg[WT_ITERS];
-            const uint32_t live = loc_load<false>(P, nullptr, qo, w0, len, lane, sl, tg);
-#pragma unroll
-            for (uint32_t r = 0; r < WT_ITERS; ++r) cnt += (uint32_t)__popcll(__ballot((live >> r) & 1u));
-        }
-        if (lane == 0) P.rows[(size_t)b * WT_ROWS + 1u + wave] = cnt;
-        if (wave == 0) {
-            const uint32_t sl = k == 0u && (uint32_t)lane < WT_SEATS ? wait_seat(P.chains[P.mode * P.n_groups + g].lobby, P.teams, (uint32_t)lane) : MM_NO_SLOT;
-            const unsigned long long m = __ballot(sl < P.capacity && P.state[sl] == MM_ST_LIVE);
-            if (lane == 0) P.rows[(size_t)b * WT_ROWS] = (uint32_t)__popcll(m);
-        }
-    }
-}
+__global__ __launch_bounds__(WT_THREADS) void k_fit_count(WaitParams P) { wait_count_body<false, true>(P); }
 
 // P: the walk's parameters for in_mode, the rows scanned.
 __global__ __launch_bounds__(WT_THREADS) void k_fit_keys(WaitParams P, FitParams F)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = wait_wave();
     const unsigned long long lt = (1ull << lane) - 1ull;
     for (uint32_t b = blockIdx.x;; b += gridDim.x) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
-        uint32_t base = P.rows[(size_t)b * WT_ROWS + 1u + wave], mine = 0u;
-        if (w0 < len) {
+        WaitChunk c;
+        if (!wait_chunk(P, b, c)) return;
+        const uint32_t w0 = c.first(wave), base0 = c.row(P)[1 + wave];
+        uint32_t base = base0, mine = 0u;
+        if (w0 < c.len) {
+            // (the load in its own lines, not wait_load<WL_ROW>: through the loader's LIVE mask this kernel measured 11 to 13 % slower,
+            // 42 VGPRs for 34 — profiles/wait_walk_refactor_check.txt)
+            const size_t qo = c.qo(P);
             uint32_t sl[WT_ITERS], cn[WT_ITERS];
             int32_t rt[WT_ITERS];
 #pragma unroll
             for (uint32_t r = 0; r < WT_ITERS; ++r) {
                 const uint32_t i = w0 + r * 64 + lane;
-                const bool in = i < len;
+                const bool in = i < c.len;
                 sl[r] = in ? P.q_slot[qo + i] : MM_NO_SLOT;
                 rt[r] = in ? F.q_rating[qo + i] : 0;
                 cn[r] = in ? F.q_cons[qo + i] : 0u;
@@ -970,24 +990,21 @@ __global__ __launch_bounds__(WT_THREADS) void k_fit_keys(WaitParams P, FitParams
 #pragma unroll
             for (uint32_t r = 0; r < WT_ITERS; ++r) {
                 const bool lv = st[r] == MM_ST_LIVE;
-                const unsigned long long m = __ballot(lv);
-                const uint32_t at = base + (uint32_t)__popcll(m & lt);
-                if (lv && at < F.key_cap) F.keys_out[at] = fit_prefix(g, cn[r], F.eqmask) | fit_bias(rt[r]);
-                base += (uint32_t)__popcll(m);
-                mine += (uint32_t)__popcll(m);
+                const uint32_t at = wait_rank(lv, lt, base);
+                if (lv && at < F.key_cap) F.keys_out[at] = fit_prefix(c.g, cn[r], F.eqmask) | fit_bias(rt[r]);
             }
+            mine = base - base0;
         }
         if (wave == 0) {
-            const LobbyDev& lb = P.chains[P.mode * P.n_groups + g].lobby;
-            uint32_t sl = MM_NO_SLOT, t = 0, i = 0;
-            if (k == 0u && (uint32_t)lane < WT_SEATS && wait_seat_at(lb, P.teams, (uint32_t)lane, t, i)) sl = lb.slot[t][i];
-            const bool lv = sl < P.capacity && P.state[sl] == MM_ST_LIVE;
-            const unsigned long long m = __ballot(lv);
-            const uint32_t at = P.rows[(size_t)b * WT_ROWS] + (uint32_t)__popcll(m & lt);
-            if (lv && at < F.key_cap) F.keys_out[at] = fit_prefix(g, lb.cons[t][i], F.eqmask) | fit_bias(lb.rating[t][i]);
-            mine += (uint32_t)__popcll(m);
+            const WaitSeat s = wait_seat(P, c, lane);
+            const uint32_t seat0 = c.row(P)[0];
+            uint32_t seat_base = seat0;
+            const bool lv = wait_live(P, s.sl);
+            const uint32_t at = wait_rank(lv, lt, seat_base);
+            if (lv && at < F.key_cap) F.keys_out[at] = fit_prefix(c.g, s.cn, F.eqmask) | fit_bias(s.rt);
+            mine += seat_base - seat0;
         }
-        if (lane == 0 && mine) atomicAdd(&F.stats[g].candidates, mine);
+        if (lane == 0 && mine) atomicAdd(&F.stats[c.g].candidates, mine);
     }
 }
 
@@ -1136,103 +1153,55 @@ static __device__ __forceinline__ void fit_one(const FitParams& F, uint32_t n, u
     }
 }
 
-// MM_PARTNER_HIST's bucket: 0 for 0, else the value's bit length (wait_bucket's rule).  Not wait_bucket itself, and nothing
-// here calls __clzll: with one more caller of that header function the compiler folds it differently inside k_wait_stats,
-// whose instructions are to stay the ones they were.
-static __device__ __forceinline__ uint32_t fit_bucket(uint32_t v) { return v ? 32u - (uint32_t)__builtin_clz(v) : 0u; }
-
-static __device__ __forceinline__ uint32_t fit_wave_sum(uint32_t v, int lane)
-{
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl((int)v, lane ^ d);
-    return v;
-}
-
-static __device__ __forceinline__ uint32_t fit_wave_max(uint32_t v, int lane)
-{
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t o = (uint32_t)__shfl((int)v, lane ^ d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-static __device__ __forceinline__ unsigned long long fit_wave_sum64(unsigned long long v, int lane)
-{
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane ^ d), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane ^ d);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-
 // P: the walk's parameters for `mode`; F.keys the sorted table.
 __global__ __launch_bounds__(WT_THREADS) void k_fit_search(WaitParams P, FitParams F)
 {
     __shared__ uint32_t s_ph[33], s_gh[33];
     __shared__ uint32_t s_cnt, s_alone, s_unr, s_pmax, s_gmax;
     __shared__ unsigned long long s_psum, s_gsum;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = wait_wave();
     const uint32_t n = dev_min_u32(*F.n_keys, F.key_cap);
     for (uint32_t b = blockIdx.x;; b += gridDim.x) {
-        uint32_t g, k, len;
-        if (!wait_chunk(P, b, g, k, len)) return;
+        WaitChunk c;
+        if (!wait_chunk(P, b, c)) return;
         if (tid < 33) { s_ph[tid] = 0; s_gh[tid] = 0; }
         if (tid == 0) { s_cnt = 0; s_alone = 0; s_unr = 0; s_pmax = 0; s_gmax = 0; s_psum = 0; s_gsum = 0; }
         __syncthreads();
-        const size_t qo = (size_t)(P.mode * P.n_groups + g) * P.capacity;
-        const uint32_t w0 = k * WT_CHUNK + wave * WT_PER_WAVE;
+        const uint32_t w0 = c.first(wave);
         uint32_t cnt = 0, alone = 0, unr = 0, pmax = 0, gmax = 0;
         unsigned long long psum = 0, gsum = 0;
-        uint32_t sl[WT_ITERS + 1], cn[WT_ITERS + 1];      // the wave's queue rows; behind them the seats' row (wave 0 of the group's first chunk)
-        int32_t rt[WT_ITERS + 1];
+        WaitRows R;                                       // the wave's queue rows; in row WT_ITERS the seat (wave 0 of the group's first chunk)
         uint32_t live = 0;
-        if (w0 < len) {
-#pragma unroll
-            for (uint32_t r = 0; r < WT_ITERS; ++r) {
-                const uint32_t i = w0 + r * 64 + lane;
-                const bool in = i < len;
-                sl[r] = in ? P.q_slot[qo + i] : MM_NO_SLOT;
-                rt[r] = in ? F.q_rating[qo + i] : 0;
-                cn[r] = in ? F.q_cons[qo + i] : 0u;
-            }
-#pragma unroll
-            for (uint32_t r = 0; r < WT_ITERS; ++r)
-                if (sl[r] < P.capacity && P.state[sl[r]] == MM_ST_LIVE) live |= 1u << r;
-        }
-        if (wave == 0 && k == 0u && (uint32_t)lane < WT_SEATS) {
-            const LobbyDev& lb = P.chains[P.mode * P.n_groups + g].lobby;
-            uint32_t t = 0, i = 0;
-            if (wait_seat_at(lb, P.teams, (uint32_t)lane, t, i)) {
-                sl[WT_ITERS] = lb.slot[t][i];
-                rt[WT_ITERS] = lb.rating[t][i];
-                cn[WT_ITERS] = lb.cons[t][i];
-                if (sl[WT_ITERS] < P.capacity && P.state[sl[WT_ITERS]] == MM_ST_LIVE) live |= 1u << WT_ITERS;
-            }
+        if (w0 < c.len) live = wait_load<WL_ROW>(P, c, w0, lane, R, F.q_rating, F.q_cons);
+        if (c.seats(wave)) {
+            const WaitSeat s = wait_seat(P, c, lane);
+            R.sl[WT_ITERS] = s.sl; R.rt[WT_ITERS] = s.rt; R.cn[WT_ITERS] = s.cn;
+            if (wait_live(P, s.sl)) live |= 1u << WT_ITERS;
         }
 #pragma unroll
         for (uint32_t r = 0; r <= WT_ITERS; ++r)
             if ((live >> r) & 1u) {
                 uint32_t partners, gap;
-                fit_one(F, n, g, rt[r], cn[r], partners, gap);
+                fit_one(F, n, c.g, R.rt[r], R.cn[r], partners, gap);
                 ++cnt;
                 psum += partners;
                 pmax = partners > pmax ? partners : pmax;
                 alone += partners == 0u;
-                atomicAdd(&s_ph[fit_bucket(partners)], 1u);
+                atomicAdd(&s_ph[wait_bucket(partners)], 1u);
                 if (gap == MM_NO_SLOT) ++unr;
                 else {
                     gsum += gap;
                     gmax = gap > gmax ? gap : gmax;
-                    atomicAdd(&s_gh[fit_bucket(gap)], 1u);
+                    atomicAdd(&s_gh[wait_bucket(gap)], 1u);
                 }
             }
-        cnt = fit_wave_sum(cnt, lane);
-        alone = fit_wave_sum(alone, lane);
-        unr = fit_wave_sum(unr, lane);
-        pmax = fit_wave_max(pmax, lane);
-        gmax = fit_wave_max(gmax, lane);
-        psum = fit_wave_sum64(psum, lane);
-        gsum = fit_wave_sum64(gsum, lane);
+        cnt = wait_wave_sum(cnt, lane);
+        alone = wait_wave_sum(alone, lane);
+        unr = wait_wave_sum(unr, lane);
+        pmax = wait_wave_max(pmax, lane);
+        gmax = wait_wave_max(gmax, lane);
+        psum = wait_wave_sum64(psum, lane);
+        gsum = wait_wave_sum64(gsum, lane);
         if (lane == 0 && cnt) {
             atomicAdd(&s_cnt, cnt);
             atomicAdd(&s_alone, alone);
@@ -1243,7 +1212,7 @@ __global__ __launch_bounds__(WT_THREADS) void k_fit_search(WaitParams P, FitPara
             atomicAdd(&s_gsum, gsum);
         }
         __syncthreads();
-        FitGroupDev* const out = F.stats + g;
+        FitGroupDev* const out = F.stats + c.g;
         if (tid < 33 && s_ph[tid]) atomicAdd(&out->partners_hist[tid], s_ph[tid]);
         if (tid >= 64 && tid < 64 + 33 && s_gh[tid - 64]) atomicAdd(&out->gap_hist[tid - 64], s_gh[tid - 64]);
         if (tid == 128 && s_cnt) {
