@@ -220,6 +220,8 @@ typedef struct mm_tuning {
     uint32_t team_late;         /* lobbies per pass at or under which kt_late takes over (0: never)   MM_TEAM_LATE       [6]  */
     uint32_t team_late0;        /* arrivals since a mode's last tick at or under which kt_late walks the tick from its first pass (0: never) MM_TEAM_LATE0 [512] */
     uint32_t team_cap;          /* sub-queue entries one thread of kt_f looks at per role, 1..4096    MM_TEAM_CAP        [512] */
+    /* wait layer (mm_wait.inc, include/mm_wait.h) */
+    uint32_t wait_sort_mtests;  /* mm_partners and the rule calls count from the sorted table once queries x bound reaches this many 2^20 predicate tests (0: always, 0xFFFFFFFF: never) MM_WAIT_SORT_MTESTS [2105] */
 } mm_tuning;
 
 /* Fills *t (t->size = the caller's sizeof on entry) with the defaults: the built-in values in [brackets] above, each

@@ -248,6 +248,11 @@ int mm_wait_stats(mm_engine* e, uint32_t mode, mm_wait_group* per_group);
 #define MM_AT_LOBBY  2u /* a seat of the stored lobby of (mode, group)                                                 */
 #define MM_AT_MARKED 4u /* or-ed in: cancelled / expired / moved / rotated, still listed until the mode's next tick drops it */
 
+/* mm_wait_route.route: how the last mm_partners / rule call counted its partners (mm_wait_route_get, below) */
+#define MM_ROUTE_NONE   0u /* the last such call counted nothing (n == 0, no output asked for, nobody old enough, refused) */
+#define MM_ROUTE_TILES  1u /* every query against every entry of its rating group                                          */
+#define MM_ROUTE_SORTED 2u /* binary searches in a sorted table of in_mode's waiting players (mm_partner_stats' table)     */
+
 /* Where slots[i] stands in `mode` at this moment, for i < n; each output column has n words and any
  * of them may be NULL.
  *   where     MM_AT_QUEUE or MM_AT_LOBBY, with MM_AT_MARKED or-ed in when the slot is no longer LIVE
@@ -305,9 +310,18 @@ int mm_locate(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t* slots, ui
  * with n > 0, n > capacity.  MM_ERR_STATE: the engine is poisoned by a failed tick.  MM_ERR_HIP / MM_ERR_OOM do NOT
  * poison the engine; the call's scratch (and mm_locate's) is released and the next call starts afresh.
  * Cost: mm_locate's with ahead == NULL (one stream of mode's queues, four small launches), one thread per query to
- * build its record, then one stream of in_mode's queues (slot, rating, constraint word, one gather of state[]) per
- * tile of 512 queries, each query tested against the entries of its own rating group only: queries x group length
- * predicate tests in all; one wait on the stream; nothing proportional to the capacity after the first call.
+ * build its record, then the count by one of two routes (mm_wait_route_get says which; the columns are the same words):
+ *   tiles    one stream of in_mode's queues (slot, rating, constraint word, one gather of state[]) per tile of 512
+ *            queries, each query tested against the entries of its own rating group only: queries x group length
+ *            predicate tests in all;
+ *   sorted   mm_partner_stats' table of in_mode — two streams of its queues and the radix passes, one more pass and
+ *            the role in the key when by_role is asked for — then four binary searches per query (per query and role
+ *            for by_role), each narrowed in a sample of the table held in LDS; 16 bytes of scratch per key.  Its cost
+ *            is the table's, nearly whatever n is.
+ * The sorted route is taken iff mm_tuning.wait_sort_mtests != 0xFFFFFFFF and n x bound >= wait_sort_mtests << 20,
+ * bound = min(players queued in ALL modes, entries not yet purged included; capacity) — a crude upper bound of in_mode's
+ * waiting players, the one the host knows without asking the device.  One wait on the stream either way; nothing
+ * proportional to the capacity after the first call.
  * Reference: none.  Search.Worker.status/0 (lib/search/worker.ex:115-117, :326-334) sees the depth only. */
 int mm_partners(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags, uint32_t n,
                 const uint32_t* slots, uint32_t* partners, uint32_t* by_role, uint32_t* gap);
@@ -381,9 +395,11 @@ typedef struct mm_partner_rule {
  * on it leaves the engine MM_ERR_STATE until mm_reset / mm_restore, as for the plain call.  An engine that never calls
  * them allocates and launches nothing for them; results never depend on mm_tuning; nothing new goes into a snapshot.
  * Cost: the plain call's age count, then — only when somebody is old enough — one more stream of from_mode's queues that
- * writes a record per candidate and marks nothing, one stream of in_mode's queues per tile of 512 candidates
- * (candidates x group length predicate tests, as mm_partners), a count, a scan and a scatter over the candidates.
- * Scratch is mm_partners', sized by the candidates.  Waits on the stream: mm_move_if three at the most (the candidates,
+ * writes a record per candidate and marks nothing, the partner count by one of mm_partners' two routes — tiles: one
+ * stream of in_mode's queues per tile of 512 candidates (candidates x group length predicate tests); sorted: the table
+ * of in_mode and four binary searches per candidate; chosen by mm_partners' rule with the number old enough for n —
+ * then a count, a scan and a scatter over the candidates.
+ * Scratch is mm_partners', sized by the candidates (and the table's on the sorted route).  Waits on the stream: mm_move_if three at the most (the candidates,
  * the selected — before anything is marked, for MM_ERR_FULL — and the lists); mm_expire_if and mm_move_out_if two
  * (nobody can be refused, so the selected count comes back with the lists); one when nobody is old enough.
  * Reference: none (as mm_expire, mm_move, mm_move_out); to the oracle the effect is mo_cancel plus mo_enqueue. */
@@ -392,6 +408,19 @@ int mm_move_if(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_
                const mm_partner_rule* rule, uint32_t* n_selected, uint32_t* n_refused);
 int mm_move_out_if(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
                    const mm_partner_rule* rule, uint32_t* n_selected);
+
+/* Which route the engine's last mm_partners / mm_expire_if / mm_move_if / mm_move_out_if took to its partner counts, and
+ * what the choice was made on.  Size-versioned like mm_path_stats; host state only — no device call — and diagnostics
+ * only: the route never changes a result.  MM_ERR_INVALID_ARG: e or out NULL, out->size < 8. */
+typedef struct mm_wait_route {
+    uint32_t size;       /* in: caller's sizeof; out: bytes filled */
+    uint32_t call;       /* 1 mm_partners, 2 mm_expire_if, 3 mm_move_if, 4 mm_move_out_if; 0: none yet */
+    uint32_t route;      /* MM_ROUTE_* */
+    uint32_t queries, bound, threshold;   /* what the choice was made on: n or the number old enough, the bound above, wait_sort_mtests */
+    uint32_t keys;       /* SORTED: the table's length; else 0 */
+    uint32_t passes;     /* SORTED: radix passes run; else 0 */
+} mm_wait_route;
+int mm_wait_route_get(mm_engine* e, mm_wait_route* out);
 
 /* How long the players of the last tick's lobbies had waited: L = teams * team_size words per
  * match, laid out like mm_matches' `slots`; each word is the clock at that tick minus the seated

@@ -126,6 +126,17 @@ class MMPartnerRule(C.Structure):
                 ("min_partners", C.c_uint32), ("max_partners", C.c_uint32)]
 
 
+MM_ROUTE_NONE, MM_ROUTE_TILES, MM_ROUTE_SORTED = 0, 1, 2
+
+
+class MMWaitRoute(C.Structure):
+    """include/mm_wait.h mm_wait_route: how the last mm_partners / rule call counted its partners (size-versioned)."""
+    _fields_ = [(n, C.c_uint32) for n in ("size", "call", "route", "queries", "bound", "threshold", "keys", "passes")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "size"}
+
+
 class MMError(RuntimeError):
     def __init__(self, status, where):
         self.status = int(status)
@@ -290,6 +301,9 @@ def bind(lib, prefix):
         f("move_if").restype = C.c_int
         f("move_out_if").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, rulep, u32p]
         f("move_out_if").restype = C.c_int
+    if hasattr(lib, prefix + "wait_route_get"):           # include/mm_wait.h: the route of the last partner count
+        f("wait_route_get").argtypes = [C.c_void_p, C.POINTER(MMWaitRoute)]
+        f("wait_route_get").restype = C.c_int
     return lib
 
 
@@ -681,6 +695,14 @@ class EngineBase:
         self._check(self._fn("partner_stats")(self._h, mode, in_mode, int(window or 0) & 0xFFFFFFFF,
                                               int(flags or 0) & 0xFFFFFFFF, out), "partner_stats")
         return [out[g].as_dict() for g in range(self.cfg.n_groups)]
+
+    def wait_route(self):
+        """mm_wait_route_get as a dict: which route (MM_ROUTE_*) the last partners / expire_if / move_if / move_out_if
+        took to its partner counts, and the queries, bound and threshold the choice was made on.  Diagnostics only."""
+        wr = MMWaitRoute()
+        wr.size = C.sizeof(MMWaitRoute)
+        self._check(self._fn("wait_route_get")(self._h, C.byref(wr)), "wait_route_get")
+        return wr.as_dict()
 
     def enqueue_stamped(self, rating, cons, stamp, group=None):
         """mm_enqueue_stamped: `enqueue`, every accepted player stamped stamp[i] instead of the clock.  -> slots."""

@@ -417,9 +417,18 @@ __global__ __launch_bounds__(256) void k_reset(uint32_t n_chains, ChainDev* __re
 #define WT_ROWS (WT_WAVES + 1)                // counters per chunk: the stored lobby's seats, then one per wave
 #define WT_SEATS (MM_MAX_TEAMS * 8)           // seats a LobbyDev has room for
 #define PAR_QTILE 512                         // query records a workgroup of k_par_count* stages in LDS at a time (mm_partners)
+// mm_tuning.wait_sort_mtests' built-in value: queries x bound >> 20 at which the medians of the two forced routes cross for
+// the `partners`-only question on cfg-2's 1M pool, interpolated between 1 000 queries (tiles 0.169 ms, sorted 0.237 ms) and
+// 10 000 (0.689 / 0.249) in the run that fixed it; profiles/wait_partners_sorted_1m.json, "crossing", is the run taken
+// afterwards with the value in place and gives 2200 (0.154 / 0.230 and 0.694 / 0.246): the same point to within the two
+// runs' spread.  That question crosses last (all three outputs: about 500), so the tiles route is never left too early.
+#define WAIT_SORT_MTESTS 2105u
 #define SEL_TILE 256                          // candidates per workgroup of k_sel_count / k_sel_scatter*, one per thread (mm_*_if)
 #if !defined(FIT_TILE)
 #define FIT_TILE 2048                         // keys a workgroup of k_fit_hist / k_fit_scatter handles per radix pass (mm_partner_stats)
+#endif
+#if !defined(FITQ_SAMPLE)
+#define FITQ_SAMPLE 4096                      // keys of the sorted table a workgroup of k_fit_query* stages in LDS, a power of two (32 KB)
 #endif
 #include "mm_wait.inc"
 
@@ -1146,7 +1155,7 @@ struct mm_engine {
     uint32_t dbg_last_w, dbg_last_c;   // MM_PAIR_DEBUG + MM_TEAM_BATCH=1: per-pass deltas of the F counters
     // host
     ChainDev* h_chains;        // pinned, n_chains
-    uint32_t* h_counters;      // pinned, 2
+    uint32_t* h_counters;      // pinned, 3: released slots | a count's total or the refused rows | the sorted table's length
     std::vector<uint8_t> h_state;
     uint32_t next_slot;
     uint32_t cancel_pending;
@@ -1180,6 +1189,7 @@ struct mm_engine {
     unsigned long long* d_fit_keys;   // [2][fit_cap] the table and the other half of a radix pass
     uint32_t* d_fit_hist;      // [256][tiles of fit_cap] + [256]: a pass's digit counts / offsets, the digits' totals
     uint32_t fit_cap;          // keys each half has room for (they grow)
+    mm_wait_route wr;          // mm_wait_route_get: the route of the last mm_partners / rule call (host state, diagnostics)
 };
 
 // Named ranges for a profiler's timeline (the reference logs nothing per attempt).  MM_ROCTX=1 makes
@@ -1531,6 +1541,8 @@ static const TuneDesc k_tune[] = {
     MM_TD(team_late, "MM_TEAM_LATE", 6u, 0u, 0xFFFFFFFFu, 0u),
     MM_TD(team_late0, "MM_TEAM_LATE0", 512u, 0u, 0xFFFFFFFFu, 0u),        // arrivals of a mode since its last tick at or under which kt_late walks the tick from its first pass
     MM_TD(team_cap, "MM_TEAM_CAP", TT_SCAN_CAP, 1u, 4096u, 0u),           // TeamParams.scan_cap; <= 4096: kt_f notes members as 13-bit sub-queue offsets (TF_REL_BITS)
+    // wait_sort_mtests: queries x bound >> 20 from which mm_partners and the rule calls count from the sorted table (route_sorted)
+    MM_TD(wait_sort_mtests, "MM_WAIT_SORT_MTESTS", WAIT_SORT_MTESTS, 0u, 0xFFFFFFFFu, 0u),
 };
 #undef MM_TD
 static const uint32_t k_tune_n = (uint32_t)(sizeof(k_tune) / sizeof(k_tune[0]));
@@ -1688,7 +1700,7 @@ static int engine_init(mm_engine* e)
     MMTRY(pin_alloc(e, e->h_chains, e->n_chains * sizeof(ChainDev)));
     MMTRY(pin_alloc(e, e->h_look_seq, 64));
     *e->h_look_seq = 0;
-    MMTRY(pin_alloc(e, e->h_counters, 2 * sizeof(uint32_t)));
+    MMTRY(pin_alloc(e, e->h_counters, 3 * sizeof(uint32_t)));
     e->h_state.assign(cap, MM_ST_FREE);
     e->tk_last_len.assign(e->n_chains, 0u);
     if (e->tk_memb) {
@@ -3850,6 +3862,153 @@ extern "C" int mm_locate(mm_engine* e, uint32_t mode, uint32_t n, const uint32_t
     });
 }
 
+// mm_partner_stats (include/mm_wait.h).  Its scratch: the rows and the records at the first call, the two halves of the key
+// table and a pass's digit counts grown to the longest table so far.
+static_assert(sizeof(FitGroupDev) == sizeof(mm_partner_group) && sizeof(mm_partner_group) == 304u &&
+              offsetof(FitGroupDev, partners_sum) == offsetof(mm_partner_group, partners_sum) &&
+              offsetof(FitGroupDev, gap_sum) == offsetof(mm_partner_group, gap_sum) &&
+              offsetof(FitGroupDev, partners_max) == offsetof(mm_partner_group, partners_max) &&
+              offsetof(FitGroupDev, partners_hist) == offsetof(mm_partner_group, partners_hist) &&
+              offsetof(FitGroupDev, gap_hist) == offsetof(mm_partner_group, gap_hist) && MM_PARTNER_HIST == 33u,
+              "FitGroupDev is mm_partner_group");
+static_assert(FIT_TILE % (WT_WAVES * 64) == 0 && FIT_TILE % WT_THREADS == 0 && MM_MAX_GROUPS <= 256, "a tile is whole rows of every wave; the group is one digit");
+
+static void fit_release(mm_engine* e)
+{
+    mem_release(e, e->d_fit_rows); mem_release(e, e->d_fit_stats); mem_release(e, e->d_fit_keys); mem_release(e, e->d_fit_hist);
+    e->fit_cap = 0;
+}
+
+static uint32_t fit_tiles_of(uint32_t n) { return (n + FIT_TILE - 1u) / FIT_TILE; }
+
+static int fit_alloc(mm_engine* e, uint32_t n)
+{
+    return guarded([&]() -> int {
+        if (!e->d_fit_stats) {
+            MMTRY(dev_alloc(e, e->d_fit_rows, wait_rows_bytes(e)));
+            MMTRY(dev_alloc(e, e->d_fit_stats, MM_MAX_GROUPS * sizeof(FitGroupDev)));
+        }
+        return scratch_grow(e, n, e->fit_cap, e->d_fit_keys, [](size_t rows) { return 2u * rows * sizeof(unsigned long long); },
+                            e->d_fit_hist, [](size_t rows) { return (size_t)FIT_DIGITS * (fit_tiles_of((uint32_t)rows) + 1u) * sizeof(uint32_t); });
+    });
+}
+
+// What bounds the waiting players of any one mode, known on the host: the players queued in ALL modes, entries not yet
+// purged included, and never more than there are slots.  Crude, but no device round trip.
+static uint32_t wait_bound(const mm_engine* e) { return (uint32_t)(e->live_upper < e->cfg.capacity ? e->live_upper : e->cfg.capacity); }
+
+// The sorted table of in_mode's waiting players, queued into fit_alloc's scratch (the caller has grown it to `bound` keys):
+// k_fit_count and the unchanged k_wait_scan over rows of the table's own, k_fit_keys, then the radix passes, least
+// significant byte first — the rating's four, then the bytes that are not zero in every key: the region's, the one the
+// party and (by_role: the key carries the role nibble, fit_prefix puts it at bits 44..47) the role share, the group's.
+// mm_partner_stats and the sorted route of mm_partners and the rule calls build it here.  T->F: the predicate, the table
+// (keys: the half the last pass wrote) and its length on the device; T->C: in_mode's walk; T->passes.  Neither checked
+// nor waited for: the caller's hipGetLastError and wait cover the launches.
+struct FitTable {
+    FitParams F;
+    WaitParams C;
+    uint32_t passes;
+};
+
+static void fit_table(mm_engine* e, uint32_t in_mode, uint32_t window, uint32_t flags, bool by_role, uint32_t bound, FitTable* T)
+{
+    const uint32_t G = e->cfg.n_groups;
+    T->C = walk_params(e, in_mode, e->d_fit_rows);         // the candidates' walk (rows of the call's own: the lookup's may not exist either)
+    FitParams& F = T->F;
+    memset(&F, 0, sizeof(F));
+    F.window = window;
+    F.eqmask = filter_eqmask(flags) | (by_role ? 0xFu << 16 : 0u);
+    F.key_cap = e->fit_cap;
+    F.q_rating = e->d_q_rating;
+    F.q_cons = e->d_q_cons;
+    F.n_keys = wait_total(T->C);
+    F.hist = e->d_fit_hist;
+    F.stats = e->d_fit_stats;
+    unsigned long long* half[2] = { e->d_fit_keys, e->d_fit_keys + e->fit_cap };
+    const uint32_t grid = wait_grid(e), tiles = fit_tiles_of(bound);
+    const dim3 wg(WT_THREADS), sg(tiles < 1024u ? (tiles ? tiles : 1u) : 1024u);
+    hipLaunchKernelGGL(k_fit_count, dim3(grid), wg, 0, e->stream, T->C);
+    hipLaunchKernelGGL(k_wait_scan, dim3(1), wg, 0, e->stream, T->C);
+    F.keys_out = half[0];
+    hipLaunchKernelGGL(k_fit_keys, dim3(grid), wg, 0, e->stream, T->C, F);
+    uint32_t shifts[7], n_pass = 0, at = 0;
+    for (uint32_t s = 0; s < 32u; s += 8u) shifts[n_pass++] = s;
+    if (flags & MM_MODE_REGION_FILTER) shifts[n_pass++] = 32u;
+    if ((flags & MM_MODE_PARTY_FILTER) || by_role) shifts[n_pass++] = 40u;
+    if (G > 1u) shifts[n_pass++] = 48u;
+    for (uint32_t p = 0; p < n_pass; ++p, at ^= 1u) {
+        F.shift = shifts[p];
+        F.keys = half[at];
+        F.keys_out = half[at ^ 1u];
+        hipLaunchKernelGGL(k_fit_hist, sg, wg, 0, e->stream, F);
+        hipLaunchKernelGGL(k_fit_scan, dim3(FIT_DIGITS / WT_WAVES), wg, 0, e->stream, F);
+        hipLaunchKernelGGL(k_fit_scatter, sg, wg, 0, e->stream, F);
+    }
+    F.keys = half[at];
+    F.keys_out = NULL;
+    T->passes = n_pass;
+}
+
+// ---- the route of a partner count (mm_partners, mm_expire_if, mm_move_if, mm_move_out_if): mm_wait_route_get's record ----
+
+// A call enters: it has counted nothing yet.
+static void route_enter(mm_engine* e, uint32_t call)
+{
+    memset(&e->wr, 0, sizeof(e->wr));
+    e->wr.call = call;
+}
+
+// The size rule (include/mm_wait.h): `queries` records against at most wait_bound() candidates each.  Notes the choice.
+static bool route_sorted(mm_engine* e, uint32_t queries)
+{
+    const uint32_t bound = wait_bound(e), t = e->tn.wait_sort_mtests;
+    const bool sorted = t != 0xFFFFFFFFu && (unsigned long long)queries * bound >= ((unsigned long long)t << 20);
+    e->wr.route = sorted ? MM_ROUTE_SORTED : MM_ROUTE_TILES;
+    e->wr.queries = queries;
+    e->wr.bound = bound;
+    e->wr.threshold = t;
+    return sorted;
+}
+
+// The call failed: it counted nothing one could use.
+static void route_failed(mm_engine* e) { route_enter(e, e->wr.call); }
+
+// The sorted route of a count, in k_par_count*'s place: the table of in_mode (fit_alloc's scratch, grown here), then
+// k_fit_query* over the n records of d_par_rec into Q's columns; the table's length leaves for h_counters[2] and is the
+// record's once the caller has waited (route_keys).  where: the lookup's column (mm_partners) or NULL (every record LIVE).
+static int fit_query_launch(mm_engine* e, uint32_t mode, uint32_t in_mode, const ParParams& Q, uint32_t flags, bool by_role, bool want_gap,
+                            const uint32_t* where)
+{
+    const uint32_t bound = wait_bound(e);
+    MMTRY(fit_alloc(e, bound ? bound : 1u));
+    FitTable T;
+    fit_table(e, in_mode, Q.window, flags, by_role, bound, &T);
+    FitQParams X;
+    memset(&X, 0, sizeof(X));
+    X.n = Q.n;
+    X.stride = Q.stride;
+    X.same_mode = in_mode == mode ? 1u : 0u;
+    X.want_gap = want_gap ? 1u : 0u;
+    X.n_roles = e->cfg.modes[in_mode].n_roles;
+    X.where = where;
+    X.rec = Q.rec;
+    X.out = Q.out;
+    const uint32_t per = (Q.n + WT_THREADS - 1u) / WT_THREADS;
+    const dim3 wg(WT_THREADS), qg(per < 1024u ? per : 1024u);
+    if (by_role) hipLaunchKernelGGL(k_fit_query_role, qg, wg, 0, e->stream, X, T.F);
+    else hipLaunchKernelGGL(k_fit_query, qg, wg, 0, e->stream, X, T.F);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(e->h_counters + 2, T.F.n_keys, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    e->wr.passes = T.passes;
+    return MM_OK;
+}
+
+// Behind the wait that covers fit_query_launch's copy.
+static void route_keys(mm_engine* e)
+{
+    if (e->wr.route == MM_ROUTE_SORTED) e->wr.keys = e->h_counters[2];
+}
+
 // The buffers of mm_partners, grown to the longest query so far; the lookup's scratch is loc_alloc's.
 static void par_release(mm_engine* e)
 {
@@ -3890,6 +4049,7 @@ static ParParams par_params(const mm_engine* e, uint32_t n, uint32_t window, uin
 static int partners_impl(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags, uint32_t n,
                          const uint32_t* slots, uint32_t* partners, uint32_t* by_role, uint32_t* gap)
 {
+    const bool sorted = route_sorted(e, n);
     MMTRY(loc_alloc(e, n));
     MMTRY(par_alloc(e, n));
     WaitParams P;                                              // the lookup: mm_locate's passes, `ahead` off
@@ -3902,7 +4062,10 @@ static int partners_impl(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t
     Q.loc = e->d_loc_out;
     const dim3 per_query((n + WT_THREADS - 1u) / WT_THREADS), wg(WT_THREADS), cg(count_grid);
     hipLaunchKernelGGL(k_par_gather, per_query, wg, 0, e->stream, P, Q);
-    if (by_role && gap) hipLaunchKernelGGL(k_par_count_all, cg, wg, 0, e->stream, C, Q);
+    // the count: every query against its group's entries, or — the sorted route — against in_mode's table (the role-keyed
+    // one only when by_role is asked for); the lookup's `where` column says which queries are LIVE
+    if (sorted) MMTRY(fit_query_launch(e, mode, in_mode, Q, flags, by_role != NULL, gap != NULL, e->d_loc_out));
+    else if (by_role && gap) hipLaunchKernelGGL(k_par_count_all, cg, wg, 0, e->stream, C, Q);
     else if (by_role) hipLaunchKernelGGL(k_par_count_role, cg, wg, 0, e->stream, C, Q);
     else if (gap) hipLaunchKernelGGL(k_par_count_gap, cg, wg, 0, e->stream, C, Q);
     else hipLaunchKernelGGL(k_par_count, cg, wg, 0, e->stream, C, Q);
@@ -3915,6 +4078,7 @@ static int partners_impl(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t
         HIPCHK(e, hipMemcpyAsync(by_role, e->d_par_out + 2u * (size_t)e->par_cap, (size_t)n * MM_MAX_ROLES * sizeof(uint32_t),
                                  hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    route_keys(e);
     return MM_OK;
 }
 
@@ -3922,6 +4086,7 @@ extern "C" int mm_partners(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32
                            const uint32_t* slots, uint32_t* partners, uint32_t* by_role, uint32_t* gap)
 {
     return guarded([&]() -> int {
+        if (e) route_enter(e, 1u);
         if (!e || mode >= e->cfg.n_modes || in_mode >= e->cfg.n_modes || (flags & ~(MM_MODE_REGION_FILTER | MM_MODE_PARTY_FILTER)) ||
             (n > 0u && !slots) || n > e->cfg.capacity)
             return MM_ERR_INVALID_ARG;
@@ -3929,85 +4094,22 @@ extern "C" int mm_partners(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32
         if (n == 0u || (!partners && !by_role && !gap)) return MM_OK;   // nothing asked for: nothing is launched
         return query_call(e, "mm_partners",
                           [&]() -> int { return partners_impl(e, mode, in_mode, window, flags, n, slots, partners, by_role, gap); },
-                          [&]() { loc_release(e); par_release(e); });   // (the lookup's scratch goes with this call's buffers)
-    });
-}
-
-// mm_partner_stats (include/mm_wait.h).  Its scratch: the rows and the records at the first call, the two halves of the key
-// table and a pass's digit counts grown to the longest table so far.
-static_assert(sizeof(FitGroupDev) == sizeof(mm_partner_group) && sizeof(mm_partner_group) == 304u &&
-              offsetof(FitGroupDev, partners_sum) == offsetof(mm_partner_group, partners_sum) &&
-              offsetof(FitGroupDev, gap_sum) == offsetof(mm_partner_group, gap_sum) &&
-              offsetof(FitGroupDev, partners_max) == offsetof(mm_partner_group, partners_max) &&
-              offsetof(FitGroupDev, partners_hist) == offsetof(mm_partner_group, partners_hist) &&
-              offsetof(FitGroupDev, gap_hist) == offsetof(mm_partner_group, gap_hist) && MM_PARTNER_HIST == 33u,
-              "FitGroupDev is mm_partner_group");
-static_assert(FIT_TILE % (WT_WAVES * 64) == 0 && FIT_TILE % WT_THREADS == 0 && MM_MAX_GROUPS <= 256, "a tile is whole rows of every wave; the group is one digit");
-
-static void fit_release(mm_engine* e)
-{
-    mem_release(e, e->d_fit_rows); mem_release(e, e->d_fit_stats); mem_release(e, e->d_fit_keys); mem_release(e, e->d_fit_hist);
-    e->fit_cap = 0;
-}
-
-static uint32_t fit_tiles_of(uint32_t n) { return (n + FIT_TILE - 1u) / FIT_TILE; }
-
-static int fit_alloc(mm_engine* e, uint32_t n)
-{
-    return guarded([&]() -> int {
-        if (!e->d_fit_stats) {
-            MMTRY(dev_alloc(e, e->d_fit_rows, wait_rows_bytes(e)));
-            MMTRY(dev_alloc(e, e->d_fit_stats, MM_MAX_GROUPS * sizeof(FitGroupDev)));
-        }
-        return scratch_grow(e, n, e->fit_cap, e->d_fit_keys, [](size_t rows) { return 2u * rows * sizeof(unsigned long long); },
-                            e->d_fit_hist, [](size_t rows) { return (size_t)FIT_DIGITS * (fit_tiles_of((uint32_t)rows) + 1u) * sizeof(uint32_t); });
+                          [&]() { loc_release(e); par_release(e); fit_release(e); route_failed(e); });   // (the lookup's and the table's scratch go with this call's buffers)
     });
 }
 
 static int partner_stats_impl(mm_engine* e, uint32_t mode, uint32_t in_mode, uint32_t window, uint32_t flags, mm_partner_group* per_group)
 {
-    const uint32_t G = e->cfg.n_groups, cap = e->cfg.capacity;
+    const uint32_t G = e->cfg.n_groups;
     // the table holds waiting players of one mode: never more than are queued in all of them, never more than there are slots
-    const uint32_t bound = (uint32_t)(e->live_upper < cap ? e->live_upper : cap);
+    const uint32_t bound = wait_bound(e);
     MMTRY(fit_alloc(e, bound));
-    const WaitParams C = walk_params(e, in_mode, e->d_fit_rows);   // the candidates' walk (rows of the call's own: the lookup's may not exist either)
-    const WaitParams Q = walk_over(e, C, mode);                // the queries' walk
-    FitParams F;
-    memset(&F, 0, sizeof(F));
-    F.window = window;
-    F.eqmask = filter_eqmask(flags);
-    F.self = in_mode == mode ? 1u : 0u;
-    F.key_cap = e->fit_cap;
-    F.q_rating = e->d_q_rating;
-    F.q_cons = e->d_q_cons;
-    F.n_keys = wait_total(C);
-    F.hist = e->d_fit_hist;
-    F.stats = e->d_fit_stats;
-    unsigned long long* half[2] = { e->d_fit_keys, e->d_fit_keys + e->fit_cap };
-    const uint32_t grid = wait_grid(e), tiles = fit_tiles_of(bound);
-    const dim3 wg(WT_THREADS), sg(tiles < 1024u ? tiles : 1024u);
     HIPCHK(e, hipMemsetAsync(e->d_fit_stats, 0, G * sizeof(FitGroupDev), e->stream));
-    hipLaunchKernelGGL(k_fit_count, dim3(grid), wg, 0, e->stream, C);
-    hipLaunchKernelGGL(k_wait_scan, dim3(1), wg, 0, e->stream, C);
-    F.keys_out = half[0];
-    hipLaunchKernelGGL(k_fit_keys, dim3(grid), wg, 0, e->stream, C, F);
-    // the passes, least significant byte first: the rating's four, then the bytes that are not zero in every key
-    uint32_t shifts[7], n_pass = 0, at = 0;
-    for (uint32_t s = 0; s < 32u; s += 8u) shifts[n_pass++] = s;
-    if (flags & MM_MODE_REGION_FILTER) shifts[n_pass++] = 32u;
-    if (flags & MM_MODE_PARTY_FILTER) shifts[n_pass++] = 40u;
-    if (G > 1u) shifts[n_pass++] = 48u;
-    for (uint32_t p = 0; p < n_pass; ++p, at ^= 1u) {
-        F.shift = shifts[p];
-        F.keys = half[at];
-        F.keys_out = half[at ^ 1u];
-        hipLaunchKernelGGL(k_fit_hist, sg, wg, 0, e->stream, F);
-        hipLaunchKernelGGL(k_fit_scan, dim3(FIT_DIGITS / WT_WAVES), wg, 0, e->stream, F);
-        hipLaunchKernelGGL(k_fit_scatter, sg, wg, 0, e->stream, F);
-    }
-    F.keys = half[at];
-    F.keys_out = NULL;
-    hipLaunchKernelGGL(k_fit_search, dim3(grid), wg, 0, e->stream, Q, F);
+    FitTable T;
+    fit_table(e, in_mode, window, flags, false, bound, &T);
+    const WaitParams Q = walk_over(e, T.C, mode);             // the queries' walk
+    T.F.self = in_mode == mode ? 1u : 0u;
+    hipLaunchKernelGGL(k_fit_search, dim3(wait_grid(e)), dim3(WT_THREADS), 0, e->stream, Q, T.F);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(per_group, e->d_fit_stats, G * sizeof(mm_partner_group), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -4203,7 +4305,8 @@ static bool rule_ok(const mm_engine* e, const mm_partner_rule* r)
 
 // The candidates of a rule call and their compaction, queued behind the age count that found k1 of them; nothing is
 // marked.  k_cand_scatter writes a query record, the age and a zeroed count per candidate at its rank; k_par_count streams
-// in_mode's chains against those records, exactly as mm_partners does behind its gather; k_sel_count and k_sel_scan rank
+// in_mode's chains against those records, exactly as mm_partners does behind its gather — or, on the sorted route (the
+// size rule with k1 for the queries), k_fit_query counts them from in_mode's table; k_sel_count and k_sel_scan rank
 // the candidates whose count lies in the rule's range.  The scratch is par_alloc's, sized by k1: the records in d_par_rec,
 // the counts in the `partners` column of d_par_out, the ages in its `gap` column and the ranks (k1 / 64 words and the
 // total) in its by_role columns, none of which this pass of the count fills.  *S: what the marking scatter needs.
@@ -4237,7 +4340,8 @@ static int rule_rank(mm_engine* e, const WaitParams& P, uint32_t grid, uint32_t 
     S->out_age = P.out_age;
     const dim3 wg(WT_THREADS), per_cand((k1 + SEL_TILE - 1u) / SEL_TILE), tile(SEL_TILE);
     hipLaunchKernelGGL(k_cand_scatter, dim3(grid), wg, 0, e->stream, P, src, C);
-    hipLaunchKernelGGL(k_par_count, dim3(count_grid), wg, 0, e->stream, W, Q);
+    if (route_sorted(e, k1)) MMTRY(fit_query_launch(e, P.mode, rule.in_mode, Q, rule.flags, false, false, NULL));   // (the gap column holds the ages)
+    else hipLaunchKernelGGL(k_par_count, dim3(count_grid), wg, 0, e->stream, W, Q);
     hipLaunchKernelGGL(k_sel_count, per_cand, tile, 0, e->stream, *S);
     hipLaunchKernelGGL(k_sel_scan, dim3(1), wg, 0, e->stream, *S);
     HIPCHK(e, hipGetLastError());
@@ -4264,7 +4368,9 @@ static int rule_call(mm_engine* e, const char* name, std::initializer_list<uint3
         if (rc != MM_OK && rc != MM_ERR_FULL && !*marked_on_device) {
             (void)hipStreamSynchronize(e->stream);
             par_release(e);
+            fit_release(e);
         }
+        if (rc != MM_OK) route_failed(e);
         return rc;
     });
 }
@@ -4282,6 +4388,7 @@ static int rule_mark_and_fetch(mm_engine* e, const WaitParams& P, uint32_t grid,
     HIPCHK(e, hipGetLastError());
     MMTRY(fetch_list(e, k1, nullptr, M));
     MMTRY(read_selected(e, rule_total(S), k2));
+    route_keys(e);
     if (*k2 > k1) return MM_ERR_INTERNAL;
     WaitLists& x = e->x;
     x.slot.resize(*k2); x.group.resize(*k2); x.age.resize(*k2);
@@ -4291,6 +4398,7 @@ static int rule_mark_and_fetch(mm_engine* e, const WaitParams& P, uint32_t grid,
 
 extern "C" int mm_expire_if(mm_engine* e, uint32_t mode, uint32_t max_age, const mm_partner_rule* rule, uint32_t* n_expired)
 {
+    if (e) route_enter(e, 2u);
     if (!e || mode >= e->cfg.n_modes || !rule_ok(e, rule)) return MM_ERR_INVALID_ARG;
     if (e->poisoned || !e->clock_on) return MM_ERR_STATE;
     return rule_call(e, "mm_expire_if", { n_expired }, [&](bool* marked_on_device) -> int {
@@ -4310,6 +4418,7 @@ extern "C" int mm_expire_if(mm_engine* e, uint32_t mode, uint32_t max_age, const
 extern "C" int mm_move_if(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
                           const mm_partner_rule* rule, uint32_t* n_selected, uint32_t* n_refused)
 {
+    if (e) route_enter(e, 3u);
     if (!e || from_mode >= e->cfg.n_modes || to_mode >= e->cfg.n_modes || from_mode == to_mode ||
         (cons_clear & (~MM_CONS_USER_MASK | 0xFu)) || !rule_ok(e, rule))
         return MM_ERR_INVALID_ARG;
@@ -4324,6 +4433,7 @@ extern "C" int mm_move_if(mm_engine* e, uint32_t from_mode, uint32_t to_mode, ui
         SelParams S;
         MMTRY(rule_rank(e, P, grid, k1, *rule, &S));
         MMTRY(read_selected(e, rule_total(S), &k2));
+        route_keys(e);
         if (k2 > k1) return MM_ERR_INTERNAL;
         if (k2 == 0u) return MM_OK;
         const MoveCols M = move_cols(e, cons_clear, to_mode, true);
@@ -4337,6 +4447,7 @@ extern "C" int mm_move_if(mm_engine* e, uint32_t from_mode, uint32_t to_mode, ui
 extern "C" int mm_move_out_if(mm_engine* e, uint32_t from_mode, uint32_t to_mode, uint32_t max_age, uint32_t cons_clear,
                               const mm_partner_rule* rule, uint32_t* n_selected)
 {
+    if (e) route_enter(e, 4u);
     if (!e || from_mode >= e->cfg.n_modes || to_mode >= MM_MAX_MODES || from_mode == to_mode ||
         (cons_clear & (~MM_CONS_USER_MASK | 0xFu)) || !rule_ok(e, rule))
         return MM_ERR_INVALID_ARG;
@@ -4434,6 +4545,17 @@ extern "C" int mm_path_stats_get(mm_engine* e, mm_path_stats* out)
     const uint32_t n = out->size < (uint32_t)sizeof(ps) ? out->size : (uint32_t)sizeof(ps);
     ps.size = n;
     memcpy(out, &ps, n);
+    return MM_OK;
+}
+
+// include/mm_wait.h: the route of the last mm_partners / rule call.  Host state only — no device call.
+extern "C" int mm_wait_route_get(mm_engine* e, mm_wait_route* out)
+{
+    if (!e || !out || out->size < 2u * sizeof(uint32_t)) return MM_ERR_INVALID_ARG;
+    mm_wait_route wr = e->wr;
+    const uint32_t n = out->size < (uint32_t)sizeof(wr) ? out->size & ~3u : (uint32_t)sizeof(wr);
+    wr.size = n;
+    memcpy(out, &wr, n);
     return MM_OK;
 }
 

@@ -1227,3 +1227,138 @@ __global__ __launch_bounds__(WT_THREADS) void k_fit_search(WaitParams P, FitPara
         __syncthreads();
     }
 }
+
+// The sorted route of mm_partners and the rule calls (include/mm_wait.h, mm_tuning.wait_sort_mtests): the two words of
+// fit_one PER QUERY RECORD — the n records k_par_gather / k_cand_scatter write — from the same sorted table of in_mode's
+// waiting players, in place of queries x group length predicate tests.  Two things differ from k_fit_search.
+//   self is per query, not per call: a query sits in the table exactly once iff in_mode == mode, the lookup found it
+//   (rec.z != MM_NO_SLOT) and it is LIVE — mm_partners answers MARKED queries too, and those are no candidates.  The LIVE
+//   bit is the lookup's `where` word (LOC_MARKED); the candidates of a rule call are all LIVE and pass no such column.
+//   The search is not 4 x log2(n) dependent global loads: a workgroup stages up to FITQ_SAMPLE evenly spaced keys of the
+//   table in LDS (fitq_stage), every bound is narrowed there to the stretch between two neighbouring samples and finished
+//   with the log2(n / FITQ_SAMPLE) global steps that remain; a table no longer than the sample is searched in LDS alone.
+//   The four bounds of a query are searched independently of each other (lo <= mine <= hi orders them anyway): four chains
+//   of loads in flight, not one.
+// A record with rec.z == MM_NO_SLOT keeps the preset of k_par_gather (0, the zero row, MM_NO_SLOT).
+#if !defined(FITQ_SAMPLE)
+#error "mm_wait.inc: define FITQ_SAMPLE beside FIT_TILE before including this file (mm_engine.hip does)"
+#endif
+
+struct FitQParams {
+    uint32_t n, stride;                       // query records; queries the columns of `out` have room for
+    uint32_t same_mode;                       // 1: in_mode == mode, a LIVE query that was found is in the table once
+    uint32_t want_gap;                        // 0: the gap column is not written (a rule call keeps the ages there)
+    uint32_t n_roles;                         // k_fit_query_role: the roles in_mode seats
+    const uint32_t* where;                    // [n] the lookup's `where` words; NULL: every query is LIVE (the rule calls)
+    const uint4* rec;                         // [n] as ParParams
+    uint32_t* out;                            // partners[stride] | gap[stride] | by_role[stride][MM_MAX_ROLES]
+};
+
+// The staged sample: key j * step of the n keys for j < m; step 1 and m == n while the table fits the sample.
+struct FitSample {
+    uint32_t n, step, m;
+};
+
+// Every thread of the workgroup must call it (barrier).
+static __device__ __forceinline__ FitSample fitq_stage(const FitParams& F, unsigned long long* __restrict__ s_key)
+{
+    FitSample S;
+    S.n = dev_min_u32(*F.n_keys, F.key_cap);
+    S.step = S.n > FITQ_SAMPLE ? (S.n + FITQ_SAMPLE - 1u) / FITQ_SAMPLE : 1u;
+    S.m = (S.n + S.step - 1u) / S.step;                   // <= FITQ_SAMPLE, and (m - 1) * step < n
+    for (uint32_t j = threadIdx.x; j < S.m; j += WT_THREADS) s_key[j] = F.keys[(size_t)j * S.step];
+    __syncthreads();
+    return S;
+}
+
+// fit_bound over the whole table: the first sample not below k (OVER: above k) is sample j — the bound lies behind
+// sample j - 1 and not behind sample j (behind the last sample: not behind the table's end).
+template <bool OVER>
+static __device__ __forceinline__ uint32_t fitq_bound(const FitParams& F, const FitSample& S, const unsigned long long* __restrict__ s_key,
+                                                      unsigned long long k)
+{
+    uint32_t lo = 0u, hi = S.m;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        const unsigned long long v = s_key[mid];
+        if (OVER ? v <= k : v < k) lo = mid + 1u;
+        else hi = mid;
+    }
+    const uint32_t a = lo ? (lo - 1u) * S.step + 1u : 0u, b = lo < S.m ? lo * S.step : S.n;
+    return fit_bound<OVER>(F.keys, a, b, k);
+}
+
+// fit_one for the segment `pre` (group, filter fields and, in the role-keyed table, the role): self 1 takes the query itself off.
+static __device__ __forceinline__ void fitq_one(const FitParams& F, const FitSample& S, const unsigned long long* __restrict__ s_key,
+                                                unsigned long long pre, int32_t rating, uint32_t self, bool want_gap,
+                                                uint32_t& partners, uint32_t& gap)
+{
+    long long lo = (long long)rating - (long long)F.window, hi = (long long)rating + (long long)F.window;
+    if (lo < -2147483648ll) lo = -2147483648ll;
+    if (hi > 2147483647ll) hi = 2147483647ll;
+    const uint32_t mine = fit_bias(rating);
+    const uint32_t a = fitq_bound<false>(F, S, s_key, pre | fit_bias((int32_t)lo));
+    const uint32_t b = fitq_bound<true>(F, S, s_key, pre | fit_bias((int32_t)hi));
+    partners = b - a - self;
+    gap = MM_NO_SLOT;
+    if (!want_gap) return;
+    const uint32_t e = fitq_bound<false>(F, S, s_key, pre | mine);
+    const uint32_t f = fitq_bound<true>(F, S, s_key, pre | mine);
+    if (f - e > self) { gap = 0u; return; }
+    if (e > 0u) {
+        const unsigned long long v = F.keys[e - 1u];
+        if ((v >> 32) == (pre >> 32)) gap = dev_min_u32(mine - (uint32_t)v, 0xFFFFFFFEu);
+    }
+    if (f < S.n) {
+        const unsigned long long v = F.keys[f];
+        if ((v >> 32) == (pre >> 32)) gap = dev_min_u32(gap, dev_min_u32((uint32_t)v - mine, 0xFFFFFFFEu));
+    }
+}
+
+// Is query i in the table itself?
+static __device__ __forceinline__ uint32_t fitq_self(const FitQParams& Q, uint32_t i)
+{
+    return Q.same_mode && !(Q.where && (Q.where[i] & LOC_MARKED)) ? 1u : 0u;
+}
+
+// F.keys: the sorted table of in_mode, keyed as mm_partner_stats keys it.  A thread per query record, the workgroups
+// stride over the records.
+__global__ __launch_bounds__(WT_THREADS) void k_fit_query(FitQParams Q, FitParams F)
+{
+    __shared__ unsigned long long s_key[FITQ_SAMPLE];
+    const FitSample S = fitq_stage(F, s_key);
+    for (uint32_t i = blockIdx.x * WT_THREADS + threadIdx.x; i < Q.n; i += gridDim.x * WT_THREADS) {
+        const uint4 q = Q.rec[i];
+        if (q.z == MM_NO_SLOT) continue;
+        uint32_t partners, gap;
+        fitq_one(F, S, s_key, fit_prefix(q.z, q.y, F.eqmask), (int32_t)q.x, fitq_self(Q, i), Q.want_gap != 0u, partners, gap);
+        Q.out[i] = partners;
+        if (Q.want_gap) Q.out[(size_t)Q.stride + i] = gap;
+    }
+}
+
+// by_role: the table is keyed with the role nibble in front of the filter fields (F.eqmask holds the role's bits, fit_prefix
+// puts them at 44..47), so every role of in_mode is a segment of its own — by_role[r] is the count of the query's segment
+// with role r in the role's place, partners the row's sum, gap the minimum over the roles; the query itself comes off its
+// own role's segment only.
+__global__ __launch_bounds__(WT_THREADS) void k_fit_query_role(FitQParams Q, FitParams F)
+{
+    __shared__ unsigned long long s_key[FITQ_SAMPLE];
+    const FitSample S = fitq_stage(F, s_key);
+    for (uint32_t i = blockIdx.x * WT_THREADS + threadIdx.x; i < Q.n; i += gridDim.x * WT_THREADS) {
+        const uint4 q = Q.rec[i];
+        if (q.z == MM_NO_SLOT) continue;
+        const unsigned long long pre = fit_prefix(q.z, q.y, F.eqmask) & ~(0xFull << 44);
+        const uint32_t self = fitq_self(Q, i), own = (q.y >> 16) & 0xFu;
+        uint32_t sum = 0u, near = MM_NO_SLOT;
+        for (uint32_t r = 0; r < Q.n_roles && r < MM_MAX_ROLES; ++r) {
+            uint32_t partners, gap;
+            fitq_one(F, S, s_key, pre | ((unsigned long long)r << 44), (int32_t)q.x, r == own ? self : 0u, Q.want_gap != 0u, partners, gap);
+            Q.out[2u * (size_t)Q.stride + (size_t)i * MM_MAX_ROLES + r] = partners;
+            sum += partners;
+            near = dev_min_u32(near, gap);
+        }
+        Q.out[i] = sum;
+        if (Q.want_gap) Q.out[(size_t)Q.stride + i] = near;
+    }
+}

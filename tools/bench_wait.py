@@ -51,6 +51,11 @@ extended to every waiting player plus the same bucketing.  All three must produc
 kernel-by-kernel split (key build, each radix pass, the search) comes from a kernel trace of --partner-stats-trace-run,
 handed in with --partner-stats-trace.
 
+--partners-sorted and --move-if-sorted add mm_partners and the rule calls by their two routes (include/mm_wait.h: tiles,
+sorted) and by the default size rule, on three engines of one process in turns over the pools of --partners and --move-if, with
+the product queries x bound >> 20 at which the forced routes cross — the measured value of mm_tuning.wait_sort_mtests; the
+kernels' own durations come from a kernel trace of --partners-sorted-trace-run.  --legs-only skips the clock's own legs.
+
 Usage (GPU box, repo root):  python tools/bench_wait.py [--steps 30] [--players 1000000] > profiles/wait_1m.json
                              python tools/bench_wait.py --move > profiles/wait_move_1m.json
                              python tools/bench_wait.py --carry > profiles/wait_carry_1m.json
@@ -58,7 +63,9 @@ Usage (GPU box, repo root):  python tools/bench_wait.py [--steps 30] [--players 
                              python tools/bench_wait.py --locate > profiles/wait_locate_1m.json
                              python tools/bench_wait.py --partners > profiles/wait_partners_1m.json
                              python tools/bench_wait.py --move-if > profiles/wait_move_if_1m.json
-                             python tools/bench_wait.py --partner-stats > profiles/wait_partner_stats_1m.json"""
+                             python tools/bench_wait.py --partner-stats > profiles/wait_partner_stats_1m.json
+                             python tools/bench_wait.py --legs-only --partners-sorted > profiles/wait_partners_sorted_1m.json
+                             python tools/bench_wait.py --legs-only --move-if-sorted > profiles/wait_move_if_sorted_1m.json"""
 import argparse
 import json
 import os
@@ -524,6 +531,163 @@ def measure_move_if(args, rating, cons, d_rating, d_cons, now):
     return out
 
 
+ROUTES = (("tiles", {"wait_sort_mtests": 0xFFFFFFFF}), ("sorted", {"wait_sort_mtests": 0}), ("default", None))
+ROUTE_NAMES = {0: "none", 1: "tiles", 2: "sorted"}
+
+
+def crossing(points, bound):
+    """Where the medians of the two forced routes cross, as queries x bound >> 20: linear interpolation between the two
+    measured points that bracket it.  points: [(queries, tiles_ms, sorted_ms)], queries ascending.  None: they do not cross."""
+    for (q0, t0, s0), (q1, t1, s1) in zip(points, points[1:]):
+        d0, d1 = t0 - s0, t1 - s1
+        if d0 < 0 <= d1:
+            q = q0 + (q1 - q0) * (-d0) / (d1 - d0)
+            return {"between_queries": [q0, q1], "queries": q, "mtests": int(q * bound) >> 20}
+    return None
+
+
+def measure_partners_sorted(args, rating, cons, d_rating, d_cons, now):
+    """mm_partners by its two routes and by the default rule, in turns on three engines over the same waiting pool (--partners'
+    pool: all of it queued, one player in a thousand cancelled), at the mode's own window and flags: `partners` only and all
+    three outputs, for 100 .. 100 000 queried slots and for every waiting slot.  The columns must be equal every step."""
+    from microservice_matchmaking_amd import Engine, make_config, mode_1v1
+    n = args.players
+    cap = 1 << (n - 1).bit_length()
+    cfg = make_config([mode_1v1(window=25, region_filter=True)], capacity=cap, timing=True)
+    rng = np.random.default_rng(3)
+    gone = np.zeros(cap, bool)
+    gone[rng.choice(n, size=max(n // 1000, 1), replace=False)] = True
+    waiting = np.flatnonzero(~gone[:n]).astype(np.uint32)
+    engines = {}
+    for name, tuning in ROUTES:
+        eng = engines[name] = Engine(cfg, tuning)
+        eng.clock_set(now)
+        eng.enqueue_device(d_rating, d_cons)                       # nobody ticks: all of them wait
+        eng.cancel(np.flatnonzero(gone).astype(np.uint32))
+    names = tuple(engines)
+    out = {"threshold_default": engines["default"].tuning()["wait_sort_mtests"]}
+    curve = {"count": [], "all": []}
+    for nq in sorted({min(x, waiting.size) for x in (100, 1000, 10000, 100000, waiting.size)}):
+        q = waiting if nq == waiting.size else rng.choice(waiting, size=nq, replace=False).astype(np.uint32)
+        point = {"queries": int(q.size)}
+        for question, kw in (("count", {"by_role": False, "gap": False}), ("all", {})):
+            t = {r: [] for r in names}
+            got, route = {}, {}
+            for k in range(args.warmup + args.steps):
+                for r in names[k % 3:] + names[:k % 3]:
+                    t0 = time.perf_counter()
+                    got[r] = engines[r].partners(0, q, **kw)
+                    t1 = time.perf_counter()
+                    if k >= args.warmup:
+                        t[r].append((t1 - t0) * 1e3)
+                for r in names[1:]:
+                    for c in range(3):
+                        assert (got[r][c] is None and got["tiles"][c] is None) or np.array_equal(got[r][c], got["tiles"][c]), \
+                            ("the routes differ", nq, question, r, c)
+            for r in names:
+                route[r] = engines[r].wait_route()
+            assert route["tiles"]["route"] == 1 and route["sorted"]["route"] == 2
+            best = min(med(t["tiles"]), med(t["sorted"]))
+            point[question] = {"tiles_ms": spread(t["tiles"]), "sorted_ms": spread(t["sorted"]), "default_ms": spread(t["default"]),
+                               "default_route": ROUTE_NAMES[route["default"]["route"]], "keys": route["sorted"]["keys"],
+                               "passes": route["sorted"]["passes"], "bound": route["sorted"]["bound"],
+                               "sorted_over_tiles": med(t["sorted"]) / med(t["tiles"]), "default_over_better": med(t["default"]) / best}
+            curve[question].append((int(q.size), med(t["tiles"]), med(t["sorted"])))
+            print("partners_sorted %d %s: %s" % (q.size, question, {r: round(med(t[r]), 3) for r in names}), file=sys.stderr, flush=True)
+        out["%d_queries" % q.size] = point
+    bound = min(n, cap)
+    out["crossing"] = {question: crossing(pts, bound) for question, pts in curve.items()}
+    out["note"] = ("host time around the calls, the wrapper's numpy buffers included; %d players waiting in %d queues, %d of them "
+                   "cancelled and not yet purged, capacity %d, window 25 and the region filter; three engines with the same pool, "
+                   "wait_sort_mtests 0xFFFFFFFF (tiles), 0 (sorted) and the built-in default, called in turns; crossing: the "
+                   "product queries x bound >> 20 at which the forced routes' medians cross" % (n, int(cfg.n_groups), int(gone.sum()), cap))
+    for eng in engines.values():
+        eng.close()
+    return out
+
+
+def measure_move_if_sorted(args, rating, cons, d_rating, d_cons, now):
+    """mm_move_if and mm_expire_if by the two routes and by the default rule, in turns on three engines: --move-if's pool (cfg-2
+    as mode 0 with a wider 1v1 as the fallback, all of it waiting, 1 000 entries cancelled), the oldest 0 %, 1 %, 10 % and
+    100 % old enough, the rule "nobody here fits me" at the mode's own window and filter.  The lists must be equal every step."""
+    from microservice_matchmaking_amd import Engine, make_config, mode_1v1
+    n = args.players
+    cap = 2 << (n - 1).bit_length()
+    cfg = make_config([mode_1v1(window=25, region_filter=True), mode_1v1(window=100)], capacity=cap, timing=True)
+    rng = np.random.default_rng(3)
+    gone_slots = np.sort(rng.choice(n, size=min(1000, n), replace=False)).astype(np.uint32)
+    gone = np.zeros(n, bool)
+    gone[gone_slots] = True
+    engines = {name: Engine(cfg, tuning) for name, tuning in ROUTES}
+    names = tuple(engines)
+    rule = {"in_mode": 0, "min_partners": 0, "max_partners": 0}
+    out = {"threshold_default": engines["default"].tuning()["wait_sort_mtests"]}
+    for label, frac in (("0pct", 0.0), ("1pct", 0.01), ("10pct", 0.1), ("100pct", 1.0)):
+        old = int(n * frac)
+        point = {"old_enough": int(old - gone[:old].sum())}
+        for call in ("move_if", "expire_if"):
+            t = {r: [] for r in names}
+            seen, route = {}, {}
+            for k in range(args.warmup + args.steps):
+                for r in names[k % 3:] + names[:k % 3]:
+                    eng = engines[r]
+                    eng.reset()
+                    now += 10
+                    eng.clock_set(now)
+                    if old:
+                        eng.enqueue_device(d_rating[:old], d_cons[:old])
+                    now += 100
+                    eng.clock_set(now)
+                    if old < n:
+                        eng.enqueue_device(d_rating[old:], d_cons[old:])
+                    eng.cancel(gone_slots)
+                    t0 = time.perf_counter()
+                    got = eng.move_if(0, 1, 50, 0, rule) if call == "move_if" else eng.expire_if(0, 50, rule)
+                    t1 = time.perf_counter()
+                    seen[r] = got
+                    route[r] = eng.wait_route()
+                    if k >= args.warmup:
+                        t[r].append((t1 - t0) * 1e3)
+                for r in names[1:]:
+                    for c in range(len(seen["tiles"])):
+                        assert np.array_equal(seen[r][c], seen["tiles"][c]), ("the routes differ", label, call, r, c)
+            best = min(med(t["tiles"]), med(t["sorted"]))
+            point[call] = {"selected": int(seen["tiles"][0].size), "tiles_ms": spread(t["tiles"]), "sorted_ms": spread(t["sorted"]),
+                           "default_ms": spread(t["default"]), "default_route": ROUTE_NAMES[route["default"]["route"]],
+                           "sorted_route": ROUTE_NAMES[route["sorted"]["route"]], "keys": route["sorted"]["keys"],
+                           "sorted_over_tiles": med(t["sorted"]) / med(t["tiles"]), "default_over_better": med(t["default"]) / best}
+            print("move_if_sorted %s %s: %s" % (label, call, {r: round(med(t[r]), 3) for r in names}), file=sys.stderr, flush=True)
+        out[label] = point
+    out["note"] = ("host time around the calls, the wrapper's numpy buffers included; %d players waiting in mode 0, %d of them "
+                   "cancelled, capacity %d, window 25 and the region filter, the rule [0, 0] in from_mode; three engines, "
+                   "wait_sort_mtests 0xFFFFFFFF (tiles), 0 (sorted) and the built-in default, in turns; nobody old enough: no "
+                   "count runs on either route" % (n, int(gone.sum()), cap))
+    for eng in engines.values():
+        eng.close()
+    return out
+
+
+def partners_sorted_trace_run(args):
+    """Only mm_partners on the sorted route, --steps times at 100 000 queries with all three outputs and with the count alone,
+    on --partners-sorted's pool: the run to trace."""
+    import torch
+    from microservice_matchmaking_amd import Engine, make_config, mode_1v1
+    from microservice_matchmaking_amd.synth import make_pool
+    n = args.players
+    cap = 1 << (n - 1).bit_length()
+    cfg = make_config([mode_1v1(window=25, region_filter=True)], capacity=cap, timing=True)
+    rating, cons = make_pool(n, seed=1)
+    rng = np.random.default_rng(3)
+    with Engine(cfg, {"wait_sort_mtests": 0}) as eng:
+        eng.clock_set(1)
+        eng.enqueue_device(torch.from_numpy(rating).cuda(), torch.from_numpy(cons.view(np.int32)).cuda())
+        q = rng.choice(n, size=min(100000, n), replace=False).astype(np.uint32)
+        for _ in range(args.steps):
+            eng.partners(0, q)
+            got = eng.partners(0, q, by_role=False, gap=False)
+    print(json.dumps({"calls": 2 * args.steps, "queries": int(q.size), "partners_mean": float(got[0].mean())}))
+
+
 def bucket_records(partners, gap, group, candidates):
     """mm_partner_group (include/mm_wait.h) per rating group, in numpy, from mm_partners' two columns over the waiting players
     and each player's rating group."""
@@ -704,12 +868,23 @@ def main():
                          "--partner-stats-trace-run, for the kernel-by-kernel split of the call")
     ap.add_argument("--partner-stats-trace-run", action="store_true",
                     help="only call mm_partner_stats --steps times on the pool of --partner-stats and exit: the run to trace")
+    ap.add_argument("--partners-sorted", action="store_true",
+                    help="also measure mm_partners by the tiles route, the sorted route and the default rule (wait_sort_mtests), "
+                         "100 queries to every waiting slot, and where the two routes cross")
+    ap.add_argument("--move-if-sorted", action="store_true",
+                    help="also measure mm_move_if and mm_expire_if by the two routes and the default rule at 0 %, 1 %, 10 % and 100 % old enough")
+    ap.add_argument("--partners-sorted-trace-run", action="store_true",
+                    help="only call mm_partners on the sorted route --steps times on the pool of --partners-sorted and exit: the run to trace")
+    ap.add_argument("--legs-only", action="store_true",
+                    help="skip the clock's own enqueue / tick / expire legs: only the legs asked for are measured and printed")
     args = ap.parse_args()
     assert args.steps >= 20, "medians of at least 20 steps"
     import torch
     assert torch.cuda.is_available(), "needs a GPU; there is no CPU path"
     if args.partner_stats_trace_run:
         return partner_stats_trace_run(args)
+    if args.partners_sorted_trace_run:
+        return partners_sorted_trace_run(args)
     from bench import kernel_source_hash
     from microservice_matchmaking_amd import Engine, make_config, mode_1v1
     from microservice_matchmaking_amd.synth import make_pool
@@ -720,6 +895,15 @@ def main():
     rating, cons = make_pool(n, seed=1)
     d_rating = torch.from_numpy(rating).cuda()
     d_cons = torch.from_numpy(cons.view(np.int32)).cuda()
+    if args.legs_only:
+        out = {"workload": "cfg-2: %d players, 1v1, +-25 rating + region filter, uniform ratings, capacity %d" % (n, cap),
+               "source_hash": kernel_source_hash(), "steps": args.steps, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
+        if args.partners_sorted:
+            out["partners_sorted"] = measure_partners_sorted(args, rating, cons, d_rating, d_cons, 1)
+        if args.move_if_sorted:
+            out["move_if_sorted"] = measure_move_if_sorted(args, rating, cons, d_rating, d_cons, 1)
+        print(json.dumps(out, indent=1))
+        return
     if args.clock_first:
         on, off = Engine(cfg), Engine(cfg)
     else:
@@ -792,6 +976,8 @@ def main():
     partners = measure_partners(args, rating, cons, d_rating, d_cons, now) if args.partners else None
     move_if = measure_move_if(args, rating, cons, d_rating, d_cons, now) if args.move_if else None
     partner_stats = measure_partner_stats(args, rating, cons, d_rating, d_cons, now) if args.partner_stats else None
+    partners_sorted = measure_partners_sorted(args, rating, cons, d_rating, d_cons, now) if args.partners_sorted else None
+    move_if_sorted = measure_move_if_sorted(args, rating, cons, d_rating, d_cons, now) if args.move_if_sorted else None
 
     bucket = med(rows["off"]["bucket_ms"])
     out = {
@@ -827,6 +1013,10 @@ def main():
         out["move_if"] = move_if
     if partner_stats is not None:
         out["partner_stats"] = partner_stats
+    if partners_sorted is not None:
+        out["partners_sorted"] = partners_sorted
+    if move_if_sorted is not None:
+        out["move_if_sorted"] = move_if_sorted
     print(json.dumps(out, indent=1))
     off.close()
     on.close()
